@@ -12,7 +12,11 @@ flat-arena all-reduce overlaps the last micro-batch's backward, then grad-norm +
 Inputs are synthetic fp32 volumes already resident in HBM; weights are the reference's random init; masking noise comes
 from the device RNG inside the timed region.  Rank 0 prints ONE JSON line.
 
-The line also carries
+A plain run sets up, warms up, times the --steps steps and prints the line: `value` (volumes/s), `ms_per_step` (wall clock of one
+timed step), the loss of the last micro-batch, the loss-scale state and the memory peak.  --dump-outputs DIR also writes what the
+last timed step computed (see dump_outputs) after the timed region.  Everything else below runs only with --full.
+
+With --full the line also carries
   roofline     -- the dominant kernel of the timed region (by summed device time, measured with HIP events recorded on the
                   launch stream around every 5th call of each MFMA entry point): algorithmic FLOP / measured time vs the dense
                   bf16 MFMA peak.  `rocprof_kernels` names the kernel(s) one call launches (the fused attention backward is
@@ -22,6 +26,7 @@ The line also carries
                   8 TB/s HBM3E peak, `traffic` = its PMC bytes per launch
   cpu_baseline -- the CPU oracle (oracle/mae3d_ref.py, a port of the reference's non-flash model) timed on this host's
                   cores for ONE volume forward+backward (rank 0, N = 1 only)
+  board, kernels, attention_qk_pv, per_rank_proxy, parity_compliant, small_batch -- see where each is built below
 """
 import argparse
 import json
@@ -337,6 +342,52 @@ def small_batch_record(model, opt, scaler, params, dev):
     return rec
 
 
+DUMP_PRED_SAMPLES = 1 << 22         # elements of pred written by dump_outputs (16 MiB in fp32)
+DUMP_PER_TENSOR = 4096              # elements per parameter / gradient tensor
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 2024
+
+
+def dump_outputs(out_dir, loss, pred, mask, model):
+    """What the last timed step handed its caller, as float32 .npy files under `out_dir`, so that two builds can be compared output
+    for output: loss (the last micro-batch's), pred (a fixed, seeded sample of its elements when it holds more than
+    DUMP_PRED_SAMPLES), mask (whole), and a seeded sample of DUMP_PER_TENSOR elements of every parameter and its gradient after the
+    optimizer step, in named_parameters() order.  The sample positions depend only on the shapes, never on the values."""
+    import numpy as np
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    arrays = {"loss": np.asarray(float(loss.detach()), dtype=np.float32),
+              "mask": mask.detach().float().cpu().numpy()}
+    pred = pred.detach()
+    n = pred.numel()
+    if n <= DUMP_PRED_SAMPLES:
+        arrays["pred"] = pred.float().cpu().numpy()
+    else:
+        idx = torch.randint(0, n, (DUMP_PRED_SAMPLES,), generator=g).sort().values
+        coords = []
+        for size in reversed(pred.shape):              # flat index -> one index per dimension, without copying pred
+            coords.append(idx % size)
+            idx = idx // size
+        coords = [c.to(pred.device) for c in reversed(coords)]
+        arrays["pred"] = pred[tuple(coords)].float().cpu().numpy()
+    ps, gs = [], []
+    for _, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        sel = torch.randint(0, flat.numel(), (DUMP_PER_TENSOR,), generator=g).sort().values if flat.numel() > DUMP_PER_TENSOR else None
+        pick = (lambda t: t) if sel is None else (lambda t: t[sel.to(t.device)])
+        ps.append(pick(flat).float().cpu())
+        if p.grad is not None:
+            gs.append(pick(p.grad.detach().reshape(-1)).float().cpu())
+    arrays["params"] = torch.cat(ps).numpy()
+    if gs:
+        arrays["grads"] = torch.cat(gs).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"dump_outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -374,7 +425,16 @@ def main():
     ap.add_argument("--same-data", action="store_true",
                     help="diagnostic: every rank draws the SAME volumes (seed without the rank) -- with identical weights and masking "
                          "noise the ranks' losses must then be bit-equal (comm.last_loss_min_max_over_ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: the parity_compliant child run, per-kernel timing (roofline, kernels, "
+                         "attention_qk_pv), board power and clock, per_rank_proxy, small_batch and cpu_baseline (each still subject "
+                         "to its --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, pred, mask, sampled parameters and "
+                         "gradients) as float32 DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ONE line on stdout: RCCL prints a version banner to stdout when a communicator is created (NCCL_DEBUG=VERSION/WARN), and
     # any library may print.  File descriptor 1 is pointed at stderr for the whole run; the JSON line goes to the saved one.
@@ -385,8 +445,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     parity_compliant = None
-    if world == 1 and args.gpus == 1 and not args.no_parity_compliant and not args.force_reducer and args.global_batch == 256 \
-            and os.environ.get("OCTMAE_LIB") is None:
+    if args.full and world == 1 and args.gpus == 1 and not args.no_parity_compliant and not args.force_reducer \
+            and args.global_batch == 256 and os.environ.get("OCTMAE_LIB") is None:
         parity_compliant = run_parity_compliant_child(args)          # BEFORE this process touches the GPU; the child has it to itself
     local_rank = 0 if args.gloo_one_gpu else int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("OCTMAE_BENCH_FORCE_LOCAL_RANK") is not None:      # tests: several ranks on one GPU with the NATIVE backend selected
@@ -507,13 +567,18 @@ def main():
             t.record_stream(torch.cuda.current_stream())
             return t
 
-        def step_(exchange=True):
+        def step_(exchange=True, keep=None):
+            """keep: a dict that receives the last micro-batch's pred and mask (--dump-outputs; asked on the last timed step only,
+            so that no step holds a previous step's pred)"""
             opt.zero_grad()
             last = None
             for i in range(accum_):
                 if os.environ.get("OCTMAE_BENCH_FAKE_OOM") and mb == 128:     # exercises the fallback (tests only)
                     raise torch.OutOfMemoryError("simulated")
-                loss_, _, _ = model(fetch(i), mask_ratio=0.75)
+                loss_, pred_, mask_ = model(fetch(i), mask_ratio=0.75)
+                if keep is not None and i == accum_ - 1:
+                    keep.update(pred=pred_, mask=mask_)
+                del pred_, mask_
                 last = loss_
                 scaler(loss_ / accum_, opt, parameters=params, update_grad=(exchange and i == accum_ - 1), clip_grad=args.clip_grad)
             if exchange and scaler.enabled and scaler.last_step_skipped:
@@ -546,19 +611,23 @@ def main():
             step()
         fence()
         break
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         ops.KTIMER = ops.KernelTimer()
     if reducer is not None:
         reducer.timing = True       # device events around every gradient chunk's exchange and around finish()'s wait (timed steps only)
-    board = BoardSampler(local_rank) if rank == 0 else None
+    board = BoardSampler(local_rank) if rank == 0 and args.full else None
     if board is not None:
         board.start()
+    kept = {}
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for s in range(args.steps):
+        loss = step(keep=kept if args.dump_outputs and s == args.steps - 1 else None)
     fence()
     dt = time.perf_counter() - t0
     board_stats = board.stop() if board is not None else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, kept["pred"], kept["mask"], model)
+    kept.clear()
     comm_timing = None
     if reducer is not None:
         reducer.timing = False
@@ -602,7 +671,7 @@ def main():
     # 256 / N in one micro-batch -- timed on this GPU with the same model, optimizer and kernels; the ratio of its rate to the
     # 256-volume rate is the scaling efficiency before any exposed communication.
     proxy = None
-    if world == 1 and not args.no_per_rank_proxy and args.global_batch == 256:
+    if args.full and world == 1 and not args.no_per_rank_proxy and args.global_batch == 256:
         proxy = {}
         main_rate = args.steps * args.global_batch / dt
         for n_ranks in (2, 4, 8):
@@ -622,7 +691,7 @@ def main():
             del pstep
 
     small_batch = None
-    if world == 1 and not args.no_small_batch and args.global_batch == 256 and not use_dist:
+    if args.full and world == 1 and not args.no_small_batch and args.global_batch == 256 and not use_dist:
         try:
             small_batch = small_batch_record(model, opt, scaler, params, dev)
         except Exception as e:      # the headline number must survive
@@ -727,7 +796,7 @@ def main():
             out["parity_compliant"] = parity_compliant
         if small_batch is not None:
             out["small_batch"] = small_batch
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # the GPU number must survive a host that cannot fit the oracle

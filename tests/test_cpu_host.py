@@ -436,3 +436,28 @@ def test_bench_parity_compliant_child_failure_is_recorded_not_raised():
     rec = bench.run_parity_compliant_child(argparse.Namespace(global_batch=256, micro_batch=0), steps=1, warmup=0)
     assert rec["dtype"] == "f16" and rec["lib"] == "liboctmae_f16.so" and rec["value"] is None
     assert "error" in rec and rec["error"]
+
+
+def test_bench_dump_outputs_writes_a_fixed_float32_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: loss, pred, mask and sampled parameters / gradients as float32 .npy files; the sample positions are
+    seeded and depend on the shapes only, so two runs (two builds) write element-for-element comparable files."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_PRED_SAMPLES", 1000)
+    monkeypatch.setattr(bench, "DUMP_PER_TENSOR", 64)
+    g = torch.Generator().manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(40, 30), torch.nn.Linear(30, 2))
+    for p in model.parameters():
+        p.grad = torch.randn(p.shape, generator=g)
+    loss, pred, mask = torch.tensor(0.25), torch.randn(3, 50, 20, generator=g), (torch.rand(3, 50, generator=g) > 0.5)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), loss, pred, mask, model)
+    bench.dump_outputs(str(tmp_path / "b"), loss, pred * 2, mask, model)
+    assert shapes == {"loss": [], "mask": [3, 50], "pred": [1000], "params": [64 + 30 + 2 + 60], "grads": [64 + 30 + 2 + 60]}
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in shapes}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert float(a["loss"]) == 0.25 and np.array_equal(a["mask"], mask.float().numpy())
+    assert np.array_equal(b["pred"], 2 * a["pred"])                 # same positions, whatever the values
+    assert set(a["pred"].tolist()) <= set(pred.reshape(-1).tolist())
+    assert np.array_equal(a["params"][64:94], model[0].bias.detach().numpy())          # small tensors whole, in parameter order
+    assert np.array_equal(a["grads"][-2:], model[1].bias.grad.numpy())

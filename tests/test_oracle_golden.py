@@ -56,10 +56,18 @@ def test_small_forward_backward_matches_reference(golden_dir):
     assert torch.equal(mask, torch.from_numpy(z["mask"]))
     assert abs(float(loss) - float(z["loss"])) <= REL * abs(float(z["loss"]))
     assert relerr(pred, z["pred"]) <= REL
+    # The key bias gets an exactly zero gradient: it shifts every score of a query row by the same q.b, which the softmax
+    # cancels.  Both sides hold fp32 summation noise there (~2e-10 of the global norm), whose pattern follows the host's thread
+    # count, so those tensors are held to an absolute bound against the global gradient norm instead of a relative error.
+    gall = sum(float(z[f"gnorm/{k}"]) ** 2 for k in grads) ** 0.5
+    zero_bound = 1e-8 * gall
     for k, g in grads.items():
         mine, ref, gn = golden_grad(z, k, g)
         if gn == 0.0:
             assert float(g.abs().max()) == 0.0, k
+            continue
+        if k.endswith(".attn.k.bias"):
+            assert gn <= zero_bound and float(g.double().norm()) <= zero_bound, (k, gn, float(g.double().norm()), zero_bound)
             continue
         assert relerr(mine, ref) <= 5e-5, k
         assert abs(float(g.double().norm()) - gn) <= 5e-5 * gn, k

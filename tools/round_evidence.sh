@@ -20,10 +20,10 @@ except Exception as e:
     print("ledgers:", e)
 PY
 # 2. the driver's command
-( time python bench.py > $O/${ROUND}_bench_final.json 2> $O/bench_final.err ) 2>&1 | grep real
+( time python bench.py --full > $O/${ROUND}_bench_final.json 2> $O/bench_final.err ) 2>&1 | grep real
 # 3. the same step under rocprofv3 --kernel-trace --stats
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_main -- python3 $R/bench.py --no-cpu-baseline --no-per-rank-proxy \
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_main -- python3 $R/bench.py --full --no-cpu-baseline --no-per-rank-proxy \
     --no-parity-compliant --no-small-batch --steps 1 --warmup 1 > $O/${ROUND}_bench_under_rocprof.json 2> $O/prof_main.err
 find $O/prof_main -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/${ROUND}_bench_final_kernel_stats.csv; rm -rf $O/prof_main
 # 4. one volume per step, and the per-rank shapes of 8 GPUs against the 128-volume micro-batch

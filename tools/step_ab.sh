@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 run() {
   args=""; for kv in $(echo "$1" | tr ',' ' '); do args="$args --set $kv"; done
-  python bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-per-rank-proxy $args 2>/dev/null | python -c "
+  python bench.py --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-per-rank-proxy $args 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d.get('kernels',{})
