@@ -26,8 +26,9 @@ extern "C" {
  * 8: octmae_linear_dgrad_delta, octmae_attn_bwd_fused_delta.  9: octmae_wgrad_accum_pair, octmae_wgrad_split_plan.
  * 10: octmae_lp_dtype, octmae_comm_stream, octmae_mt_adamw_fused, octmae_gemm_bf16_ws + workspace arguments.
  * 11: the small-launch GEMM kernel and its split-K workspace (octmae_gemm_split_ws_kib, octmae_gemm_small_plan, "gemm_small");
- *     the stream-K and 16x16x32 variants of round 4 / 5 left the library (octmae_gemm_streamk_*, "gemm_mfma16", "gemm_streamk"). */
-#define OCTMAE_ABI_VERSION 11
+ *     the stream-K and 16x16x32 variants of round 4 / 5 left the library (octmae_gemm_streamk_*, "gemm_mfma16", "gemm_streamk").
+ * 12: octmae_slice_pool_fwd / _bwd / _ws_floats (the slice-pooling head of the RETFound-all model). */
+#define OCTMAE_ABI_VERSION 12
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -163,6 +164,23 @@ int octmae_layernorm_bwd(const void* dy_bf16, const float* x, const float* mean,
                          float* partial_ws, int M, int D, void* stream);
 /* number of floats `partial_ws` must hold for (M, D) */
 int octmae_layernorm_bwd_ws_floats(int M, int D);
+
+/* ---- slice-pooling head ----------------------------------------------------------------------------
+ * RETFound-all (OCTCube/models_vit_3dhead_flash_attn.py:47-65 over models_vit_flash_attn.py:143-149): every slice of a volume is
+ * its own image; x f32 [B*S][T][D] is the final token stream of all B*S slices (T = 1 + L, token 0 = cls).
+ *   pooled[s] = mean of x[s][1..T-1]  (cls = 0)   or   x[s][0]  (cls = 1; LayerNorm of the cls row alone = norm(x)[:, 0])
+ *   out f32 [B][D] = (1/S) sum over the S slices of volume b of LayerNorm(pooled[s]; gamma, beta, eps)     (fc_norm, slice mean)
+ * fwd saves pooled f32 [B*S][D] and its LayerNorm statistics mean / rstd f32 [B*S] for the backward.
+ * bwd: dx f32 [B*S][T][D] (written densely: the LayerNorm backward of dout[b] / S, divided by T-1 on tokens 1..T-1 and exact zeros
+ *      on token 0 -- or on token 0 only in cls mode); optional 16-bit copy of dx (dx_bf16, NULL = none); dgamma / dbeta / dxsum
+ *      (the column sums of dx over all rows) are ACCUMULATED (+=) when non-NULL.  All reductions run in a fixed order through the
+ *      caller's workspace `ws` (no atomics: results are bit-reproducible).  D % 4 == 0, D <= 2048. */
+int octmae_slice_pool_ws_floats(int BS, int T, int D);     /* floats `ws` must hold (forward and backward), BS = B * S */
+int octmae_slice_pool_fwd(const float* x, const float* gamma, const float* beta, float* out, float* pooled, float* mean,
+                          float* rstd, float* ws, int B, int S, int T, int D, int cls, float eps, void* stream);
+int octmae_slice_pool_bwd(const float* dout, const float* pooled, const float* mean, const float* rstd, const float* gamma,
+                          float* dx, void* dx_bf16, float* dgamma, float* dbeta, float* dxsum, float* ws, int B, int S, int T,
+                          int D, int cls, void* stream);
 
 /* ---- attention -----------------------------------------------------------------------------------
  * softmax(q k^T * scale) v, non-causal, no dropout: video_vit.py:130-134 (flash path: flash_attn MHA,

@@ -457,6 +457,39 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres=None, want_bf16=
     return dx, dxb
 
 
+
+def slice_pool_fwd(x: torch.Tensor, gamma, beta, eps: float, S: int, cls: bool):
+    """x fp32 [B*S, T, D] -> out fp32 [B, D] = mean over the S slices of LayerNorm(mean of tokens 1..T-1, or token 0); with the
+    pooled rows and their LayerNorm statistics (saved for the backward)."""
+    BS, T, D = x.shape
+    if BS % S:
+        raise RuntimeError(f"slice_pool: {BS} rows are not a whole number of volumes of {S} slices")
+    B = BS // S
+    out = torch.empty((B, D), dtype=F32, device=x.device)
+    pooled = torch.empty((BS, D), dtype=F32, device=x.device)
+    mean = torch.empty((BS,), dtype=F32, device=x.device)
+    rstd = torch.empty((BS,), dtype=F32, device=x.device)
+    ws = torch.empty((load().octmae_slice_pool_ws_floats(BS, T, D),), dtype=F32, device=x.device)
+    # algorithmic HBM bytes: x read (mean mode: every patch token; cls mode: one row per slice)
+    _launch(f"pool_fwd_d{D}", 0.0, 4.0 * BS * (1 if cls else T - 1) * D,
+            lambda: call("octmae_slice_pool_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), pooled.data_ptr(),
+                         mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), B, S, T, D, int(cls), float(eps), _stream()))
+    return out, pooled, mean, rstd
+
+
+def slice_pool_bwd(dout, pooled, mean, rstd, gamma, T: int, S: int, cls: bool, dgamma, dbeta, want_bf16=False, dxsum=None):
+    B, D = dout.shape
+    BS = B * S
+    dx = torch.empty((BS, T, D), dtype=F32, device=dout.device)
+    dxb = torch.empty((BS, T, D), dtype=BF16, device=dout.device) if want_bf16 else None
+    ws = torch.empty((load().octmae_slice_pool_ws_floats(BS, T, D),), dtype=F32, device=dout.device)
+    # algorithmic HBM bytes: the dense dx written (fp32, + the 16-bit copy)
+    _launch(f"pool_bwd_d{D}", 0.0, (4.0 + (2.0 if want_bf16 else 0.0)) * BS * T * D,
+            lambda: call("octmae_slice_pool_bwd", dout.data_ptr(), pooled.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+                         dx.data_ptr(), _p(dxb), _p(dgamma), _p(dbeta), _p(dxsum), ws.data_ptr(), B, S, T, D, int(cls), _stream()))
+    return dx, dxb
+
+
 # optimistic (no running max) forward first, safe kernel as the device-side fallback.  Not in the half build: the un-normalised
 # P = exp2(s) of that kernel is an MFMA operand, and half ends at 65 504 = e^11.09 where bfloat16 has fp32's range (the online-max
 # kernel keeps P <= 2^8)
@@ -605,6 +638,39 @@ class LayerNormFn(torch.autograd.Function):
         dx = dx.view(ctx.shp)
         _sidecar_put(dx, dxb.view(ctx.shp), colsum)      # the producing Block's backward takes these instead of redoing them
         return dx, None, None, None
+
+
+
+class SlicePoolFn(torch.autograd.Function):
+    """out fp32 [B, D] = mean over the S slices of fc_norm(pooled slice row), pooled = mean of the patch tokens (or the cls token) of
+    x fp32 [B*S, T, D] -- the RETFound-all head (OCTCube/models_vit_3dhead_flash_attn.py:47-58 over models_vit_flash_attn.py:143-149);
+    S = 1 is the 2-D ViT's own pooling.  The backward writes the dense token gradient together with its 16-bit copy and column sums
+    for the producing Block (as LayerNormFn does)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, S, cls):
+        x = _chk(x if x.is_contiguous() else x.contiguous(), F32, "slice_pool input")
+        out, pooled, mean, rstd = slice_pool_fwd(x, gamma, beta, eps, S, cls)
+        ctx.save_for_backward(pooled, mean, rstd, gamma, beta)
+        ctx.meta = (x.shape, S, bool(cls))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        pooled, mean, rstd, gamma, beta = ctx.saved_tensors
+        shp, S, cls = ctx.meta
+        dout = dout.contiguous().float()
+        D = shp[-1]
+        want_dx = ctx.needs_input_grad[0]
+        colsum = torch.zeros(D, dtype=F32, device=dout.device) if want_dx else None
+        dx, dxb = slice_pool_bwd(dout, pooled, mean, rstd, gamma, shp[1], S, cls,
+                                 grad_buf(gamma) if ctx.needs_input_grad[1] else None,
+                                 grad_buf(beta) if ctx.needs_input_grad[2] else None, want_bf16=want_dx, dxsum=colsum)
+        notify_grad_ready((gamma, beta))
+        if not want_dx:
+            return None, None, None, None, None, None
+        _sidecar_put(dx, dxb, colsum)      # the producing Block's backward takes these instead of redoing them
+        return dx, None, None, None, None, None
 
 
 class LinearFn(torch.autograd.Function):
