@@ -188,7 +188,9 @@ int octmae_slice_pool_bwd(const float* dout, const float* pooled, const float* m
  * lse f32 [B][H][N] (natural log); rowc_ws f32 [2][B][H][N] workspace; dqkv bf16 like qkv.  HD in {32, 64}.
  * flag_ws: one int of device workspace, or NULL.  Non-NULL enables the optimistic forward: a kernel without running-max
  * tracking runs first and raises *flag_ws if any softmax row sum is not a finite positive number; the online-max kernel is
- * always enqueued behind it and returns immediately unless the flag is set (no host synchronisation). */
+ * always enqueued behind it and returns immediately unless the flag is set (no host synchronisation).  In the half build
+ * (octmae_lp_dtype() == 1) flag_ws is ignored and only the online-max kernel runs: the optimistic kernel's un-normalised P does not
+ * fit half's range (P = e^-20 rounds to zero, e^+12 overflows) and its give-up test assumes bfloat16's exponent range. */
 int octmae_attn_fwd(const void* qkv, void* o, float* lse, int* flag_ws, int B, int N, int H, int HD, float scale, void* stream);
 int octmae_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, float* rowc_ws, void* dqkv, int B,
                     int N, int H, int HD, float scale, void* stream);

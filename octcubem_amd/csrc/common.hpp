@@ -121,7 +121,9 @@ __device__ __forceinline__ float gelu_phi(float x) {
   p = fmaf(p, t, 3.989180135e-01f);
   return fmaf(u, p, 0.5f);
 }
-__device__ __forceinline__ float gelu_f(float x) { return x * gelu_phi(x); }
+// Below the clamp Phi(x) < 1.4e-5 is not resolved by the polynomial: x * Phi(-4.2) would grow with |x| (-0.87 at x = -65 504, -inf for
+// an overflowed pre-activation where the answer is -0), so the product is taken with 0 there (|gelu(x)| < 6e-5 for x < -4.2).
+__device__ __forceinline__ float gelu_f(float x) { return (x < -4.2f ? 0.0f : x) * gelu_phi(x); }
 // gelu'(x) = Phi(x) + x phi(x), nn.GELU's exact (erf) derivative (models_mae_joint_res_flash_attn.py:141 act_layer under
 // autograd).  With a = |x|: Phi(a) = 1 - phi(a) (b1 t + ... + b5 t^5), t = 1 / (1 + p a) (Abramowitz & Stegun 26.2.17,
 // |error| < 7.5e-8), so gelu'(a) = 1 - g with g = phi(a) (poly(t) - a), and gelu'(-a) = g.  1 / sqrt(2 pi) is folded into the
@@ -177,7 +179,7 @@ __device__ __forceinline__ f32x2 gelu_f2(f32x2 x) {
   p = pk_fma(p, t, splat2(9.898752642e-03f));
   p = pk_fma(p, t, splat2(-6.641823237e-02f));
   p = pk_fma(p, t, splat2(3.989180135e-01f));
-  return x * pk_fma(u, p, splat2(0.5f));
+  return f32x2{x[0] < -4.2f ? 0.0f : x[0], x[1] < -4.2f ? 0.0f : x[1]} * pk_fma(u, p, splat2(0.5f));
 }
 __device__ __forceinline__ f32x2 dgelu_poly_f2(f32x2 x) {
   const f32x2 u = {__builtin_amdgcn_fmed3f(x[0], -5.0f, 5.0f), __builtin_amdgcn_fmed3f(x[1], -5.0f, 5.0f)};

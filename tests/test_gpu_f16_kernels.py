@@ -1,0 +1,143 @@
+"""The kernel-level suites, run once more against the half-operand build (liboctmae_f16.so).
+
+tests/test_gpu_f16_parity.py runs whole models on the half build; this module runs the kernel tests themselves -- every GEMM tile
+variant, the split-K hand-off, the attention tail kernels, both backward forms, the delta epilogue, the weight-gradient pairs,
+LayerNorm, the token plumbing, AdamW, the slice-pooling kernels and the operand-type edges of tests/test_gpu_lp_edges.py -- in a child
+pytest process with OCTMAE_LIB pointing at the half build (the 16-bit type is chosen per process, before octcubem_amd is imported).
+
+The child is started once the collection is known to contain a test of this module (tests/conftest.py::pytest_collection_finish ->
+start_children()), writes its log to a file and its results to a JUnit XML file, runs under a wall-clock limit, and is reaped at
+exit.  The tests below read the XML: the child passed, every module ran at least as many tests as it holds today (a collection that
+quietly shrinks fails), and every skip is on the allowlist.
+"""
+import atexit
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import xml.etree.ElementTree as ET
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB_F16 = os.path.join(ROOT, "octcubem_amd", "liboctmae_f16.so")
+TIMEOUT_S = 1500
+
+SUITES = ["tests/test_gpu_kernels.py", "tests/test_gpu_gemm_small.py",
+          "tests/test_gpu_slicehead.py::test_slice_pool_kernels_vs_fp32_composition",
+          "tests/test_gpu_slicehead.py::test_slice_pool_sidecar_matches_its_gradient",
+          "tests/test_gpu_lp_edges.py"]
+# tests per module the child must run (passed + skipped), as collected with -m gpu when this module was written
+MIN_TESTS = {"tests.test_gpu_kernels": 529, "tests.test_gpu_gemm_small": 20, "tests.test_gpu_slicehead": 37,
+             "tests.test_gpu_lp_edges": 64}
+# (test id, skip reason) pairs the half build may skip: none today
+ALLOWED_SKIPS = set()
+
+_CHILD = {}
+
+
+def _reap():
+    c = _CHILD.get("proc")
+    if c is not None and c.poll() is None:
+        c.kill()
+        try:
+            c.wait(timeout=10)
+        except subprocess.TimeoutExpired:
+            pass
+    if "logf" in _CHILD:
+        _CHILD["logf"].close()
+
+
+def start_children():
+    """The half-build child (idempotent; nothing when the library is missing: _result() then fails with the build hint)."""
+    if _CHILD or not os.path.exists(LIB_F16):
+        return
+    tmp = tempfile.mkdtemp(prefix="octmae_f16_kernels_")
+    xml = os.path.join(tmp, "junit.xml")
+    logf = open(os.path.join(tmp, "child.log"), "wb")            # a file, not a pipe: the child never blocks on a full pipe
+    cmd = [sys.executable, "-m", "pytest", "-q", "-s", "-m", "gpu", "-p", "no:cacheprovider", f"--junitxml={xml}", *SUITES]
+    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdout=logf, stderr=subprocess.STDOUT),
+                  xml=xml, logf=logf, tmp=tmp)
+    atexit.register(_reap)
+
+
+_RESULT = {}
+
+
+def _log_tail(n=6000):
+    _CHILD["logf"].flush()
+    with open(_CHILD["logf"].name, "rb") as f:
+        text = f.read().decode(errors="replace")
+    return text if n is None else text[-n:]
+
+
+def _result():
+    if _RESULT:
+        return _RESULT
+    start_children()
+    assert _CHILD, f"{LIB_F16} is missing: build it (python -c 'import __graft_entry__ as g; g.build()' or make -C octcubem_amd/csrc both)"
+    proc = _CHILD["proc"]
+    try:
+        proc.wait(timeout=TIMEOUT_S)
+    except subprocess.TimeoutExpired:
+        proc.kill()
+        proc.wait(timeout=30)
+        pytest.fail(f"the half-build kernel suite did not finish in {TIMEOUT_S} s:\n{_log_tail()}")
+    cases = []
+    if os.path.exists(_CHILD["xml"]):
+        for tc in ET.parse(_CHILD["xml"]).getroot().iter("testcase"):
+            status, msg = "passed", ""
+            for kind in ("failure", "error", "skipped"):
+                el = tc.find(kind)
+                if el is not None:
+                    status, msg = kind, el.get("message", "")
+                    break
+            cases.append((f"{tc.get('classname')}::{tc.get('name')}", status, msg))
+    _RESULT.update(rc=proc.returncode, cases=cases)
+    # the child's parity ledger (the u-scaled errors on half, printed by its session under -s) joins this session's, which
+    # tests/conftest.py writes out at the end: one file holds both builds
+    from tests import conftest
+    m = re.search(r"^\[parity ledger\] (.*)$", _log_tail(None), re.M)
+    for entry in (m.group(1).split("; ") if m else []):
+        e = re.fullmatch(r"(\S+) (\S+) \(<= (\S+)\)", entry)
+        if e:
+            conftest._LEDGER.append((e.group(1), float(e.group(2)), float(e.group(3))))
+    print(f"\n[half-build kernel suite] exit code {proc.returncode}: " +
+          ", ".join(f"{mod} {c}" for mod, c in _counts(cases).items()))
+    return _RESULT
+
+
+def _module(case_id):
+    return case_id.split("::")[0]
+
+
+def _counts(cases):
+    c = {}
+    for cid, status, _ in cases:
+        c.setdefault(_module(cid), {}).setdefault(status, 0)
+        c[_module(cid)][status] += 1
+    return c
+
+
+def test_half_build_kernel_suite_passes():
+    r = _result()
+    bad = [cid for cid, status, _ in r["cases"] if status in ("failure", "error")]
+    assert r["rc"] == 0 and not bad and r["cases"], (f"half build: exit code {r['rc']}, {len(bad)} failing:\n" + "\n".join(bad[:40]) +
+                                                    f"\n--- child log ---\n{_log_tail()}")
+
+
+def test_half_build_ran_every_kernel_module_in_full():
+    r = _result()
+    counts = _counts(r["cases"])
+    short = {m: (sum(counts.get(m, {}).values()), n) for m, n in MIN_TESTS.items() if sum(counts.get(m, {}).values()) < n}
+    assert not short, f"modules that ran fewer tests than they hold (ran, expected): {short}\n--- child log ---\n{_log_tail()}"
+
+
+def test_half_build_skips_only_what_is_allowed():
+    r = _result()
+    skips = [(cid, msg) for cid, status, msg in r["cases"] if status == "skipped"]
+    unexpected = [s for s in skips if s not in ALLOWED_SKIPS]
+    assert not unexpected, "skips not on the allowlist:\n" + "\n".join(f"{c}: {m}" for c, m in unexpected) + f"\n--- child log ---\n{_log_tail(2000)}"

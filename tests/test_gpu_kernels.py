@@ -20,7 +20,7 @@ if torch.cuda.is_available():
 from oracle import mae3d_ref as O
 
 DEV = "cuda"
-BF16 = torch.bfloat16
+BF16 = ops.BF16 if torch.cuda.is_available() else torch.bfloat16   # the library's 16-bit operand type (OCTMAE_LIB)
 
 
 def rel(a, b):
