@@ -302,6 +302,12 @@ __global__ __launch_bounds__(256) void gather_rows_cast_kernel(const float* __re
   }
 }
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Fused patchify + masked MSE (models_mae…:289-314, :613-667).  One wave per token.
 // target[(u, py, px, c)] = imgs[b][c][fi(t*u_sz + u)][hy*p + py][wx*p + px]; fi = linspace frame select (identity
@@ -341,29 +347,30 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ pred
     const float mk = (MODE == 1) ? mask[(size_t)b * L + l] : 0.f;
     const int t = l / (gh * gw), hy = (l / gw) % gh, wx = l % gw;
     const float* pr = pred + ((size_t)b * (L + 1) + 1 + l) * PD;
-    // target statistics for norm_pix_loss (unbiased variance, torch.var default)
-    float mu = 0.f, inv = 1.f;
+    // target statistics for norm_pix_loss (unbiased variance, torch.var default), in double: pred - (target - mu) * inv cancels
+    // where the prediction is good, and an fp32 mu / inv (1e-7 absolute on the normalised target) is then tens of 16-bit ulps of
+    // the difference that dpred stores (tests/test_gpu_tokens.py checks every element to one ulp)
+    double mu = 0.0, inv = 1.0;
     if (norm_pix) {
-      float s = 0.f, s2 = 0.f;
+      double s = 0.0, s2 = 0.0;
       for (int e = lane; e < PD; e += 64) {
         const int c = e % C; int rest = e / C;
         const int px = rest % p; rest /= p;
         const int py = rest % p; const int u = rest / p;
         const int f = frame_idx ? frame_idx[t * u_sz + u] : t * u_sz + u;
-        const float v = imgs[((((size_t)b * C + c) * T + f) * H + hy * p + py) * W + wx * p + px];
-        s += v;
+        s += (double)imgs[((((size_t)b * C + c) * T + f) * H + hy * p + py) * W + wx * p + px];
       }
-      mu = wave_sum(s) / (float)PD;
+      mu = wave_sum_f64(s) / (double)PD;
       for (int e = lane; e < PD; e += 64) {
         const int c = e % C; int rest = e / C;
         const int px = rest % p; rest /= p;
         const int py = rest % p; const int u = rest / p;
         const int f = frame_idx ? frame_idx[t * u_sz + u] : t * u_sz + u;
-        const float v = imgs[((((size_t)b * C + c) * T + f) * H + hy * p + py) * W + wx * p + px] - mu;
-        s2 = fmaf(v, v, s2);
+        const double v = (double)imgs[((((size_t)b * C + c) * T + f) * H + hy * p + py) * W + wx * p + px] - mu;
+        s2 = fma(v, v, s2);
       }
-      const float var = wave_sum(s2) / (float)(PD - 1);
-      inv = rsqrtf(var + 1.0e-6f);
+      const double var = wave_sum_f64(s2) / (double)(PD - 1);
+      inv = 1.0 / sqrt(var + 1.0e-6);
     }
     float acc = 0.f;
     for (int q = lane; q < nq; q += 64) {
@@ -390,7 +397,7 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ pred
       float d[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        d[k] = pv[k] - (tg[k] - mu) * inv;
+        d[k] = norm_pix ? (float)((double)pv[k] - ((double)tg[k] - mu) * inv) : pv[k] - tg[k];
         acc = fmaf(d[k], d[k], acc);
       }
       if (MODE == 1) {

@@ -152,6 +152,64 @@ def dgelu_poly(x):
     return u * q + 0.5
 
 
+def scale_log2e(scale: float) -> torch.Tensor:
+    """scale*log2e as the kernels form it: an fp32 product (of two fp32 values: exact in float64, then rounded once)."""
+    return f32(f32(torch.tensor(scale, dtype=D)) * f32(torch.tensor(LOG2E, dtype=D)))
+
+
+def attention_forward(q, k, v, sc2):
+    """The attention part of block_forward: q, k, v [B, H, N, hd] float64 holding 16-bit values, sc2 = scale_log2e(scale).
+    Returns (o rounded to 16 bits, lse rounded to fp32 [B, H, N], qs = the pre-scaled rounded query the pair's dQ kernel reuses)."""
+    qs = bf(f32(q * sc2))                                                   # fp32 product, then bf16, as scale_frag does
+    S2 = qs @ k.transpose(-1, -2)                                           # exp2-domain scores
+    Pm = torch.exp2(S2)                                                     # optimistic forward: no running max
+    l = Pm.sum(-1, keepdim=True)
+    o = bf((bf(Pm) @ v) / l)                                                # [B, H, N, hd]
+    lse = torch.log2(l.squeeze(-1)) * math.log(2.0)                         # natural log, as the kernel stores it
+    lse = f32(lse)
+    return o, lse, qs
+
+
+def attention_backward(q, k, v, qs, o, lse, do, scale, sc2, both_dq: bool = True):
+    """The attention part of block_backward: do [B, H, N, hd] 16-bit values in float64.  Returns (dQ of the fused form, dQ of the
+    two-kernel pair -- None unless both_dq --, dK, dV), all BEFORE their rounding to 16 bits."""
+    delta = f32((do * o).sum(-1, keepdim=True))
+    nl = f32(-(lse * f32(torch.tensor(LOG2E, dtype=D)))).unsqueeze(-1)      # -lse*log2e (fp32 product)
+    ks = bf(f32(k * sc2))
+    Pk = torch.exp2(q @ ks.transpose(-1, -2) + nl)                          # key-on-the-lane kernels: K pre-scaled
+    dPk = do @ v.transpose(-1, -2) - delta
+    dSk = Pk * dPk
+    dV = bf(Pk).transpose(-1, -2) @ do
+    dK = scale * (bf(dSk).transpose(-1, -2) @ q)
+    dQf = scale * (bf(dSk) @ k)
+    dQp = None
+    if both_dq:                                                             # the dQ kernel of the pair pre-scales Q
+        Pq = torch.exp2(qs @ k.transpose(-1, -2) + nl)
+        dQp = scale * (bf(Pq * dPk) @ k)
+    return dQf, dQp, dK, dV
+
+
+def attention_forward_backward(q, k, v, do, scale: float, o=None, lse=None):
+    """The attention kernels alone, as the model above evaluates them: q, k, v, do [B, H, N, hd] holding 16-bit values.
+    Returns a dict of float64 tensors: o, dq_fused, dq_pair, dk, dv (rounded to 16 bits, as the kernels store them) and lse (fp32).
+    o [B, H, N, hd], lse [B, H, N] (both or neither): the forward results the backward is fed INSTEAD of the model's own -- a backward
+    kernel under test reads the o and lse its caller hands it (delta = rowsum(dO * o) moves a whole row of dS), so its model must too.
+    Evaluated one (b, h) slice at a time: the [N, N] intermediates of one slice are all that is ever alive."""
+    q, k, v, do = (t.to(D) for t in (q, k, v, do))
+    sc2 = scale_log2e(scale)
+    assert (o is None) == (lse is None)
+    B, H = q.shape[:2]
+    out = {n: [] for n in ("o", "lse", "dq_fused", "dq_pair", "dk", "dv")}
+    for i in range(B * H):
+        qi, ki, vi, di = (t.reshape(B * H, 1, *t.shape[2:])[i:i + 1] for t in (q, k, v, do))
+        o_m, lse_m, qs = attention_forward(qi, ki, vi, sc2)
+        o_b, lse_b = (o_m, lse_m) if o is None else (o.to(D).reshape(B * H, 1, *o.shape[2:])[i:i + 1], lse.to(D).reshape(B * H, 1, -1)[i:i + 1])
+        dQf, dQp, dK, dV = attention_backward(qi, ki, vi, qs, o_b, lse_b, di, scale, sc2)
+        for n, t in zip(out, (o_m, lse_m, bf(dQf), bf(dQp), bf(dK), bf(dV))):
+            out[n].append(t)
+    return {n: torch.cat(ts, 0).reshape(B, H, *ts[0].shape[2:]) for n, ts in out.items()}
+
+
 def block_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, num_heads: int, eps: float = 1e-6, exact_gelu: bool = False):
     """Forward of one Block with the HIP path's roundings.  P: the Block's parameters by their reference names
     (norm1.weight, attn.q.weight, ..., mlp.fc2.bias); x [B, N, C].  Returns (x3 float64, saved) -- `saved` is what
@@ -160,8 +218,7 @@ def block_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, num_heads: int, e
     H = num_heads
     hd = C // H
     scale = hd ** -0.5
-    # the kernels form scale*log2e as an fp32 product (of two fp32 values: exact in float64, then rounded once)
-    sc2 = f32(f32(torch.tensor(scale, dtype=D)) * f32(torch.tensor(LOG2E, dtype=D)))
+    sc2 = scale_log2e(scale)
     p = {k: v.to(D) for k, v in P.items()}
     x = x.to(D)
     wqkv = bf(torch.cat([p["attn.q.weight"], p["attn.k.weight"], p["attn.v.weight"]], 0))
@@ -171,13 +228,7 @@ def block_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, num_heads: int, e
     y1 = bf(y1f)
     qkv = bf(y1 @ wqkv.T + bqkv)                                            # [B, N, 3C]
     q, k, v = (t.reshape(B, N, H, hd).transpose(1, 2) for t in qkv.split(C, dim=-1))     # [B, H, N, hd]
-    qs = bf(f32(q * sc2))                                                   # fp32 product, then bf16, as scale_frag does
-    S2 = qs @ k.transpose(-1, -2)                                           # exp2-domain scores
-    Pm = torch.exp2(S2)                                                     # optimistic forward: no running max
-    l = Pm.sum(-1, keepdim=True)
-    o = bf((bf(Pm) @ v) / l)                                                # [B, H, N, hd]
-    lse = torch.log2(l.squeeze(-1)) * math.log(2.0)                         # natural log, as the kernel stores it
-    lse = f32(lse)
+    o, lse, qs = attention_forward(q, k, v, sc2)
     o2 = o.transpose(1, 2).reshape(B, N, C)
     x2 = x + o2 @ wp.T + p["attn.proj.bias"]
     y2f, xh2, rs2 = ln_fwd(x2, p["norm2.weight"], p["norm2.bias"], eps)
@@ -219,19 +270,8 @@ def block_backward(saved, dx3: torch.Tensor, fused_bwd: bool = True, poly_dgelu:
     G["attn.proj.bias"] = dx2.reshape(-1, C).sum(0)
     G["attn.proj.weight"] = dx2b.reshape(-1, C).T @ o2.reshape(-1, C)
     do = bf(dx2b @ wp).reshape(B, N, H, hd).transpose(1, 2)                 # [B, H, N, hd]
-    delta = f32((do * o).sum(-1, keepdim=True))
-    nl = f32(-(lse * f32(torch.tensor(LOG2E, dtype=D)))).unsqueeze(-1)      # -lse*log2e (fp32 product)
-    ks = bf(f32(k * sc2))
-    Pk = torch.exp2(q @ ks.transpose(-1, -2) + nl)                          # key-on-the-lane kernels: K pre-scaled
-    dPk = do @ v.transpose(-1, -2) - delta
-    dSk = Pk * dPk
-    dV = bf(Pk).transpose(-1, -2) @ do
-    dK = scale * (bf(dSk).transpose(-1, -2) @ q)
-    if fused_bwd:
-        dQ = scale * (bf(dSk) @ k)
-    else:                                                                   # the dQ kernel of the pair pre-scales Q
-        Pq = torch.exp2(qs @ k.transpose(-1, -2) + nl)
-        dQ = scale * (bf(Pq * dPk) @ k)
+    dQf, dQp, dK, dV = attention_backward(q, k, v, qs, o, lse, do, scale, sc2, both_dq=not fused_bwd)
+    dQ = dQf if fused_bwd else dQp
     dqkv = bf(torch.cat([t.transpose(1, 2).reshape(B, N, C) for t in (dQ, dK, dV)], -1))
     gb = dqkv.reshape(-1, 3 * C).sum(0)
     gw = dqkv.reshape(-1, 3 * C).T @ y1.reshape(-1, C)
