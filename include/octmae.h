@@ -27,8 +27,10 @@ extern "C" {
  * 10: octmae_lp_dtype, octmae_comm_stream, octmae_mt_adamw_fused, octmae_gemm_bf16_ws + workspace arguments.
  * 11: the small-launch GEMM kernel and its split-K workspace (octmae_gemm_split_ws_kib, octmae_gemm_small_plan, "gemm_small");
  *     the stream-K and 16x16x32 variants of round 4 / 5 left the library (octmae_gemm_streamk_*, "gemm_mfma16", "gemm_streamk").
- * 12: octmae_slice_pool_fwd / _bwd / _ws_floats (the slice-pooling head of the RETFound-all model). */
-#define OCTMAE_ABI_VERSION 12
+ * 12: octmae_slice_pool_fwd / _bwd / _ws_floats (the slice-pooling head of the RETFound-all model).
+ * 13: octmae_gemm_plan, octmae_wgrad_pair_plan (the GEMM launch planner of csrc/gemm_plan.hpp, queried without a GPU); variant bits 9 / 10
+ *     now force the 256-tile main loop they name for forward and dgrad launches too, and never the small-launch kernel. */
+#define OCTMAE_ABI_VERSION 13
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -49,7 +51,7 @@ int octmae_lp_dtype(void);
  *                          workspace -> bf16 conversion of their (batch, head); 0: the separate launch (same results)
  *   "gemm_small"           1 (default): forward / dgrad launches whose 256 x 256 tiles would leave most CUs idle take the
  *                          small-launch kernel (gemm128d_kernel: 128 x 128 tiles, deterministic split-K) where the cost model of
- *                          csrc/gemm.hip (plan128) prices it faster; 0: never (the choice before round 6).  Bits 12 / 13 (0x1000 /
+ *                          csrc/gemm_plan.hpp (plan128) prices it faster; 0: never (the choice before round 6).  Bits 12 / 13 (0x1000 /
  *                          0x2000) of octmae_gemm_bf16's `epilogue` argument force that kernel with a 4- / 2-stage ring for one
  *                          call (its k split is then `splitk`, 1 .. 4), bit 14 (0x4000) forbids it (bits 8-10: the other variants)
  *   "gemm_small_launches", "gemm_small_split_launches", "gemm_small_wgrad_launches"   read-only: how many GEMM launches of this process
@@ -95,6 +97,24 @@ int octmae_gemm_split_ws_kib(void);     /* size of that workspace in KiB */
  * kernel under the current "gemm_small" option (*slices = its k split, *stages = its ring depth, 4 or 2), 0 otherwise.
  * have_ws: a split workspace is lent; big_ok: the problem qualifies for the 256-tile kernels */
 int octmae_gemm_small_plan(int NA, int NB, int K, int cus, int have_ws, int big_ok, int* slices, int* stages);
+/* The whole launch plan of one GEMM call (csrc/gemm_plan.hpp: plan_gemm), host-side arithmetic only: what octmae_gemm_bf16[_ws] and the
+ * fused entry points below would launch for X[a][b] = sum_k A[a][k] B[b][k] (NA, NB, K, lda, ldb as there) on `cus` CUs under the
+ * current options.  kind: 0 forward (epilogues 0-3 plan alike), 1 dgrad, 2 dgrad x GELU' with the column sums by atomics (epilogue 4
+ * with C2), 3 the same through the per-slab workspace (octmae_linear_dgrad_dgelu), 4 dgrad + delta (octmae_linear_dgrad_delta),
+ * 5 wgrad, 6 wgrad with the bias gradient (epilogue 5 with C2).  variant: the kernel-selection bits
+ *   bit 8 (0x100) the 128-tile register-staged kernel; bit 9 (0x200) / bit 10 (0x400) the two-stage / phased 256-tile main loop wherever
+ *   the problem takes 256-tiles (the register-staged kernel elsewhere, never the small-launch kernel); bit 12 / 13 (0x1000 / 0x2000)
+ *   the small-launch kernel with a 4- / 2-stage ring wherever its operands allow (it wins over bits 9 / 10; bits 8 and 14 win over
+ *   it), split `splitk` ways or, where bits 16-18 are set,
+ *   that many (1 .. 4; fewer without a workspace or when a slice would be empty); bit 14 (0x4000) never the small-launch kernel;
+ *   bit 15 (0x8000) epilogues 2 / 4 store / read gelu'(pre).
+ * Returns 0 and writes 13 ints to out, or -2 where the entry point would (combination not built / the caller falls back):
+ *   out[0] kernel family: 0 gemm_kernel (128-tile register-staged), 1 gemm256_kernel (two-stage), 2 gemm256p_kernel (phased),
+ *          3 gemm128d_kernel (small launch);  [1] workgroups;  [2] tiles_a  [3] tiles_b  [4] cgroup  [5] k slices  [6] k-tiles per slice
+ *   [7] kstagger  [8] atomic1  [9] ring depth (small launch, else 0)  [10] the small launch's k split (else 1)
+ *   [11] rows of the column-sum workspace that are folded (route 2)  [12] column-sum route: 0 none, 1 atomics inside the kernel,
+ *   2 per-slab rows + a folding launch, 3 / 4 a separate octmae_colsum_accum launch before / after the GEMM. */
+int octmae_gemm_plan(int kind, int NA, int NB, int K, int lda, int ldb, int variant, int splitk, int have_ws, int cus, int* out);
 int octmae_gemm_bf16_ws(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
                         int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided, int b_kstrided,
                         int epilogue, int splitk, void* split_ws, long long split_ws_bytes, void* stream);
@@ -131,6 +151,11 @@ int octmae_wgrad_accum_pair(const void* dY0, const void* X0, float* gW0, float* 
  * (bounds[0 .. *slices], bounds[*slices] = ceil(M / 64); room for splitk + 1 ints), and -- the return value -- the length step between
  * neighbouring slices in 1/256 k-tiles (0 = equal slices; see "wgrad_stagger" above).  Negative: argument error. */
 int octmae_wgrad_split_plan(int M, int splitk, int tiles, int* slices, int* bounds);
+/* The launch plan of octmae_wgrad_accum_pair (csrc/gemm_plan.hpp: plan_wgrad_pair, with the 128- against 256-tile cost model), host side
+ * only.  Returns 0 and writes 14 ints, or -2 as the entry point does:  out[0] kernel family (2: gemm256p_wgrad_pair_kernel,
+ * 3: gemm128d_wgrad_kernel)  [1] workgroups  [2] k slices  [3] k-tiles per slice  [4] kstagger  [5] atomic1  [6] ring depth (family 3)
+ * [7] bias-gradient route (1 inside the kernel, 3 a launch of its own before)  [8..10] / [11..13] tiles_a, tiles_b, cgroup of each problem. */
+int octmae_wgrad_pair_plan(int N0, int K0, int ldy0, int ldx0, int N1, int K1, int ldy1, int ldx1, int M, int splitk, int cus, int* out);
 
 /* The proj dgrad of an attention block together with the attention backward's per-query constant delta (flash-attn's `dsoftmax_sum`,
  * the backward of video_vit.py:130-134 under autograd):

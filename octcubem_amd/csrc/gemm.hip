@@ -20,24 +20,12 @@
 // LDS-DMA kernels further down: gemm256p_kernel (phased main loop with staggered wave groups; the default for forward, dgrad and
 // wgrad) and gemm256_kernel (plain two-stage main loop: the round-1 forward kernel, kept selectable for tests and A/B runs).
 #include "common.hpp"
+#include "gemm_plan.hpp"   // tile constants, Epi, and every host-side launch decision
 #include "../../include/octmae.h"
 
 namespace octmae {
 
-constexpr int TA = 128, TB = 128, TK = 64;
 constexpr int TILE_BYTES = 128 * 64 * 2;  // one operand tile, either layout: 16 KiB
-
-enum Epi : int {
-  EPI_BF16 = 0,      // C bf16 = X (+bias[a])
-  EPI_F32 = 1,       // C f32  = X (+bias[a])
-  EPI_GELU = 2,      // C bf16 = X+bias (pre-activation), C2 bf16 = gelu(X+bias)
-  EPI_RESID = 3,     // C f32  = aux_f32 + X + bias
-  EPI_DGELU = 4,     // C bf16 = X * gelu'(aux_bf16)
-  EPI_ACCUM = 5,     // C f32 += X   (OUT_AB; atomics when split-K > 1)
-  EPI_DELTA = 6,     // C bf16 = X, C2 f32 [NB][ldc2]: C2[b][a / hd] = -sum_{j < hd} bf16(X[b][a0 + j]) * aux_bf16[b][a0 + j]
-                     //   (the attention backward's per-query delta = rowsum(dO * O), from the proj dgrad that produces dO;
-                     //   256-tile LDS-transposing epilogue only)
-};
 
 constexpr unsigned EPI_OOB_ANY = 0xfffffff0u;   // a byte offset past any buffer range: masks a lane of a raw buffer access
 
@@ -354,7 +342,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
 // Out-of-range rows are zero-filled by the buffer descriptor's bounds check (rows past the end of the operand);
 // requires K % 64 == 0 for k-contiguous operands (host falls back to the 128-tile kernel otherwise).
 // =====================================================================================================
-constexpr int T2 = 256;
 constexpr int TILE2_BYTES = 256 * 64 * 2;  // 32 KiB per operand tile
 
 __device__ __forceinline__ int kc2_off(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
@@ -1016,9 +1003,7 @@ struct SplitWs {
   float* slots;       // [tiles x S] fp32 partial tiles of 128 x 128 (S > 1)
   unsigned* ctr;      // [tiles] arrival counters: zero before the launch, zero again after it
 };
-constexpr int T1 = 128;
 constexpr int D_STAGE = 2 * TILE_BYTES;      // 32 KiB: A image | B image
-constexpr int D_SLOT_FLOATS = T1 * T1;
 
 // main loop of the small-launch kernels: tile t of p, k slice kz of S -> acc (the wave's 64 x 64 block at a0 + wa 64, b0 + wb 64);
 // returns with every ring request retired and a workgroup barrier passed (the LDS is free for the epilogue)
@@ -1221,17 +1206,16 @@ __global__ __launch_bounds__(256, NST == 2 ? 2 : 1) void gemm128d_wgrad_kernel(c
   }
 }
 
-// Staggered split-K slices of the 256-tile weight-gradient kernel (split_range): v = the length step between neighbouring slices in
-// 1/256 k-tiles PER OUTPUT TILE of the launch (the atomic time of a slice grows with its tile count: 256 KiB at 1.35 TB/s = 0.19 us
-// per tile against 1.7 us per k-tile, i.e. v = 29); 0 = equal slices.  octmae_set_option("wgrad_stagger", v) / OCTMAE_WGRAD_STAGGER.
-// Applied only to splits of >= 8 slices with <= 96 k-tiles each (the [C x C] proj gradients at <= 32 volumes per rank): measured
-// (profiles/r04_wgrad_stagger.txt) -9 / -11 % there, and nothing or a loss for the 4- and 5-way splits
-// and for every shape at 128 volumes -- their workgroups do not end together anyway.
-std::atomic<int> g_wgrad_stagger{29};
+// ---- host side: option state, launch helpers, entry points.  Every launch decision is made in gemm_plan.hpp --------------------------
+std::atomic<int> g_wgrad_stagger{29};      // "wgrad_stagger" / OCTMAE_WGRAD_STAGGER (wgrad_stagger_for)
 // The epilogue of an UNSPLIT weight-gradient launch of the phased 256-tile kernel: 0 = plain read-modify-write (one guarded load + store
 // per register), 1 = the same fire-and-forget fp32 atomics a split launch uses (still deterministic: one add per element and launch),
 // 2 = read-modify-write in batches of 16 registers through a buffer descriptor.  "wgrad_s1_atomic" / OCTMAE_WGRAD_S1_ATOMIC.
 std::atomic<int> g_wgrad_s1_atomic{2};
+std::atomic<int> g_gemm_small{1};          // octmae_set_option("gemm_small", 0 / 1); OCTMAE_GEMM_SMALL overrides
+std::atomic<int> g_small_launches{0};      // how many launches took gemm128d_kernel ("gemm_small_launches": tests)
+std::atomic<int> g_small_split_launches{0};   // ... with a k split
+std::atomic<int> g_small_wgrad_launches{0};   // weight-gradient pairs that took gemm128d_wgrad_kernel ("gemm_small_wgrad_launches")
 
 // CU count of the current device (cached per device)
 static int device_cus() {
@@ -1245,170 +1229,69 @@ static int device_cus() {
   return v;
 }
 
-template <bool A_KS, bool B_KS, int EPI, bool OUT_AB>
-static int launch256(const GemmParams& p, int splitk, hipStream_t st, bool phased) {
-  auto kern = phased ? gemm256p_kernel<A_KS, B_KS, EPI, OUT_AB> : gemm256_kernel<A_KS, B_KS, EPI, OUT_AB>;
-  static DynLdsOnce once[2];
-  if (int rc = once[phased].ensure(reinterpret_cast<const void*>(kern), 4 * TILE2_BYTES)) return rc;
-  dim3 grid(p.tiles_a * p.tiles_b, 1, splitk);
-  hipLaunchKernelGGL(kern, grid, dim3(512), 4 * TILE2_BYTES, st, p);
+// one launch of kernel KERN with `lds` bytes of dynamic LDS (raised above the default limit once per kernel and device)
+template <auto KERN, typename... Args>
+static int launch_dyn(dim3 grid, int block, int lds, hipStream_t st, const Args&... args) {
+  static DynLdsOnce once;
+  if (int rc = once.ensure(reinterpret_cast<const void*>(KERN), lds)) return rc;
+  hipLaunchKernelGGL(KERN, grid, dim3(block), lds, st, args...);
   OCTMAE_LAUNCH_CHECK();
   return 0;
 }
 
-// ---- the small-launch kernel: workspace, plan, launch -------------------------------------------------------------------------
-// Workspace (caller-owned, lent per call, one per stream): [D_WS_SLOTS partial tiles of 64 KiB][D_WS_TILES arrival counters].  The
-// counters must be zero when the workspace is first lent; every launch leaves them zero.
-constexpr int D_WS_SLOTS = 1024, D_WS_TILES = 4096;
-static long long d_ws_bytes() { return (long long)D_WS_SLOTS * D_SLOT_FLOATS * 4 + (long long)D_WS_TILES * 4; }
-
-std::atomic<int> g_gemm_small{1};          // octmae_set_option("gemm_small", 0 / 1); OCTMAE_GEMM_SMALL overrides
-std::atomic<int> g_small_launches{0};      // how many launches took gemm128d_kernel ("gemm_small_launches": tests)
-std::atomic<int> g_small_split_launches{0};
-std::atomic<int> g_small_wgrad_launches{0};   // weight-gradient pairs that took gemm128d_wgrad_kernel ("gemm_small_wgrad_launches")
-
-struct Plan128 {
-  int use;      // 1: gemm128d_kernel
-  int S;        // k slices per tile (1: no workspace needed)
-  int nst;      // ring stages: 4 (one workgroup per CU) or 2 (two)
-};
-// Which kernel a forward / dgrad launch of NA x NB x K takes on G CUs (fitted on MI355X with tools/gemm_small_fit.py: device times of
-// graph-replayed launches, profiles/r06_gemm_small_fit.txt).
-//  * At most one round of 256-tiles (nt256 <= G, the regime the kernel was built for): a latency model in microseconds.  A workgroup of
-//    the 256-tile kernel takes ~1.05 us per k-tile + ~6.5 us (prologue, epilogue, launch); one of this kernel ~0.5 us per k-tile + ~4.5 us
-//    alone on its CU (4-stage ring) and ~0.85 us per k-tile + ~5.5 us in rounds of two per CU (2-stage ring); a k split adds the publish
-//    and the last arriver's gather, ~5.5 us + ~1.5 us per slice beyond the second.
-//  * More than one round: both kernels stream, and what differs is how much of their LAST round is empty.  Per 128 x 128 x 64 block of
-//    work the 256-tile kernel costs 1.18 / 4 us and this kernel's 2-stage form 0.64 / 2 us; with eff = tiles / (rounds x slots) of each
-//    (slots: G and 2 G) it is taken when 0.32 / eff128 < 0.9 x 0.295 / eff256 -- e.g. the decoder's [8 x 5121 rows] x K -> 512 dgrads:
-//    322 tiles of 256 = 1.26 rounds of CUs against 1284 of 128 = 2.5 rounds of 512 slots, 82 against 96 us.  The 128-volume shapes of
-//    the headline step sit at eff256 >= 0.83 and keep the 256-tile kernel (tests/test_cpu_host.py).
-static Plan128 plan128(int NA, int NB, int K, int G, bool have_ws, bool big256_ok) {
-  static const int env = getenv("OCTMAE_GEMM_SMALL") ? atoi(getenv("OCTMAE_GEMM_SMALL")) : -1;
-  const int on = env >= 0 ? env : g_gemm_small.load(std::memory_order_relaxed);
-  Plan128 pl{0, 1, 4};
-  if (!on) return pl;
-  const int ktiles = (K + TK - 1) / TK;
-  const long long nt128 = (long long)((NA + T1 - 1) / T1) * ((NB + T1 - 1) / T1);
-  const long long nt256 = (long long)((NA + T2 - 1) / T2) * ((NB + T2 - 1) / T2);
-  if (big256_ok && nt256 > G) {
-    const double eff256 = (double)nt256 / (double)(((nt256 + G - 1) / G) * G);
-    const double eff128 = (double)nt128 / (double)(((nt128 + 2 * G - 1) / (2 * G)) * 2 * G);
-    if (0.32 / eff128 < 0.9 * 0.295 / eff256) { pl.use = 1; pl.S = 1; pl.nst = 2; }
-    return pl;
-  }
-  const double t256 = big256_ok ? 1.05 * ktiles + 6.5 : 1e30;
-  double best = 1e30;
-  for (int S = 1; S <= 4; ++S) {
-    if (S > 1 && (!have_ws || ktiles / S < 8 || nt128 * S > D_WS_SLOTS || nt128 > D_WS_TILES)) break;
-    const int kper = (ktiles + S - 1) / S;
-    if (S > 1 && (long long)(S - 1) * kper >= ktiles) continue;          // an empty last slice
-    const long long wg = nt128 * S;
-    const double split = S > 1 ? 5.5 + 1.5 * (S - 2) : 0.0;
-    const double t4 = (double)((wg + G - 1) / G) * (0.5 * kper + 4.5 + split);
-    const double t2 = wg > G ? (double)((wg + 2 * G - 1) / (2 * G)) * (0.85 * kper + 5.5 + split) : 1e30;
-    if (t4 < best) { best = t4; pl.S = S; pl.nst = 4; }
-    if (t2 < best) { best = t2; pl.S = S; pl.nst = 2; }
-  }
-  pl.use = best < 0.92 * t256;
-  if (!pl.use) { pl.S = 1; pl.nst = 4; }
-  return pl;
+// operands and shape of a launch; tiles, tile order and k split come from the plan
+static GemmParams make_params(const void* A, const void* B, void* C, void* C2, const void* aux, int NA, int NB, int K, int lda,
+                              int ldb, int ldc, int ldaux) {
+  GemmParams p;
+  p.A = reinterpret_cast<const bf16_t*>(A); p.B = reinterpret_cast<const bf16_t*>(B);
+  p.C = C; p.C2 = C2; p.bias = nullptr; p.aux = aux; p.rowscale = nullptr; p.rows_per_scale = 1;
+  p.NA = NA; p.NB = NB; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldaux = ldaux;
+  p.ktiles = cdiv(K, TK); p.ldc2 = 0; p.hd = 0;
+  return p;
+}
+static void apply_plan(GemmParams& p, const GemmPlan& pl) {
+  p.tiles_a = pl.tiles_a; p.tiles_b = pl.tiles_b; p.cgroup = pl.cgroup;
+  p.ktiles_per_split = pl.ktiles_per_split; p.kstagger = pl.kstagger; p.atomic1 = pl.atomic1;
 }
 
-// operands the small-launch kernel can take (the epilogue transposes 8-column chunks; LDS-DMA of whole k-tiles; 32-bit buffer ranges)
-static bool gemm128_ok(int NA, int NB, int K, int lda, int ldb, bool a_ks, bool b_ks) {
-  if ((NA & 7) != 0 || (a_ks && b_ks)) return false;
-  if ((!a_ks || !b_ks) && (K % TK) != 0) return false;
-  const size_t a_bytes = (size_t)(a_ks ? K : NA) * lda * 2, b_bytes = (size_t)(b_ks ? K : NB) * ldb * 2;
-  return a_bytes < 0xFFF00000ull && b_bytes < 0xFFF00000ull;
-}
-
+// the small-launch kernel; ws: the lent split-K workspace (read only when the plan splits)
 template <bool A_KS, bool B_KS, int EPI>
-static int launch128d(GemmParams p, const Plan128& pl, void* ws, hipStream_t st) {
-  p.tiles_a = (p.NA + T1 - 1) / T1;
-  p.tiles_b = (p.NB + T1 - 1) / T1;
-  p.cgroup = p.tiles_a;
-  p.kstagger = 0;
-  p.ktiles_per_split = (p.ktiles + pl.S - 1) / pl.S;
+static int launch128d(const GemmParams& p, const GemmPlan& pl, void* ws, hipStream_t st) {
   SplitWs w{nullptr, nullptr};
-  if (pl.S > 1) {
+  if (pl.slices > 1) {
     w.slots = reinterpret_cast<float*>(ws);
     w.ctr = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + (long long)D_WS_SLOTS * D_SLOT_FLOATS * 4);
     g_small_split_launches.fetch_add(1, std::memory_order_relaxed);
   }
-  const int nt = p.tiles_a * p.tiles_b;
-  if (pl.nst == 2) {
-    auto kern = gemm128d_kernel<A_KS, B_KS, EPI, 2>;
-    static DynLdsOnce once;
-    if (int rc = once.ensure(reinterpret_cast<const void*>(kern), 2 * D_STAGE)) return rc;
-    hipLaunchKernelGGL(kern, dim3(nt * pl.S, 1, 1), dim3(256), 2 * D_STAGE, st, p, w, pl.S);
-  } else {
-    auto kern = gemm128d_kernel<A_KS, B_KS, EPI, 4>;
-    static DynLdsOnce once;
-    if (int rc = once.ensure(reinterpret_cast<const void*>(kern), 4 * D_STAGE)) return rc;
-    hipLaunchKernelGGL(kern, dim3(nt * pl.S, 1, 1), dim3(256), 4 * D_STAGE, st, p, w, pl.S);
-  }
-  OCTMAE_LAUNCH_CHECK();
-  g_small_launches.fetch_add(1, std::memory_order_relaxed);
-  return 0;
+  const int rc = pl.nst == 2 ? launch_dyn<gemm128d_kernel<A_KS, B_KS, EPI, 2>>(dim3(pl.grid()), 256, 2 * D_STAGE, st, p, w, pl.slices)
+                             : launch_dyn<gemm128d_kernel<A_KS, B_KS, EPI, 4>>(dim3(pl.grid()), 256, 4 * D_STAGE, st, p, w, pl.slices);
+  if (rc == 0) g_small_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
 }
 
+// the kernel family the plan names, for one layout / epilogue combination
 template <bool A_KS, bool B_KS, int EPI, bool OUT_AB>
-static int launch(const GemmParams& p, int splitk, hipStream_t st) {
-  auto kern = gemm_kernel<A_KS, B_KS, EPI, OUT_AB>;
-  static DynLdsOnce once;
-  if (int rc = once.ensure(reinterpret_cast<const void*>(kern), 4 * TILE_BYTES)) return rc;
-  dim3 grid(p.tiles_a * p.tiles_b, 1, splitk);
-  hipLaunchKernelGGL(kern, grid, dim3(256), 4 * TILE_BYTES, st, p);
-  OCTMAE_LAUNCH_CHECK();
-  return 0;
+static int launch_plan(const GemmParams& p, const GemmPlan& pl, void* split_ws, hipStream_t st) {
+  const dim3 grid(pl.tiles_a * pl.tiles_b, 1, pl.slices);
+  switch (pl.kernel) {
+    case GemmKernel::Tile128: return launch_dyn<gemm_kernel<A_KS, B_KS, EPI, OUT_AB>>(grid, 256, 4 * TILE_BYTES, st, p);
+    case GemmKernel::TwoStage256: return launch_dyn<gemm256_kernel<A_KS, B_KS, EPI, OUT_AB>>(grid, 512, 4 * TILE2_BYTES, st, p);
+    case GemmKernel::Phased256: return launch_dyn<gemm256p_kernel<A_KS, B_KS, EPI, OUT_AB>>(grid, 512, 4 * TILE2_BYTES, st, p);
+    case GemmKernel::Small128d:
+      if constexpr (!OUT_AB) return launch128d<A_KS, B_KS, EPI>(p, pl, split_ws, st);
+  }
+  return PLAN_FALLBACK;
 }
 
 }  // namespace octmae
-
 using namespace octmae;
-
-// GemmParams::kstagger of an S-way split over `ktiles` k-tiles of a launch with `tiles` output tiles (0: equal slices)
-static int wgrad_stagger_for(int ktiles, int splitk, int tiles) {
-  static const int envs = getenv("OCTMAE_WGRAD_STAGGER") ? atoi(getenv("OCTMAE_WGRAD_STAGGER")) : -1;
-  const int v = envs >= 0 ? envs : g_wgrad_stagger.load(std::memory_order_relaxed);
-  if (!(v > 0 && splitk >= 8 && ktiles <= 96 * splitk)) return 0;
-  // the shortest slice (ktiles / S - d (S - 1) / 2) keeps at least half the mean length and 8 k-tiles
-  const long long mean_q8 = ((long long)ktiles << 8) / splitk;
-  long long d = (long long)v * tiles;
-  const long long dmax = (mean_q8 - (8 << 8) < mean_q8 / 2 ? mean_q8 - (8 << 8) : mean_q8 / 2) * 2 / (splitk - 1);
-  if (d > dmax) d = dmax;
-  return d > 0 ? (int)d : 0;
-}
-
-static int wgrad_s1_atomic() {
-  static const int env = getenv("OCTMAE_WGRAD_S1_ATOMIC") ? atoi(getenv("OCTMAE_WGRAD_S1_ATOMIC")) : -1;
-  return env >= 0 ? env : g_wgrad_s1_atomic.load(std::memory_order_relaxed);
-}
-
 extern "C" int octmae_colsum_accum(const void* in, int in_is_bf16, float* out, int M, int N, int ld, void* stream);
 
 // C[b][a] (+epilogue) = sum_k A[a][k] B[b][k];  see include/octmae.h for the contract.
-static int gemm_impl(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
-                     int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided,
-                     int b_kstrided, int epilogue, int splitk, void* stream, const float* rowscale, int rows_per_scale,
-                     float* colsum_ws = nullptr, void* split_ws = nullptr, long long split_bytes = 0) {
-  // Variant bits of `epilogue` (tests and A/B runs exercise every kernel on the same problem): bit 8 forces the 128-tile
-  // register-staged kernel, bit 9 the two-stage (un-phased) 256-tile main loop, bit 10 the phased one; bit 12 / 13 force the
-  // small-launch kernel gemm128d_kernel with a 4- / 2-stage ring (its k split is then `splitk`, 1 .. 4, which otherwise only the
-  // weight gradients read); bit 14 forbids it (the pre-round-6 choice); bits 16-18: the forced kernel's k split where the entry point has no `splitk`.
-  const int variant = (epilogue >> 8) & 1;
-  const int force128 = ((epilogue >> 12) & 1) ? 4 : ((epilogue >> 13) & 1) ? 2 : 0;
-  const bool never128 = ((epilogue >> 14) & 1) != 0;
-  const int dgelu_stored = (epilogue >> 15) & 1;        // bit 15: the fc1 forward stores gelu'(pre) / the fc2 dgrad multiplies with it
-  // phased main loop by default (dgrad, wgrad: +10..25 % over the two-stage loop; forward, re-measured in round 2 after the
-  // epilogue work: qkv -4 %, proj -11 %, fc2 -8 %, fc1 + GELU -1.5 %, decoder fc1 + GELU +0.6 % -- in round 1 the two-stage loop
-  // had still been 12 % faster at K = 1024).
-  const bool phased = ((epilogue >> 10) & 1) ? true : ((epilogue >> 9) & 1) ? false : true;
-  const int forced_split = ((epilogue >> 16) & 7) ? ((epilogue >> 16) & 7) : splitk;     // bits 16-18: the forced kernel's k split
-  epilogue &= 0xff;
-  OCTMAE_CHECK_ARG(A && B && C);
-  OCTMAE_CHECK_ARG(NA > 0 && NB > 0 && K > 0);
+static int gemm_impl(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux, int NA, int NB, int K, int lda,
+                     int ldb, int ldc, int ldaux, int a_kstrided, int b_kstrided, int epilogue, const GemmVariant& v, int splitk, void* stream,
+                     const float* rowscale, int rows_per_scale, float* colsum_ws = nullptr, void* split_ws = nullptr, long long split_bytes = 0) {
+  OCTMAE_CHECK_ARG(A && B && C && NA > 0 && NB > 0 && K > 0);
   OCTMAE_CHECK_ARG((lda % 8) == 0 && (ldb % 8) == 0);
   OCTMAE_CHECK_ARG(epilogue >= 0 && epilogue <= 5);
   // contiguous-dimension granularity: 16-byte chunks of 8 bf16
@@ -1417,267 +1300,63 @@ static int gemm_impl(const void* A, const void* B, void* C, void* C2, const floa
   if (epilogue != EPI_ACCUM) OCTMAE_CHECK_ARG(NA % 4 == 0 && ldc % 4 == 0);
   if (epilogue == EPI_GELU) OCTMAE_CHECK_ARG(C2 != nullptr);
   if (epilogue == EPI_RESID || epilogue == EPI_DGELU) OCTMAE_CHECK_ARG(aux != nullptr && ldaux % 4 == 0);
-  if (splitk < 1) splitk = 1;
-  if (epilogue != EPI_ACCUM) splitk = 1;
-  GemmParams p;
-  p.A = reinterpret_cast<const bf16_t*>(A);
-  p.B = reinterpret_cast<const bf16_t*>(B);
-  p.C = C; p.C2 = C2; p.bias = bias; p.aux = aux;
-  p.rowscale = rowscale; p.rows_per_scale = rows_per_scale > 0 ? rows_per_scale : 1;
-  p.NA = NA; p.NB = NB; p.K = K;
-  p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldaux = ldaux;
-  p.ktiles = (K + TK - 1) / TK;
+  const GemmProblem q{NA, NB, K, lda, ldb, a_kstrided != 0, b_kstrided != 0, epilogue, splitk, C2 != nullptr, colsum_ws != nullptr};
+  const GemmPlan pl = plan_gemm(q, v, current_options(), device_cus, split_ws != nullptr && split_bytes >= d_ws_bytes());
+  if (pl.status != 0) return pl.status;
+  GemmParams p = make_params(A, B, C, C2, aux, NA, NB, K, lda, ldb, ldc, ldaux);
+  p.bias = bias; p.rowscale = rowscale; p.rows_per_scale = rows_per_scale > 0 ? rows_per_scale : 1;
+  p.dgelu_stored = (epilogue == EPI_GELU || epilogue == EPI_DGELU) ? v.dgelu_stored : 0;
+  apply_plan(p, pl);
+  // Column sums that ride along: the kernel sees the fp32 [NA] vector C2 only where it adds to it itself (Colsum::Fused)
+  float* const colsum = pl.colsum != Colsum::None ? reinterpret_cast<float*>(C2) : nullptr;
+  if (pl.colsum == Colsum::FoldWs) { p.C2 = colsum_ws; p.ldc2 = NA; }
+  if (pl.colsum == Colsum::PassBefore || pl.colsum == Colsum::PassAfter) p.C2 = nullptr;
+  if (pl.colsum == Colsum::PassBefore) { if (int rc = octmae_colsum_accum(A, 1, colsum, K, NA, lda, stream)) return rc; }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-
-  // 256-tile LDS-DMA kernel when the problem has at least one full tile each way, k-contiguous operands have whole
-  // k-tiles, and each operand fits a 32-bit buffer descriptor; otherwise the 128-tile register-staged kernel.
-  const size_t a_bytes = (size_t)(a_kstrided ? K : NA) * lda * 2, b_bytes = (size_t)(b_kstrided ? K : NB) * ldb * 2;
-  bool big = NA >= T2 && NB >= T2 && a_bytes < 0xFFF00000ull && b_bytes < 0xFFF00000ull && (variant & 1) == 0;
-  if ((!a_kstrided || !b_kstrided) && (K % TK) != 0) big = false;
-  const int tile = big ? T2 : TA;
-  p.tiles_a = (NA + tile - 1) / tile;
-  p.tiles_b = (NB + tile - 1) / tile;
-  // column-tile group of the tile order (tile_coord): groups of 4 column tiles when there are >= 16 of them and 4 weight
-  // panels fit half the L2 (K <= 1024: the fc1 forward and the fc2 dgrad of ViT-L).  Measured same-box: fc1 forward
-  // 891 -> 871 us, fc2 dgrad+dgelu 801 -> 790 us; narrower groups (K >= 3072, one panel per group) lose 3-5 % to the
-  // activation re-reads and 12 column tiles (qkv) gain nothing, so those keep the plain order.
-  p.cgroup = p.tiles_a;
-  if (big && epilogue != EPI_ACCUM) {
-    static const int force = getenv("OCTMAE_CGROUP") ? atoi(getenv("OCTMAE_CGROUP")) : 0;
-    const size_t panel = (size_t)T2 * K * 2;
-    if (force > 0) {
-      if (p.tiles_a % force == 0) p.cgroup = force;
-    } else if (p.tiles_a >= 16 && p.tiles_a % 4 == 0 && 4 * panel <= (2u << 20)) {
-      p.cgroup = 4;
-    }
-  } else if (big && p.tiles_a * p.tiles_b > 32) {
-    // weight gradients: the ~32 workgroups an XCD runs at a time should form a compact rectangle of tiles (8 x 4 rather than
-    // 16 x 2 for fc1's 16 x 4 tiles): c column tiles x all row tiles, c = 32 / tiles_b rounded down to a divisor of tiles_a
-    int c = 32 / p.tiles_b;
-    if (c < 1) c = 1;
-    while (c > 1 && p.tiles_a % c != 0) --c;
-    p.cgroup = c;
-  }
-  if (splitk > p.ktiles) splitk = p.ktiles;
-  p.ktiles_per_split = (p.ktiles + splitk - 1) / splitk;
-  splitk = (p.ktiles + p.ktiles_per_split - 1) / p.ktiles_per_split;
-
-  // The small-launch kernel (forward / dgrad kinds): when the cost model says so (plan128), or forced.
-  Plan128 pl{0, 1, 4};
-  if (epilogue != EPI_ACCUM && !never128 && (variant & 1) == 0 && gemm128_ok(NA, NB, K, lda, ldb, a_kstrided != 0, b_kstrided != 0)) {
-    const bool have_ws = split_ws != nullptr && split_bytes >= d_ws_bytes();
-    if (force128) {
-      pl.use = 1; pl.nst = force128;
-      pl.S = forced_split < 1 ? 1 : forced_split > 4 ? 4 : forced_split;
-      while (pl.S > 1 && (!have_ws || (long long)(pl.S - 1) * ((p.ktiles + pl.S - 1) / pl.S) >= p.ktiles ||
-                          (long long)((NA + T1 - 1) / T1) * ((NB + T1 - 1) / T1) * pl.S > D_WS_SLOTS)) --pl.S;
-    } else if (!((epilogue >> 9) & 1) && !((epilogue >> 10) & 1)) {
-      pl = plan128(NA, NB, K, device_cus(), have_ws, big);
-    }
-  }
-
-  // EPI_DGELU with C2: C2 is an fp32 [NA] vector that receives += the column sums of C (bias gradient of the Linear whose
-  // activation is being differentiated).  Fused into the LDS-transposing epilogues (256-tile kernels, small-launch kernel); the
-  // 128-tile register-staged kernel is followed by the stand-alone column-sum kernel.
-  float* dgelu_colsum = (epilogue == EPI_DGELU) ? reinterpret_cast<float*>(C2) : nullptr;
-  if (epilogue == EPI_DGELU && !((big || pl.use) && (NA & 7) == 0)) p.C2 = nullptr;
-  p.ldc2 = 0; p.hd = 0;
-  p.kstagger = (big && epilogue == EPI_ACCUM) ? wgrad_stagger_for(p.ktiles, splitk, p.tiles_a * p.tiles_b) : 0;
-  p.atomic1 = (big && phased && epilogue == EPI_ACCUM) ? wgrad_s1_atomic() : 0;
-  p.dgelu_stored = (epilogue == EPI_GELU || epilogue == EPI_DGELU) ? dgelu_stored : 0;
-  // 64-row slabs that write a row of partial column sums: those of the grid that runs (octmae_dgelu_colsum_ws_rows covers both)
-  const int ws_rows = pl.use ? 2 * ((NB + T1 - 1) / T1) : 4 * p.tiles_b;
-  if (epilogue == EPI_DGELU && p.C2 != nullptr && colsum_ws != nullptr) { p.C2 = colsum_ws; p.ldc2 = NA; }
-#define OCTMAE_GEMM_CASE(AKS, BKS, E, AB)                                  \
-  if (a_kstrided == AKS && b_kstrided == BKS && epilogue == E) {           \
-    int rc_;                                                               \
-    if constexpr (!AB) {                                                   \
-      rc_ = pl.use ? launch128d<AKS, BKS, E>(p, pl, split_ws, st)          \
-                   : big ? launch256<AKS, BKS, E, AB>(p, splitk, st, phased) : launch<AKS, BKS, E, AB>(p, splitk, st);  \
-    } else {                                                               \
-      rc_ = big ? launch256<AKS, BKS, E, AB>(p, splitk, st, phased) : launch<AKS, BKS, E, AB>(p, splitk, st);           \
-    }                                                                      \
-    if (rc_ == 0 && E == EPI_DGELU && dgelu_colsum != nullptr && p.C2 == nullptr)                                       \
-      rc_ = octmae_colsum_accum(C, 1, dgelu_colsum, NB, NA, ldc, stream);                                                \
-    if (rc_ == 0 && E == EPI_DGELU && dgelu_colsum != nullptr && p.ldc2 > 0)                                             \
-      rc_ = octmae_colsum_accum(colsum_ws, 0, dgelu_colsum, ws_rows, NA, NA, stream);                                     \
-    return rc_;                                                                                                           \
-  }
-  // forward linears (nn.Linear layout both sides)
-  OCTMAE_GEMM_CASE(0, 0, EPI_BF16, false)
+  int rc = PLAN_FALLBACK;
+#define OCTMAE_GEMM_CASE(AKS, BKS, E, AB) \
+  if (q.a_ks == AKS && q.b_ks == BKS && epilogue == E) rc = launch_plan<AKS, BKS, E, AB>(p, pl, split_ws, st);
+  OCTMAE_GEMM_CASE(0, 0, EPI_BF16, false)      // forward linears (nn.Linear layout both sides)
   OCTMAE_GEMM_CASE(0, 0, EPI_F32, false)
   OCTMAE_GEMM_CASE(0, 0, EPI_GELU, false)
   OCTMAE_GEMM_CASE(0, 0, EPI_RESID, false)
-  // dgrad (weight read k-strided)
-  OCTMAE_GEMM_CASE(1, 0, EPI_BF16, false)
+  OCTMAE_GEMM_CASE(1, 0, EPI_BF16, false)      // dgrad (weight read k-strided)
   OCTMAE_GEMM_CASE(1, 0, EPI_F32, false)
   OCTMAE_GEMM_CASE(1, 0, EPI_DGELU, false)
-  // wgrad (both k-strided, fp32 accumulate, lane-contiguous output).  A non-NULL C2: fp32 [NA] += column sums of A over k (the
-  // bias gradient, A = dY [K rows][NA]); fused into the phased 256-tile kernel, a separate pass over A otherwise.
-  if (a_kstrided == 1 && b_kstrided == 1 && epilogue == EPI_ACCUM && C2 != nullptr && !(big && phased)) {
-    p.C2 = nullptr;
-    if (int rc = octmae_colsum_accum(A, 1, reinterpret_cast<float*>(C2), K, NA, lda, stream)) return rc;
-  }
-  OCTMAE_GEMM_CASE(1, 1, EPI_ACCUM, true)
+  OCTMAE_GEMM_CASE(1, 1, EPI_ACCUM, true)      // wgrad (both k-strided, fp32 accumulate, lane-contiguous output)
 #undef OCTMAE_GEMM_CASE
-  return -2;  // layout / epilogue combination not built
-}
-
-// The split a weight-gradient launch of `tiles` 256 x 256 output tiles over M rows would use for a requested `splitk` (host-side
-// arithmetic only; no GPU is touched): writes the number of slices to *slices and the first k-tile of slice z to bounds[z]
-// (z = 0 .. slices, bounds[slices] = the number of 64-row k-tiles), and returns the length step kstagger (1/256 k-tiles; 0 = equal
-// slices).  `bounds` needs splitk + 1 ints.  For tests of the planning code (tests/test_cpu_host.py).
-extern "C" int octmae_wgrad_split_plan(int M, int splitk, int tiles, int* slices, int* bounds) {
-  OCTMAE_CHECK_ARG(M > 0 && tiles > 0 && slices && bounds);
-  const int ktiles = (M + TK - 1) / TK;
-  if (splitk < 1) splitk = 1;
-  if (splitk > ktiles) splitk = ktiles;
-  const int per = (ktiles + splitk - 1) / splitk;
-  splitk = (ktiles + per - 1) / per;
-  const int d = wgrad_stagger_for(ktiles, splitk, tiles);
-  *slices = splitk;
-  for (int z = 0; z < splitk; ++z) {
-    int a, b;
-    split_range_of(ktiles, per, d, z, splitk, a, b);
-    bounds[z] = a;
-    bounds[z + 1] = b;
-  }
-  return d;
-}
-
-// gW0[N0][K0] += dY0[M][N0]^T X0[M][K0]  and  gW1[N1][K1] += dY1[M][N1]^T X1[M][K1]  (gB: fp32 [N] += column sums of dY, or NULL) in
-// one launch of gemm256p_wgrad_pair_kernel.  Returns -2 when either problem does not take the 256-tile kernel (the caller then
-// issues two octmae_gemm_bf16 calls).
-extern "C" int octmae_wgrad_accum_pair(const void* dY0, const void* X0, float* gW0, float* gB0, int N0, int K0, int ldy0, int ldx0, int ldw0,
-                                       const void* dY1, const void* X1, float* gW1, float* gB1, int N1, int K1, int ldy1, int ldx1, int ldw1,
-                                       int M, int splitk, void* stream) {
-  OCTMAE_CHECK_ARG(dY0 && X0 && gW0 && dY1 && X1 && gW1 && M > 0 && N0 > 0 && K0 > 0 && N1 > 0 && K1 > 0);
-  OCTMAE_CHECK_ARG((ldy0 % 8) == 0 && (ldx0 % 8) == 0 && (ldy1 % 8) == 0 && (ldx1 % 8) == 0);
-  OCTMAE_CHECK_ARG((N0 % 8) == 0 && (K0 % 8) == 0 && (N1 % 8) == 0 && (K1 % 8) == 0);
-  GemmPair pp;
-  auto fill = [&](GemmParams& p, const void* dY, const void* X, float* gW, float* gB, int N, int K, int ldy, int ldx, int ldw) {
-    const size_t a_bytes = (size_t)M * ldy * 2, b_bytes = (size_t)M * ldx * 2;
-    if (!(N >= T2 && K >= T2 && a_bytes < 0xFFF00000ull && b_bytes < 0xFFF00000ull)) return false;
-    p.A = reinterpret_cast<const bf16_t*>(dY); p.B = reinterpret_cast<const bf16_t*>(X);
-    p.C = gW; p.C2 = gB; p.bias = nullptr; p.aux = nullptr; p.rowscale = nullptr; p.rows_per_scale = 1;
-    p.NA = N; p.NB = K; p.K = M; p.lda = ldy; p.ldb = ldx; p.ldc = ldw; p.ldaux = 0;
-    p.ktiles = (M + TK - 1) / TK;
-    p.tiles_a = (N + T2 - 1) / T2; p.tiles_b = (K + T2 - 1) / T2;
-    p.cgroup = p.tiles_a;
-    if (p.tiles_a * p.tiles_b > 32) {          // as in gemm_impl: a compact rectangle of tiles per XCD
-      int c = 32 / p.tiles_b;
-      if (c < 1) c = 1;
-      while (c > 1 && p.tiles_a % c != 0) --c;
-      p.cgroup = c;
-    }
-    p.ldc2 = 0; p.hd = 0; p.kstagger = 0;
-    p.atomic1 = wgrad_s1_atomic();
-    return true;
-  };
-  if (!fill(pp.p0, dY0, X0, gW0, gB0, N0, K0, ldy0, ldx0, ldw0) || !fill(pp.p1, dY1, X1, gW1, gB1, N1, K1, ldy1, ldx1, ldw1)) return -2;
-  const int ktiles = pp.p0.ktiles;
-  if (splitk < 1) splitk = 1;
-  if (splitk > ktiles) splitk = ktiles;
-  const int per = (ktiles + splitk - 1) / splitk;
-  splitk = (ktiles + per - 1) / per;
-  pp.p0.ktiles_per_split = pp.p1.ktiles_per_split = per;
-  pp.nt0 = pp.p0.tiles_a * pp.p0.tiles_b; pp.nt1 = pp.p1.tiles_a * pp.p1.tiles_b; pp.S = splitk;
-  pp.p0.kstagger = pp.p1.kstagger = wgrad_stagger_for(ktiles, splitk, pp.nt0 + pp.nt1);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // Small launches (round 6): 128 x 128 tiles when the cost model prices them faster.  Microseconds, fitted with tools/gemm_small_fit.py:
-  // the 256-tile pair ~1.4 per k-tile of a slice + 0.22 per tile and slice of fp32 atomics (split) or ~10 of read-modify-write
-  // (unsplit); a 128-tile workgroup (both operands through transposing LDS reads) ~0.6 per k-tile alone on its CU (4-stage ring), ~1.05
-  // two per CU (2-stage), + ~8, + 0.055 per tile and slice of atomics.  Measured (profiles/r06_gemm_small_fit.txt): one volume, encoder
-  // fc pair 40 -> 32 us, qkv + proj 40 -> 26, decoder 52 -> 39 and 40 -> 32; four volumes 113 -> 90 and 77 -> 64.  Short reductions only
-  // (<= 96 k-tiles per launch): beyond, both kernels stream and the larger tile wins.
-  {
-    static const int env = getenv("OCTMAE_GEMM_SMALL") ? atoi(getenv("OCTMAE_GEMM_SMALL")) : -1;
-    const int on = env >= 0 ? env : g_gemm_small.load(std::memory_order_relaxed);
-    const int G = device_cus();
-    const long long nt128_0 = (long long)((N0 + T1 - 1) / T1) * ((K0 + T1 - 1) / T1), nt128_1 = (long long)((N1 + T1 - 1) / T1) * ((K1 + T1 - 1) / T1);
-    const long long nt128 = nt128_0 + nt128_1;
-    static const int maxkt = getenv("OCTMAE_WGRAD128_MAXKT") ? atoi(getenv("OCTMAE_WGRAD128_MAXKT")) : 96;      // A/B runs
-    if (on && ktiles <= maxkt && nt128 <= 2 * G) {
-      const double c256 = 1.4 * per + (splitk > 1 ? 0.22 * (pp.nt0 + pp.nt1) * splitk : 10.0);
-      double best = 1e30;
-      int bS = 1, bN = 4;
-      for (int S2 = 1; S2 <= 4 && S2 <= splitk; ++S2) {        // never more slices than the caller allows (splitk = 1: no atomics)
-        const int kper = (ktiles + S2 - 1) / S2;
-        if (S2 > 1 && (kper < 8 || (long long)(S2 - 1) * kper >= ktiles)) continue;
-        const long long wg = nt128 * S2;
-        const double at = S2 > 1 ? 0.055 * nt128 * S2 : 0.0;
-        if (wg <= G && 0.6 * kper + 8.0 + at < best) { best = 0.6 * kper + 8.0 + at; bS = S2; bN = 4; }
-        if (wg > G && wg <= 2 * G && 1.05 * kper + 8.0 + at < best) { best = 1.05 * kper + 8.0 + at; bS = S2; bN = 2; }
-      }
-      if (best < 0.9 * c256) {
-        auto to128 = [&](GemmParams& p, int N, int K) {
-          p.tiles_a = (N + T1 - 1) / T1; p.tiles_b = (K + T1 - 1) / T1; p.cgroup = p.tiles_a; p.kstagger = 0;
-          p.ktiles_per_split = (ktiles + bS - 1) / bS;
-        };
-        // the bias gradients ride in the 256-tile kernel's main loop; on this path they are a pass of their own over dY
-        if (gB0 != nullptr) { if (int rc = octmae_colsum_accum(dY0, 1, gB0, M, N0, ldy0, stream)) return rc; }
-        if (gB1 != nullptr) { if (int rc = octmae_colsum_accum(dY1, 1, gB1, M, N1, ldy1, stream)) return rc; }
-        pp.p0.C2 = nullptr; pp.p1.C2 = nullptr;
-        to128(pp.p0, N0, K0); to128(pp.p1, N1, K1);
-        pp.nt0 = (int)nt128_0; pp.nt1 = (int)nt128_1; pp.S = bS;
-        if (bN == 2) {
-          auto k2 = gemm128d_wgrad_kernel<2>;
-          static DynLdsOnce once2;
-          if (int rc = once2.ensure(reinterpret_cast<const void*>(k2), 2 * D_STAGE)) return rc;
-          hipLaunchKernelGGL(k2, dim3((unsigned)(nt128 * bS), 1, 1), dim3(256), 2 * D_STAGE, st, pp);
-        } else {
-          auto k4 = gemm128d_wgrad_kernel<4>;
-          static DynLdsOnce once4;
-          if (int rc = once4.ensure(reinterpret_cast<const void*>(k4), 4 * D_STAGE)) return rc;
-          hipLaunchKernelGGL(k4, dim3((unsigned)(nt128 * bS), 1, 1), dim3(256), 4 * D_STAGE, st, pp);
-        }
-        OCTMAE_LAUNCH_CHECK();
-        g_small_wgrad_launches.fetch_add(1, std::memory_order_relaxed);
-        return 0;
-      }
-    }
-  }
-  auto kern = gemm256p_wgrad_pair_kernel;
-  static DynLdsOnce once;
-  if (int rc = once.ensure(reinterpret_cast<const void*>(kern), 4 * TILE2_BYTES)) return rc;
-  hipLaunchKernelGGL(kern, dim3((pp.nt0 + pp.nt1) * splitk, 1, 1), dim3(512), 4 * TILE2_BYTES, st, pp);
-  OCTMAE_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int octmae_gemm_bf16(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
-                                int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided,
-                                int b_kstrided, int epilogue, int splitk, void* stream) {
-  return gemm_impl(A, B, C, C2, bias, aux, NA, NB, K, lda, ldb, ldc, ldaux, a_kstrided, b_kstrided, epilogue, splitk, stream,
-                   nullptr, 1);
-}
-
-// Which kernel a forward / dgrad launch of NA x NB x K would take on `cus` CUs under the current "gemm_small" option (host-side
-// arithmetic only, no GPU is touched; for tests of the planning code): returns 1 for the small-launch kernel (gemm128d_kernel) and
-// writes its k split to *slices and its ring depth to *stages, 0 for the 256-tile / register-staged kernels.  `have_ws`: a split
-// workspace is lent; `big_ok`: the problem qualifies for the 256-tile kernel.
-extern "C" int octmae_gemm_small_plan(int NA, int NB, int K, int cus, int have_ws, int big_ok, int* slices, int* stages) {
-  OCTMAE_CHECK_ARG(NA > 0 && NB > 0 && K > 0 && cus > 0 && slices && stages);
-  const Plan128 pl = plan128(NA, NB, K, cus, have_ws != 0, big_ok != 0);
-  *slices = pl.S; *stages = pl.nst;
-  return pl.use;
+  if (rc == 0 && pl.colsum == Colsum::PassAfter) rc = octmae_colsum_accum(C, 1, colsum, NB, NA, ldc, stream);
+  if (rc == 0 && pl.colsum == Colsum::FoldWs) rc = octmae_colsum_accum(colsum_ws, 0, colsum, pl.ws_rows, NA, NA, stream);
+  return rc;
 }
 
 extern "C" int octmae_gemm_split_ws_kib(void) { return (int)((d_ws_bytes() + 1023) / 1024); }
-
 extern "C" int octmae_gemm_bf16_ws(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
                                    int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided,
                                    int b_kstrided, int epilogue, int splitk, void* split_ws, long long split_ws_bytes, void* stream) {
-  return gemm_impl(A, B, C, C2, bias, aux, NA, NB, K, lda, ldb, ldc, ldaux, a_kstrided, b_kstrided, epilogue, splitk, stream,
-                   nullptr, 1, nullptr, split_ws, split_ws_bytes);
+  return gemm_impl(A, B, C, C2, bias, aux, NA, NB, K, lda, ldb, ldc, ldaux, a_kstrided, b_kstrided, epilogue & 0xff,
+                   decode_variant(epilogue), splitk, stream, nullptr, 1, nullptr, split_ws, split_ws_bytes);
+}
+extern "C" int octmae_gemm_bf16(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
+                                int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided,
+                                int b_kstrided, int epilogue, int splitk, void* stream) {
+  return octmae_gemm_bf16_ws(A, B, C, C2, bias, aux, NA, NB, K, lda, ldb, ldc, ldaux, a_kstrided, b_kstrided, epilogue, splitk, nullptr, 0, stream);
 }
 
 extern "C" int octmae_linear_resid_rowscale(const void* W, const void* X, float* out, const float* bias, const float* res,
                                             const float* rowscale, int rows_per_scale, int N, int M, int K, int ldw, int ldx,
                                             int ldout, int ldres, int variant, void* split_ws, long long split_ws_bytes, void* stream) {
   OCTMAE_CHECK_ARG(rowscale != nullptr && rows_per_scale > 0);
-  return gemm_impl(W, X, out, nullptr, bias, res, N, M, K, ldw, ldx, ldout, ldres, 0, 0, EPI_RESID | (variant & 0x77F00), 1,
+  return gemm_impl(W, X, out, nullptr, bias, res, N, M, K, ldw, ldx, ldout, ldres, 0, 0, EPI_RESID, decode_variant(variant), 1,
                    stream, rowscale, rows_per_scale, nullptr, split_ws, split_ws_bytes);
+}
+extern "C" int octmae_dgelu_colsum_ws_rows(int M) { return M > 0 ? 4 * cdiv(M, T2) : 0; }
+extern "C" int octmae_linear_dgrad_dgelu(const void* W, const void* dY, void* dX, const void* pre, float* ws, float* bias_grad,
+                                         int M, int N, int K, int ldw, int ldy, int ldx, int ldpre, int variant, void* split_ws,
+                                         long long split_ws_bytes, void* stream) {
+  OCTMAE_CHECK_ARG(bias_grad == nullptr || ws != nullptr);
+  return gemm_impl(W, dY, dX, bias_grad, nullptr, pre, K, M, N, ldw, ldy, ldx, ldpre, 1, 0, EPI_DGELU, decode_variant(variant), 1, stream,
+                   nullptr, 1, bias_grad != nullptr ? ws : nullptr, split_ws, split_ws_bytes);
 }
 
 // dX[M][K] bf16 = dY[M][N] @ W[N][K]  and  delta[M][H] f32 = -sum over each head's hd columns of dX * O  (O bf16 [M][K], K = H * hd):
@@ -1686,53 +1365,87 @@ extern "C" int octmae_linear_resid_rowscale(const void* W, const void* X, float*
 extern "C" int octmae_linear_dgrad_delta(const void* W, const void* dY, void* dX, const void* O, float* delta, int M, int N, int K,
                                          int ldw, int ldy, int ldx, int ldo, int H, int hd, int variant, void* split_ws,
                                          long long split_ws_bytes, void* stream) {
-  OCTMAE_CHECK_ARG(W && dY && dX && O && delta && M > 0 && N > 0 && K > 0);
+  OCTMAE_CHECK_ARG(W && dY && dX && O && delta && M > 0 && N > 0 && K > 0 && K % 8 == 0 && N % 8 == 0);
   OCTMAE_CHECK_ARG((hd == 32 || hd == 64) && H > 0 && H * hd == K && (ldw % 8) == 0 && (ldy % 8) == 0 && (ldx % 4) == 0 && (ldo % 4) == 0);
-  OCTMAE_CHECK_ARG(K % 8 == 0 && N % 8 == 0);
-  const size_t a_bytes = (size_t)N * ldw * 2, b_bytes = (size_t)M * ldy * 2;
-  const bool big = K >= T2 && M >= T2 && a_bytes < 0xFFF00000ull && b_bytes < 0xFFF00000ull && ((variant >> 8) & 1) == 0 &&
-                   (N % TK) == 0 && (K & 7) == 0;
-  GemmParams p;
-  p.A = reinterpret_cast<const bf16_t*>(W); p.B = reinterpret_cast<const bf16_t*>(dY);
-  p.C = dX; p.C2 = delta; p.bias = nullptr; p.aux = O; p.rowscale = nullptr; p.rows_per_scale = 1;
-  p.NA = K; p.NB = M; p.K = N; p.lda = ldw; p.ldb = ldy; p.ldc = ldx; p.ldaux = ldo;
-  p.ktiles = (N + TK - 1) / TK; p.ktiles_per_split = p.ktiles;
-  p.tiles_a = (K + T2 - 1) / T2; p.tiles_b = (M + T2 - 1) / T2;
-  p.cgroup = p.tiles_a;
-  if (p.tiles_a >= 16 && p.tiles_a % 4 == 0 && 4 * (size_t)T2 * N * 2 <= (2u << 20)) p.cgroup = 4;
-  p.hd = hd; p.ldc2 = H; p.kstagger = 0;
+  const GemmProblem q{K, M, N, ldw, ldy, true, false, EPI_DELTA, 1, false, false};
+  const bool have_ws = split_ws != nullptr && split_ws_bytes >= d_ws_bytes();
+  const GemmPlan pl = plan_gemm(q, decode_variant(variant), current_options(), device_cus, have_ws);
+  if (pl.status != 0) return pl.status;
+  GemmParams p = make_params(W, dY, dX, delta, O, K, M, N, ldw, ldy, ldx, ldo);
+  p.hd = hd; p.ldc2 = H;
+  apply_plan(p, pl);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int force128 = ((variant >> 12) & 1) ? 4 : ((variant >> 13) & 1) ? 2 : 0;
-  if (((variant >> 8) & 1) == 0 && ((variant >> 14) & 1) == 0 && gemm128_ok(K, M, N, ldw, ldy, true, false)) {
-    const bool have_ws = split_ws != nullptr && split_ws_bytes >= d_ws_bytes();
-    Plan128 pl{0, 1, 4};
-    if (force128) {
-      pl.use = 1; pl.nst = force128;
-      pl.S = (variant >> 16) & 7;
-      if (pl.S < 1) pl.S = 1;
-      if (pl.S > 4) pl.S = 4;
-      while (pl.S > 1 && (!have_ws || (long long)(pl.S - 1) * ((p.ktiles + pl.S - 1) / pl.S) >= p.ktiles ||
-                          (long long)((K + T1 - 1) / T1) * ((M + T1 - 1) / T1) * pl.S > D_WS_SLOTS)) --pl.S;
-    } else {
-      pl = plan128(K, M, N, device_cus(), have_ws, big);
-    }
-    if (pl.use) return launch128d<true, false, EPI_DELTA>(p, pl, split_ws, st);
-  }
-  if (!big) return -2;
-  auto kern = gemm256p_kernel<true, false, EPI_DELTA, false>;
-  static DynLdsOnce once;
-  if (int rc = once.ensure(reinterpret_cast<const void*>(kern), 4 * TILE2_BYTES)) return rc;
-  hipLaunchKernelGGL(kern, dim3(p.tiles_a * p.tiles_b, 1, 1), dim3(512), 4 * TILE2_BYTES, st, p);
-  OCTMAE_LAUNCH_CHECK();
-  return 0;
+  if (pl.kernel == GemmKernel::Small128d) return launch128d<true, false, EPI_DELTA>(p, pl, split_ws, st);
+  return launch_dyn<gemm256p_kernel<true, false, EPI_DELTA, false>>(dim3(pl.grid()), 512, 4 * TILE2_BYTES, st, p);
 }
 
-extern "C" int octmae_dgelu_colsum_ws_rows(int M) { return M > 0 ? 4 * ((M + T2 - 1) / T2) : 0; }
+// gW0[N0][K0] += dY0[M][N0]^T X0[M][K0]  and  gW1[N1][K1] += dY1[M][N1]^T X1[M][K1]  (gB: fp32 [N] += column sums of dY, or NULL) in
+// one launch of gemm256p_wgrad_pair_kernel or gemm128d_wgrad_kernel (plan_wgrad_pair).  Returns -2 when either problem does not take
+// the 256-tile kernel (the caller then issues two octmae_gemm_bf16 calls).
+extern "C" int octmae_wgrad_accum_pair(const void* dY0, const void* X0, float* gW0, float* gB0, int N0, int K0, int ldy0, int ldx0, int ldw0,
+                                       const void* dY1, const void* X1, float* gW1, float* gB1, int N1, int K1, int ldy1, int ldx1, int ldw1,
+                                       int M, int splitk, void* stream) {
+  OCTMAE_CHECK_ARG(dY0 && X0 && gW0 && dY1 && X1 && gW1 && M > 0 && N0 > 0 && K0 > 0 && N1 > 0 && K1 > 0);
+  OCTMAE_CHECK_ARG((ldy0 % 8) == 0 && (ldx0 % 8) == 0 && (ldy1 % 8) == 0 && (ldx1 % 8) == 0);
+  OCTMAE_CHECK_ARG((N0 % 8) == 0 && (K0 % 8) == 0 && (N1 % 8) == 0 && (K1 % 8) == 0);
+  const int N[2] = {N0, N1}, K[2] = {K0, K1}, ldy[2] = {ldy0, ldy1}, ldx[2] = {ldx0, ldx1}, ldw[2] = {ldw0, ldw1};
+  const void* const dY[2] = {dY0, dY1}, * const X[2] = {X0, X1};
+  float* const gW[2] = {gW0, gW1}, * const gB[2] = {gB0, gB1};
+  const PairPlan pl = plan_wgrad_pair(N, K, ldy, ldx, M, splitk, current_options(), device_cus());
+  if (pl.status != 0) return pl.status;
+  GemmPair pp;
+  for (int i = 0; i < 2; ++i) {
+    GemmParams& p = i ? pp.p1 : pp.p0;
+    if (gB[i] != nullptr && pl.colsum == Colsum::PassBefore)
+      if (int rc = octmae_colsum_accum(dY[i], 1, gB[i], M, N[i], ldy[i], stream)) return rc;
+    p = make_params(dY[i], X[i], gW[i], pl.colsum == Colsum::Fused ? gB[i] : nullptr, nullptr, N[i], K[i], M, ldy[i], ldx[i], ldw[i], 0);
+    p.tiles_a = pl.tiles_a[i]; p.tiles_b = pl.tiles_b[i]; p.cgroup = pl.cgroup[i];
+    p.ktiles_per_split = pl.ktiles_per_split; p.kstagger = pl.kstagger; p.atomic1 = pl.atomic1;
+  }
+  pp.nt0 = pl.tiles_a[0] * pl.tiles_b[0]; pp.nt1 = pl.tiles_a[1] * pl.tiles_b[1]; pp.S = pl.slices;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (pl.kernel == GemmKernel::Phased256) return launch_dyn<gemm256p_wgrad_pair_kernel>(dim3(pl.grid()), 512, 4 * TILE2_BYTES, st, pp);
+  const int rc = pl.nst == 2 ? launch_dyn<gemm128d_wgrad_kernel<2>>(dim3(pl.grid()), 256, 2 * D_STAGE, st, pp)
+                             : launch_dyn<gemm128d_wgrad_kernel<4>>(dim3(pl.grid()), 256, 4 * D_STAGE, st, pp);
+  if (rc == 0) g_small_wgrad_launches.fetch_add(1, std::memory_order_relaxed);
+  return rc;
+}
 
-extern "C" int octmae_linear_dgrad_dgelu(const void* W, const void* dY, void* dX, const void* pre, float* ws, float* bias_grad,
-                                         int M, int N, int K, int ldw, int ldy, int ldx, int ldpre, int variant, void* split_ws,
-                                         long long split_ws_bytes, void* stream) {
-  OCTMAE_CHECK_ARG(bias_grad == nullptr || ws != nullptr);
-  return gemm_impl(W, dY, dX, bias_grad, nullptr, pre, K, M, N, ldw, ldy, ldx, ldpre, 1, 0, EPI_DGELU | (variant & 0x7FF00), 1, stream, nullptr, 1,
-                   bias_grad != nullptr ? ws : nullptr, split_ws, split_ws_bytes);
+// ---- plan queries: host-side arithmetic only, no GPU is touched (tests/test_cpu_host.py; include/octmae.h) ---------------------------
+extern "C" int octmae_gemm_small_plan(int NA, int NB, int K, int cus, int have_ws, int big_ok, int* slices, int* stages) {
+  OCTMAE_CHECK_ARG(NA > 0 && NB > 0 && K > 0 && cus > 0 && slices && stages);
+  const Plan128 pl = plan128(NA, NB, K, cus, have_ws != 0, big_ok != 0, current_options());
+  *slices = pl.S; *stages = pl.nst;
+  return pl.use;
+}
+extern "C" int octmae_wgrad_split_plan(int M, int splitk, int tiles, int* slices, int* bounds) {
+  OCTMAE_CHECK_ARG(M > 0 && tiles > 0 && slices && bounds);
+  const int ktiles = cdiv(M, TK);
+  const Split s = normalise_split(ktiles, splitk);
+  const int d = wgrad_stagger_for(ktiles, s.slices, tiles, current_options().wgrad_stagger);
+  *slices = s.slices;
+  for (int z = 0; z < s.slices; ++z) split_range_of(ktiles, s.per, d, z, s.slices, bounds[z], bounds[z + 1]);
+  return d;
+}
+extern "C" int octmae_gemm_plan(int kind, int NA, int NB, int K, int lda, int ldb, int variant, int splitk, int have_ws, int cus, int* out) {
+  OCTMAE_CHECK_ARG(kind >= 0 && kind <= 6 && NA > 0 && NB > 0 && K > 0 && cus > 0 && out);
+  const int epi = kind == 0 || kind == 1 ? EPI_BF16 : kind <= 3 ? EPI_DGELU : kind == 4 ? EPI_DELTA : EPI_ACCUM;       // include/octmae.h
+  const GemmProblem q{NA, NB, K, lda, ldb, kind >= 1, kind >= 5, epi, splitk, kind == 2 || kind == 3 || kind == 6, kind == 3};
+  const GemmPlan pl = plan_gemm(q, decode_variant(variant), current_options(), [cus] { return cus; }, have_ws != 0);
+  const bool small = pl.kernel == GemmKernel::Small128d;
+  const int o[13] = {(int)pl.kernel, pl.grid(), pl.tiles_a, pl.tiles_b, pl.cgroup,                                // [0..4]
+                     pl.slices, pl.ktiles_per_split, pl.kstagger, pl.atomic1, small ? pl.nst : 0,                 // [5..9]
+                     small ? pl.slices : 1, pl.colsum == Colsum::FoldWs ? pl.ws_rows : 0, (int)pl.colsum};        // [10..12]
+  for (int i = 0; i < 13; ++i) out[i] = pl.status == 0 ? o[i] : 0;
+  return pl.status;
+}
+extern "C" int octmae_wgrad_pair_plan(int N0, int K0, int ldy0, int ldx0, int N1, int K1, int ldy1, int ldx1, int M, int splitk, int cus, int* out) {
+  OCTMAE_CHECK_ARG(N0 > 0 && K0 > 0 && N1 > 0 && K1 > 0 && M > 0 && cus > 0 && out);
+  const int N[2] = {N0, N1}, K[2] = {K0, K1}, ldy[2] = {ldy0, ldy1}, ldx[2] = {ldx0, ldx1};
+  const PairPlan pl = plan_wgrad_pair(N, K, ldy, ldx, M, splitk, current_options(), cus);
+  const int o[14] = {(int)pl.kernel, pl.grid(), pl.slices, pl.ktiles_per_split, pl.kstagger, pl.atomic1,           // [0..5]
+                     pl.nst, (int)pl.colsum, pl.tiles_a[0], pl.tiles_b[0], pl.cgroup[0],                          // [6..10]
+                     pl.tiles_a[1], pl.tiles_b[1], pl.cgroup[1]};                                                 // [11..13]
+  for (int i = 0; i < 14; ++i) out[i] = pl.status == 0 ? o[i] : 0;
+  return pl.status;
 }

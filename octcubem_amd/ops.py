@@ -353,7 +353,7 @@ def linear_dgrad_delta(dy: torch.Tensor, w: torch.Tensor, o: torch.Tensor, H: in
         rc[0] = load().octmae_linear_dgrad_delta(*args)
 
     _launch("gemm_dgrad_epi6", 2.0 * K * M * N, 2.0 * (K * N + M * N) + 2.0 * K * M + 2.0 * K * M, run)
-    if rc[0] == -2:           # the library's own applicability test said no (e.g. an operand beyond a 32-bit buffer range): plain dgrad
+    if rc[0] == -2:           # the library's own applicability test (plan_gemm, EPI_DELTA) said no (e.g. an operand beyond a 32-bit buffer range): plain dgrad
         return linear_dgrad(dy, w), None
     if rc[0] != 0:
         raise RuntimeError(f"octmae_linear_dgrad_delta failed (rc={rc[0]})")
@@ -383,7 +383,7 @@ def linear_wgrad_accum(dy: torch.Tensor, x: torch.Tensor, gw: torch.Tensor, gb: 
     separate pass over dY."""
     M, N = dy.shape
     K = x.shape[1]
-    big = N >= 256 and K >= 256 and not FORCE_SMALL_TILE          # mirrors the tile choice in octmae_gemm_bf16
+    big = N >= 256 and K >= 256 and not FORCE_SMALL_TILE          # mirrors fits_256 / plan_gemm (csrc/gemm_plan.hpp)
     t = 256 if big else 128
     tiles = ((N + t - 1) // t) * ((K + t - 1) // t)
     ktiles = (M + 63) // 64
@@ -404,7 +404,7 @@ def linear_wgrad_accum_pair(first, second):
     M = dy0.shape[0]
     ok = (WGRAD_PAIR and not FORCE_SMALL_TILE and dy1.shape[0] == M and x0.shape[0] == M and x1.shape[0] == M
           and min(dy0.shape[1], x0.shape[1], dy1.shape[1], x1.shape[1]) >= 256
-          # the library's own applicability test (each operand inside one 32-bit buffer descriptor), so that -2 is not met here
+          # the library's own applicability test (plan_wgrad_pair: fits_256, each operand inside one 32-bit buffer descriptor), so that -2 is not met here
           and 2 * M * max(dy0.stride(0), x0.stride(0), dy1.stride(0), x1.stride(0)) < 0xFFF00000)
     if ok:
         tiles = sum(((dy.shape[1] + 255) // 256) * ((x.shape[1] + 255) // 256) for dy, x in ((dy0, x0), (dy1, x1)))

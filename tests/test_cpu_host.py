@@ -461,3 +461,119 @@ def test_bench_dump_outputs_writes_a_fixed_float32_sample(tmp_path, monkeypatch)
     assert set(a["pred"].tolist()) <= set(pred.reshape(-1).tolist())
     assert np.array_equal(a["params"][64:94], model[0].bias.detach().numpy())          # small tensors whole, in parameter order
     assert np.array_equal(a["grads"][-2:], model[1].bias.grad.numpy())
+
+
+# ------------------------------------------------------------------------------------------------ the GEMM launch planner
+PLAN_FWD, PLAN_DGRAD, PLAN_DGELU, PLAN_DGELU_WS, PLAN_DELTA, PLAN_WGRAD, PLAN_WGRAD_BIAS = range(7)       # `kind` of octmae_gemm_plan
+TILE128, TWOSTAGE256, PHASED256, SMALL128D = range(4)                                                     # out[0]: the kernel family
+PLAN_FIELDS = ("kernel", "grid", "tiles_a", "tiles_b", "cgroup", "slices", "per", "kstagger", "atomic1", "nst", "small_S", "ws_rows", "colsum")
+
+
+def _both_libraries():
+    from octcubem_amd import _lib
+    return [_lib.load(), ctypes.CDLL(os.path.join(ROOT, "octcubem_amd", "liboctmae_f16.so"))]
+
+
+def _gemm_plan(lib, kind, NA, NB, K, lda=None, ldb=None, variant=0, splitk=1, ws=1, cus=256):
+    """(rc, fields) for X[a][b] = sum_k A[a][k] B[b][k]; the default leading dimensions are those of packed operands"""
+    a_ks = kind != PLAN_FWD
+    b_ks = kind in (PLAN_WGRAD, PLAN_WGRAD_BIAS)
+    out = (ctypes.c_int * 13)()
+    rc = lib.octmae_gemm_plan(kind, NA, NB, K, lda or (NA if a_ks else K), ldb or (NB if b_ks else K), variant, splitk, ws, cus, out)
+    return rc, dict(zip(PLAN_FIELDS, out))
+
+
+def _fits_256(NA, NB, K, kind):
+    return NA >= 256 and NB >= 256 and (kind in (PLAN_WGRAD, PLAN_WGRAD_BIAS) or K % 64 == 0)
+
+
+def test_gemm_plan_variant_bits_mean_what_they_say():
+    """octmae_gemm_plan on both libraries: bit 8 gives the 128-tile register-staged kernel; bits 9 / 10 the two-stage / phased
+    256-tile kernel wherever the problem takes 256-tiles and never the small-launch kernel (dgrad + delta is built for the phased
+    main loop only: bit 9 gives that one there); bit 14 never the small-launch kernel; bits 12 / 13 the small-launch kernel with
+    that ring depth wherever its operands allow (NA % 8 == 0, whole k-tiles), its split clamped so that no slice is empty and
+    slices x tiles fit the workspace's 1024 slots; and no plan splits a small launch without a workspace."""
+    for lib in _both_libraries():
+        for NA, NB, K in [(N, M, K) for M in (64, 200, 256, 1281, 5121, 8 * 5121) for N in (136, 384, 512, 1024, 4096) for K in (64, 72, 512, 4096)]:
+            kt = -(-K // 64)
+            for kind in (PLAN_FWD, PLAN_DGRAD, PLAN_DGELU, PLAN_DGELU_WS, PLAN_DELTA, PLAN_WGRAD, PLAN_WGRAD_BIAS):
+                wgrad = kind in (PLAN_WGRAD, PLAN_WGRAD_BIAS)
+                if (wgrad and NB % 8) or (not wgrad and K % 8):
+                    continue                                                 # the entry points reject these operands
+                big, small_ok = _fits_256(NA, NB, K, kind), not wgrad and NA % 8 == 0 and K % 64 == 0
+                for ws in (0, 1):
+                    plan = lambda bits, splitk=1: _gemm_plan(lib, kind, NA, NB, K, variant=bits, splitk=splitk, ws=ws)    # noqa: E731
+                    rc, p = plan(0x100)
+                    assert (rc, p["kernel"]) == ((0, TILE128) if kind != PLAN_DELTA else (-2, 0))
+                    for bits, fam in ((0x200, TWOSTAGE256), (0x400, PHASED256), (0x600, PHASED256)):
+                        rc, p = plan(bits)
+                        if kind == PLAN_DELTA:
+                            assert (rc, p["kernel"]) == ((0, PHASED256) if big else (-2, 0))
+                        else:
+                            assert rc == 0 and p["kernel"] == (fam if big else TILE128)
+                    rc, p = plan(0x4000)
+                    assert p["kernel"] != SMALL128D and (rc == 0 or (kind == PLAN_DELTA and not big))
+                    rc, p = plan(0)
+                    assert rc == -2 or p["small_S"] == 1 or (ws and p["kernel"] == SMALL128D)
+                    for bits, nst in ((0x1000, 4), (0x2000, 2)):
+                        for S, via_bits in ((1, 0), (2, 0), (3, 1), (4, 1), (7, 1)):
+                            rc, p = plan(bits | (S << 16 if via_bits else 0), splitk=1 if via_bits else S)
+                            if not small_ok:
+                                assert p["kernel"] != SMALL128D
+                                continue
+                            assert rc == 0 and p["kernel"] == SMALL128D and p["nst"] == nst
+                            s_ = p["small_S"]
+                            nt = -(-NA // 128) * -(-NB // 128)
+                            assert 1 <= s_ <= min(S, 4) and p["slices"] == s_ and p["grid"] == nt * s_ and p["per"] == -(-kt // s_)
+                            assert s_ == 1 or (ws and (s_ - 1) * -(-kt // s_) < kt and nt * s_ <= 1024)
+                            # the largest split <= the request that meets the three conditions
+                            assert all(not (ws and (t - 1) * -(-kt // t) < kt and nt * t <= 1024) for t in range(s_ + 1, min(S, 4) + 1))
+
+
+def test_gemm_plan_agrees_with_the_two_older_plan_queries():
+    """octmae_gemm_small_plan / octmae_wgrad_split_plan are implemented over the same planner: on every case of test_small_launch_plan
+    the small-launch decision, split and ring depth of octmae_gemm_plan are theirs, and a weight-gradient plan has the slices and the
+    stagger octmae_wgrad_split_plan reports."""
+    S, st = ctypes.c_int(0), ctypes.c_int(0)
+    for lib in _both_libraries():
+        for cus in (256, 304, 64):
+            for NA in (512, 1024, 1536, 2048, 3072, 4096):
+                for NB in (1, 64, 1281, 2562, 5121, 4 * 1281, 8 * 5121, 32 * 1281, 128 * 5121):
+                    for K in (64, 512, 768, 1024, 2048, 3072, 4096):
+                        for ws in (0, 1):
+                            use = lib.octmae_gemm_small_plan(NA, NB, K, cus, ws, int(NA >= 256 and NB >= 256), ctypes.byref(S), ctypes.byref(st))
+                            for kind in (PLAN_FWD, PLAN_DGRAD):
+                                rc, p = _gemm_plan(lib, kind, NA, NB, K, ws=ws, cus=cus)
+                                assert rc == 0 and (p["kernel"] == SMALL128D) == bool(use)
+                                if use:
+                                    assert (p["small_S"], p["nst"]) == (S.value, st.value)
+        bounds = (ctypes.c_int * 65)()
+        for M in (64, 1281, 5121, 4 * 1281, 32 * 1281, 32 * 5121, 128 * 5121):
+            for N, K in ((1024, 1024), (3072, 1024), (1024, 4096), (512, 512), (512, 2048), (384, 128)):
+                for splitk in (1, 2, 3, 8, 16, 64):
+                    rc, p = _gemm_plan(lib, PLAN_WGRAD_BIAS, N, K, M, variant=0x4000, splitk=splitk)
+                    d = lib.octmae_wgrad_split_plan(M, splitk, p["tiles_a"] * p["tiles_b"], ctypes.byref(S), bounds)
+                    assert rc == 0 and p["slices"] == S.value and p["grid"] == p["tiles_a"] * p["tiles_b"] * S.value
+                    assert p["kstagger"] == (d if p["kernel"] != TILE128 else 0)
+
+
+def test_gemm_plans_of_the_model_shapes_are_those_the_previous_dispatch_launched():
+    """tests/golden/gemm_plan_pins.json: kernel family, workgroups, k slices and ring depth of every forward / dgrad / dgrad x GELU' /
+    dgrad + delta launch and weight-gradient pair of the ViT-L encoder and decoder Linears at 1, 4, 32 and 128 volumes and of the
+    GEMM_SHAPES of tests/test_gpu_kernels.py, on 256 CUs with and without the split-K workspace.  The values were NOT produced by this
+    planner: they were read off a rocprofv3 kernel trace of tools/gemm_dispatch_sweep.py on an MI355X running the commit BEFORE the
+    planner existed (kernel name -> family, its ring-depth template argument -> ring depth, grid / workgroup -> workgroups and
+    slices; profiles/gemm_dispatch_sweep_parent_vs_branch.txt).  cgroup is a kernel argument and not visible in a trace: its
+    columns (one per problem for a pair) are that commit's rule in gemm_impl / octmae_wgrad_accum_pair, transcribed by hand into the
+    script that wrote the file -- a second statement of the rule, not an observation."""
+    import json
+    pins = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_plan_pins.json")))
+    assert len(pins["gemm"]) >= 340 and len(pins["pair"]) == 16
+    for lib in _both_libraries():
+        for name, kind, NA, NB, K, splitk, ws, family, grid, cgroup, slices, nst in pins["gemm"]:
+            rc, p = _gemm_plan(lib, kind, NA, NB, K, splitk=splitk, ws=ws)
+            assert (rc, p["kernel"], p["grid"], p["cgroup"], p["slices"], p["nst"]) == (0, family, grid, cgroup, slices, nst), (name, ws, p)
+        out = (ctypes.c_int * 14)()
+        for name, N0, K0, N1, K1, M, splitk, family, grid, slices, nst, cgroup0, cgroup1 in pins["pair"]:
+            rc = lib.octmae_wgrad_pair_plan(N0, K0, N0, K0, N1, K1, N1, K1, M, splitk, 256, out)
+            assert (rc, out[0], out[1], out[2], out[6], out[10], out[13]) == (0, family, grid, slices, nst, cgroup0, cgroup1), (name, list(out))

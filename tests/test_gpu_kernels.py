@@ -89,12 +89,47 @@ def tile_variant(request):
     ops.FORCE_PHASED = request.param == "phased"
     ops.FORCE_SMALL_LAUNCH = {"small4": 4, "small2": 2, "small4_split3": 4, "small2_split2": 2, "never_small": -1}.get(request.param, 0)
     ops.FORCE_SPLITK = {"small4_split3": 3, "small2_split2": 2}.get(request.param, 1)
-    yield request.param
-    ops.FORCE_SMALL_TILE = False
-    ops.FORCE_TWO_STAGE = False
-    ops.FORCE_PHASED = False
-    ops.FORCE_SMALL_LAUNCH = 0
-    ops.FORCE_SPLITK = 1
+    # The forced variants mean what they say (csrc/gemm_plan.hpp): under a forced small launch every forward / dgrad problem whose
+    # operands that kernel can take (gemm128_ok: NA % 8 == 0, whole k-tiles, 32-bit buffer ranges) runs it; under the four variants that
+    # name another kernel the small-launch counter does not move across the test.
+    small_before, real_call, real_delta, missed = ops.set_option("gemm_small_launches", 0), ops.call, ops.linear_dgrad_delta, []
+    # (NA, NB, K, lda, ldb) among the arguments of the forward / dgrad entry points that go through ops.call
+    where = {"octmae_gemm_bf16_ws": (6, 7, 8, 9, 10), "octmae_linear_resid_rowscale": (7, 8, 9, 10, 11), "octmae_linear_dgrad_dgelu": (8, 6, 7, 9, 10)}
+
+    def check(what, n0, NA, NB, K, lda, ldb, a_ks):
+        admitted = NA % 8 == 0 and K % 64 == 0 and 2 * max((K if a_ks else NA) * lda, NB * ldb) < 0xFFF00000
+        if admitted and ops.set_option("gemm_small_launches", 0) != n0 + 1:
+            missed.append((what, NA, NB, K))
+
+    def counting_call(fn, *args):
+        n0 = ops.set_option("gemm_small_launches", 0)
+        r = real_call(fn, *args)
+        if fn in where:
+            a_ks = fn == "octmae_linear_dgrad_dgelu" or (fn == "octmae_gemm_bf16_ws" and args[13] == 1)
+            check(fn, n0, *(args[i] for i in where[fn]), a_ks)
+        return r
+
+    def counting_delta(dy, w, o, H, HD):          # dgrad + delta reaches the library without ops.call
+        n0 = ops.set_option("gemm_small_launches", 0)
+        dx, delta = real_delta(dy, w, o, H, HD)
+        if delta is not None:                     # (None: it fell back to the plain dgrad, which counting_call has checked)
+            check("octmae_linear_dgrad_delta", n0, w.shape[1], dy.shape[0], dy.shape[1], w.stride(0), dy.stride(0), True)
+        return dx, delta
+
+    try:
+        if request.param.startswith("small"):
+            ops.call, ops.linear_dgrad_delta = counting_call, counting_delta
+        yield request.param
+    finally:
+        ops.call, ops.linear_dgrad_delta = real_call, real_delta
+        ops.FORCE_SMALL_TILE = False
+        ops.FORCE_TWO_STAGE = False
+        ops.FORCE_PHASED = False
+        ops.FORCE_SMALL_LAUNCH = 0
+        ops.FORCE_SPLITK = 1
+    if request.param in ("twostage", "phased", "tile128", "never_small"):
+        assert ops.set_option("gemm_small_launches", 0) == small_before
+    assert not missed, f"{request.param}: admitted problems that did not take gemm128d_kernel: {missed}"
 
 
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
