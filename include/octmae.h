@@ -29,8 +29,10 @@ extern "C" {
  *     the stream-K and 16x16x32 variants of round 4 / 5 left the library (octmae_gemm_streamk_*, "gemm_mfma16", "gemm_streamk").
  * 12: octmae_slice_pool_fwd / _bwd / _ws_floats (the slice-pooling head of the RETFound-all model).
  * 13: octmae_gemm_plan, octmae_wgrad_pair_plan (the GEMM launch planner of csrc/gemm_plan.hpp, queried without a GPU); variant bits 9 / 10
- *     now force the 256-tile main loop they name for forward and dgrad launches too, and never the small-launch kernel. */
-#define OCTMAE_ABI_VERSION 13
+ *     now force the 256-tile main loop they name for forward and dgrad launches too, and never the small-launch kernel.
+ * 14: splitk = 0 of a weight gradient (octmae_gemm_bf16[_ws] epilogue 5, octmae_wgrad_accum_pair and the two plan queries) means
+ *     "chosen by the planner" (csrc/gemm_plan.hpp: auto_wgrad_split); until now 0 ran as 1.  No new entry points. */
+#define OCTMAE_ABI_VERSION 14
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -74,7 +76,8 @@ int octmae_set_option(const char* key, int value);
  *   4  C bf16 = X * gelu'(aux_bf16[b][a])         backward of 2 (dgrad of fc2 fused with GELU'); a non-NULL C2 is an fp32 [NA]
  *                                                 vector that receives += the column sums of C (fc1's bias gradient)
  *   5  C f32[a][b] += X  (NA rows x NB columns; split-K over `splitk` workgroup slices, fp32 atomics
- *                         when splitk > 1)        weight gradients (autograd of nn.Linear)
+ *                         when there is more than one; splitk = 0: chosen by the planner, csrc/gemm_plan.hpp:
+ *                         auto_wgrad_split)       weight gradients (autograd of nn.Linear)
  *                         a non-NULL C2 is an fp32 [NA] vector that receives += sum_k A[a][k]: with A = dY this is the
  *                         bias gradient of the same Linear, taken from the operand tiles the kernel stages anyway
  * bias may be NULL.  Requirements: lda, ldb multiples of 8; NA multiple of 4 (epilogues 0-4). */
@@ -82,7 +85,7 @@ int octmae_gemm_bf16(const void* A, const void* B, void* C, void* C2, const floa
                      int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided, int b_kstrided,
                      int epilogue, int splitk, void* stream);
 
-/* octmae_gemm_bf16 with a split-K workspace lent for this one call (also the trailing `split_ws, split_ws_bytes` of the three
+/* octmae_gemm_bf16 (splitk = 0 included) with a split-K workspace lent for this one call (also the trailing `split_ws, split_ws_bytes` of the three
  * fused entry points below; NULL / 0 = no k split).  The reference's cuBLAS / hipBLASLt picks split-K / stream-K kernels by itself
  * for such shapes (nn.Linear forward and backward: video_vit.py:114-135, timm Mlp); its shipped recipe runs ONE volume per GPU
  * (scripts/run_chunks_pretraining_vitl_oph_joint_flash_attn.sh:25-30), where a [1281 x 4096] x [4096 x 1024] Linear is 24 tiles of
@@ -113,7 +116,8 @@ int octmae_gemm_small_plan(int NA, int NB, int K, int cus, int have_ws, int big_
  *          3 gemm128d_kernel (small launch);  [1] workgroups;  [2] tiles_a  [3] tiles_b  [4] cgroup  [5] k slices  [6] k-tiles per slice
  *   [7] kstagger  [8] atomic1  [9] ring depth (small launch, else 0)  [10] the small launch's k split (else 1)
  *   [11] rows of the column-sum workspace that are folded (route 2)  [12] column-sum route: 0 none, 1 atomics inside the kernel,
- *   2 per-slab rows + a folding launch, 3 / 4 a separate octmae_colsum_accum launch before / after the GEMM. */
+ *   2 per-slab rows + a folding launch, 3 / 4 a separate octmae_colsum_accum launch before / after the GEMM.
+ * splitk as in octmae_gemm_bf16 (kinds 5 / 6: 0 = chosen by the planner, so that the answer is what a weight gradient launches). */
 int octmae_gemm_plan(int kind, int NA, int NB, int K, int lda, int ldb, int variant, int splitk, int have_ws, int cus, int* out);
 int octmae_gemm_bf16_ws(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
                         int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided, int b_kstrided,
@@ -138,7 +142,7 @@ int octmae_linear_dgrad_dgelu(const void* W, const void* dY, void* dX, const voi
  *   gW0 f32 [N0][K0] += dY0[M][N0]^T @ X0[M][K0],   gW1 f32 [N1][K1] += dY1[M][N1]^T @ X1[M][K1]      (dY, X bf16, row-major)
  *   gB0 / gB1: NULL, or f32 [N] += the column sums of dY (the bias gradient, as epilogue 5 of octmae_gemm_bf16 with C2)
  * The output tiles of both problems share one split over M: half the fp32-atomic epilogues of two separate launches and k-loops
- * twice as long.  splitk as in octmae_gemm_bf16.  Short reductions on few tiles (one or two volumes per step: M <= 96 k-tiles of 64 rows)
+ * twice as long.  splitk as in octmae_gemm_bf16 (0: chosen by the planner for the pair's tiles).  Short reductions on few tiles (one or two volumes per step: M <= 96 k-tiles of 64 rows)
  * run on 128 x 128 tiles instead when the cost model of csrc/gemm.hip prices that faster ("gemm_small"; gB is then a launch of its own).
  * Returns -2 when either problem does not take the 256-tile kernel (N or K < 256, an operand beyond a 32-bit buffer range): the
  * caller then issues two octmae_gemm_bf16 calls. */
@@ -154,7 +158,8 @@ int octmae_wgrad_split_plan(int M, int splitk, int tiles, int* slices, int* boun
 /* The launch plan of octmae_wgrad_accum_pair (csrc/gemm_plan.hpp: plan_wgrad_pair, with the 128- against 256-tile cost model), host side
  * only.  Returns 0 and writes 14 ints, or -2 as the entry point does:  out[0] kernel family (2: gemm256p_wgrad_pair_kernel,
  * 3: gemm128d_wgrad_kernel)  [1] workgroups  [2] k slices  [3] k-tiles per slice  [4] kstagger  [5] atomic1  [6] ring depth (family 3)
- * [7] bias-gradient route (1 inside the kernel, 3 a launch of its own before)  [8..10] / [11..13] tiles_a, tiles_b, cgroup of each problem. */
+ * [7] bias-gradient route (1 inside the kernel, 3 a launch of its own before)  [8..10] / [11..13] tiles_a, tiles_b, cgroup of each problem.
+ * splitk = 0: chosen by the planner, as in the entry point. */
 int octmae_wgrad_pair_plan(int N0, int K0, int ldy0, int ldx0, int N1, int K1, int ldy1, int ldx1, int M, int splitk, int cus, int* out);
 
 /* The proj dgrad of an attention block together with the attention backward's per-query constant delta (flash-attn's `dsoftmax_sum`,

@@ -2,6 +2,7 @@
 // pointers), so that every decision is written once, can be queried without a GPU (octmae_gemm_plan, octmae_wgrad_pair_plan) and is
 // tested there (tests/test_cpu_host.py).  gemm.hip checks arguments, asks plan_gemm / plan_wgrad_pair and launches what the plan names.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <cstddef>
 #include <cstdlib>
@@ -106,6 +107,25 @@ inline Split normalise_split(int ktiles, int splitk) {
   return {cdiv(ktiles, per), per};
 }
 inline bool last_slice_empty(int ktiles, int S) { return (long long)(S - 1) * cdiv(ktiles, S) >= ktiles; }
+// The k split of a weight gradient whose caller leaves it to the planner (splitk <= 0): as many k slices as keep tiles x slices within
+// ONE round of workgroups over the chip (target: 256 blocks of 256-tiles, 1024 of 128-tiles; a second, partly filled round costs more
+// than the slightly lower fill), and >= 8 k-tiles (512 token rows) per slice --
+// unless, on 256-tiles, the split costs more than it saves (round 6, small batches): every workgroup ends with 256 KiB of fp32
+// atomics, which the L2s retire at ~1.2 TB/s in all -- 0.22 us per tile and slice -- against ~1.4 us per k-tile of the main loop (fitted
+// on graph-replayed launches, tools/gemm_small_fit.py / profiles/r06_gemm_small_fit.txt).  One volume per step (21 k-tiles): the
+// fc1 + fc2 pair as 128 tiles x 2 slices was 68 us, unsplit (one atomic add per element) it is 54 us.  From 32 volumes per micro-batch
+// on the minimum is the old choice (the most slices that fit one round).  The first minimum wins.
+inline int auto_wgrad_split(int out_tiles, int ktiles, int target_blocks) {
+  int s = std::max(1, std::min(target_blocks / out_tiles, ktiles >= 8 ? ktiles / 8 : 1));
+  if (s > 1 && target_blocks == 256) {
+    double best = 1e30;
+    for (int k = 1, most = s; k <= most; ++k) {
+      const double cost = 1.4 * cdiv(ktiles, k) + 0.22 * out_tiles * k;
+      if (cost < best) { best = cost; s = k; }
+    }
+  }
+  return s;
+}
 // the k split of a FORCED small launch: 1 .. 4 as asked; less without a workspace, with an empty slice or with more partial
 // tiles than slots
 inline int clamp_forced_split(int S, int ktiles, long long nt128, bool have_ws) {
@@ -186,7 +206,7 @@ constexpr int PLAN_FALLBACK = -2;   // layout / epilogue combination not built, 
 struct GemmProblem {
   int NA, NB, K, lda, ldb;
   bool a_ks, b_ks;
-  int epi, splitk;       // Epi (EPI_DELTA included); the k split the caller asks for
+  int epi, splitk;       // Epi (EPI_DELTA included); the k split the caller asks for (weight gradients: <= 0 = auto_wgrad_split)
   bool have_c2;          // EPI_DGELU / EPI_ACCUM: column sums are wanted
   bool have_colsum_ws;   // EPI_DGELU: a per-slab workspace for them was given
 };
@@ -231,7 +251,7 @@ inline GemmPlan plan_gemm(const GemmProblem& q, const GemmVariant& v, const Gemm
     const int tile = big ? T2 : TA;
     pl.tiles_a = cdiv(q.NA, tile); pl.tiles_b = cdiv(q.NB, tile);
     pl.cgroup = big ? cgroup_for(q.epi, pl.tiles_a, pl.tiles_b, q.K, o) : pl.tiles_a;
-    const Split s = normalise_split(ktiles, wgrad ? q.splitk : 1);
+    const Split s = normalise_split(ktiles, !wgrad ? 1 : q.splitk > 0 ? q.splitk : auto_wgrad_split(pl.tiles_a * pl.tiles_b, ktiles, big ? 256 : 1024));
     pl.slices = s.slices; pl.ktiles_per_split = s.per;
     pl.kstagger = (big && wgrad) ? wgrad_stagger_for(ktiles, s.slices, pl.tiles_a * pl.tiles_b, o.wgrad_stagger) : 0;
     pl.atomic1 = (pl.kernel == GemmKernel::Phased256 && wgrad) ? o.wgrad_s1_atomic : 0;
@@ -262,8 +282,8 @@ inline PairPlan plan_wgrad_pair(const int N[2], const int K[2], const int ldy[2]
   for (int i = 0; i < 2; ++i)
     if (!fits_256(N[i], K[i], M, ldy[i], ldx[i], true, true)) { pl.status = PLAN_FALLBACK; return pl; }
   const int ktiles = cdiv(M, TK);
-  const Split s = normalise_split(ktiles, splitk);
   const int nt256 = cdiv(N[0], T2) * cdiv(K[0], T2) + cdiv(N[1], T2) * cdiv(K[1], T2);
+  const Split s = normalise_split(ktiles, splitk > 0 ? splitk : auto_wgrad_split(nt256, ktiles, 256));   // splitk <= 0: the planner's own
   const long long nt128 = (long long)cdiv(N[0], T1) * cdiv(K[0], T1) + (long long)cdiv(N[1], T1) * cdiv(K[1], T1);
   pl.atomic1 = o.wgrad_s1_atomic;
   pl.colsum = Colsum::Fused;

@@ -126,18 +126,19 @@ class KernelTimer:
 
     def launch(self, kind, flops, nbytes, fn, exec_flops=None):
         """flops: ALGORITHMIC (SURVEY 8d: attention forward 4 B H N^2 hd, backward 8 B H N^2 hd = x3 in total);
-        exec_flops: what the kernel executes (recomputed products included), defaults to flops."""
+        exec_flops: what the kernel executes (recomputed products included), defaults to flops.
+        fn returning False: nothing was launched (the library's -2; the caller goes another way), so nothing is counted."""
         st = self.stats.setdefault(kind, [0, 0.0, 0.0, 0.0])
         sampled = st[0] % self.stride == 0
-        st[0] += 1; st[1] += flops; st[2] += nbytes; st[3] += flops if exec_flops is None else exec_flops
-        if not sampled:
-            fn()
+        if sampled:
+            s = torch.cuda.Event(enable_timing=True); e = torch.cuda.Event(enable_timing=True)
+            s.record()
+        if fn() is False:
             return
-        s = torch.cuda.Event(enable_timing=True); e = torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        self.records.setdefault(kind, []).append((s, e))
+        st[0] += 1; st[1] += flops; st[2] += nbytes; st[3] += flops if exec_flops is None else exec_flops
+        if sampled:
+            e.record()
+            self.records.setdefault(kind, []).append((s, e))
 
     def summary(self):
         torch.cuda.synchronize()
@@ -238,7 +239,7 @@ def _split_ws_for(st: int):
     return ws.data_ptr(), ws.numel()
 
 
-def _gemm(A, B, C, NA, NB, K, lda, ldb, ldc, a_ks, b_ks, epi, C2=None, bias=None, aux=None, ldaux=0, splitk=1):
+def _gemm(A, B, C, NA, NB, K, lda, ldb, ldc, a_ks, b_ks, epi, C2=None, bias=None, aux=None, ldaux=0, splitk=0):
     st = _stream()
     if (epi & 0xff) != EPI_ACCUM and not FORCE_SMALL_TILE:   # forward / dgrad kinds: lend the split-K workspace
         skp, skn = _split_ws_for(st)
@@ -351,6 +352,7 @@ def linear_dgrad_delta(dy: torch.Tensor, w: torch.Tensor, o: torch.Tensor, H: in
 
     def run():
         rc[0] = load().octmae_linear_dgrad_delta(*args)
+        return rc[0] != -2
 
     _launch("gemm_dgrad_epi6", 2.0 * K * M * N, 2.0 * (K * N + M * N) + 2.0 * K * M + 2.0 * K * M, run)
     if rc[0] == -2:           # the library's own applicability test (plan_gemm, EPI_DELTA) said no (e.g. an operand beyond a 32-bit buffer range): plain dgrad
@@ -360,35 +362,13 @@ def linear_dgrad_delta(dy: torch.Tensor, w: torch.Tensor, o: torch.Tensor, H: in
     return dx, delta
 
 
-def _splitk_for(n_out_tiles: int, ktiles: int, target_blocks: int) -> int:
-    # as many k-slices as keep tiles x slices within ONE round of workgroups over the chip (a second, partly filled
-    # round costs more than the slightly lower fill), and >= 8 k-tiles (512 token rows) per slice
-    s = max(1, target_blocks // n_out_tiles)
-    s = max(1, min(s, ktiles // 8 if ktiles >= 8 else 1))
-    if s > 1 and target_blocks == 256:
-        # ... unless the split costs more than it saves (round 6, small batches): every workgroup ends with 256 KiB of fp32 atomics,
-        # which the L2s retire at ~1.2 TB/s in all -- 0.22 us per tile and slice -- against ~1.4 us per k-tile of the main loop
-        # (fitted on graph-replayed launches, tools/gemm_small_fit.py / profiles/r06_gemm_small_fit.txt).  One volume per step
-        # (21 k-tiles): the fc1 + fc2 pair as 128 tiles x 2 slices was 68 us, unsplit (one atomic add per element) it is 54 us.
-        # From 32 volumes per micro-batch on the minimum is the old choice (the most slices that fit one round).
-        def cost(k):
-            return 1.4 * -(-ktiles // k) + 0.22 * n_out_tiles * k
-        s = min(range(1, s + 1), key=cost)
-    return s
-
-
 def linear_wgrad_accum(dy: torch.Tensor, x: torch.Tensor, gw: torch.Tensor, gb: Optional[torch.Tensor] = None):
     """gw[N,K] (f32) += dy[M,N].T @ x[M,K]; with ``gb`` (f32 [N]) also gb += dy.sum(0) -- the bias gradient, taken from the
     dY tiles the weight-gradient kernel stages anyway (one extra MFMA per k-step in the first column of tiles) instead of a
     separate pass over dY."""
     M, N = dy.shape
     K = x.shape[1]
-    big = N >= 256 and K >= 256 and not FORCE_SMALL_TILE          # mirrors fits_256 / plan_gemm (csrc/gemm_plan.hpp)
-    t = 256 if big else 128
-    tiles = ((N + t - 1) // t) * ((K + t - 1) // t)
-    ktiles = (M + 63) // 64
-    _gemm(dy, x, gw, N, K, M, dy.stride(0), x.stride(0), gw.stride(0), 1, 1, EPI_ACCUM, C2=gb,
-          splitk=_splitk_for(tiles, ktiles, 256 if big else 1024))
+    _gemm(dy, x, gw, N, K, M, dy.stride(0), x.stride(0), gw.stride(0), 1, 1, EPI_ACCUM, C2=gb)    # k split: the planner's (auto_wgrad_split)
 
 
 # fc1 + fc2 and qkv + proj weight gradients of a Block as one launch each (octmae_wgrad_accum_pair); OCTMAE_WGRAD_PAIR=0: same-box A/B
@@ -402,12 +382,8 @@ def linear_wgrad_accum_pair(first, second):
     the library says the pair does not apply (-2) or WGRAD_PAIR is off."""
     (dy0, x0, gw0, gb0), (dy1, x1, gw1, gb1) = first, second
     M = dy0.shape[0]
-    ok = (WGRAD_PAIR and not FORCE_SMALL_TILE and dy1.shape[0] == M and x0.shape[0] == M and x1.shape[0] == M
-          and min(dy0.shape[1], x0.shape[1], dy1.shape[1], x1.shape[1]) >= 256
-          # the library's own applicability test (plan_wgrad_pair: fits_256, each operand inside one 32-bit buffer descriptor), so that -2 is not met here
-          and 2 * M * max(dy0.stride(0), x0.stride(0), dy1.stride(0), x1.stride(0)) < 0xFFF00000)
-    if ok:
-        tiles = sum(((dy.shape[1] + 255) // 256) * ((x.shape[1] + 255) // 256) for dy, x in ((dy0, x0), (dy1, x1)))
+    # the pair entry point has no variant argument, hence the switch tests; whether the shapes take it is the library's answer (-2)
+    if WGRAD_PAIR and not FORCE_SMALL_TILE and dy1.shape[0] == M and x0.shape[0] == M and x1.shape[0] == M:
         rc = [0]
         args = []
         for dy, x, gw, gb in (first, second):
@@ -415,10 +391,11 @@ def linear_wgrad_accum_pair(first, second):
                 if not (t_.is_cuda and t_.dtype == dt_ and t_.dim() == 2 and t_.stride(1) == 1):
                     raise RuntimeError(f"linear_wgrad_accum_pair: {nm_} must be a GPU {dt_} matrix with contiguous rows")
             args += [dy.data_ptr(), x.data_ptr(), gw.data_ptr(), _p(gb), dy.shape[1], x.shape[1], dy.stride(0), x.stride(0), gw.stride(0)]
-        args += [M, _splitk_for(tiles, (M + 63) // 64, 256), _stream()]
+        args += [M, 0, _stream()]                        # k split 0: the planner's (auto_wgrad_split)
 
         def run():
             rc[0] = load().octmae_wgrad_accum_pair(*args)
+            return rc[0] != -2
 
         fl = 2.0 * M * (dy0.shape[1] * x0.shape[1] + dy1.shape[1] * x1.shape[1])
         nb = 2.0 * M * (dy0.shape[1] + x0.shape[1] + dy1.shape[1] + x1.shape[1]) + 4.0 * (gw0.numel() + gw1.numel())

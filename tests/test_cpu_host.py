@@ -405,29 +405,6 @@ def test_small_launch_plan():
         lib.octmae_set_option(b"gemm_small", prev)
 
 
-def test_weight_gradient_split_rule():
-    """ops._splitk_for (host arithmetic): as many k slices as keep tiles x slices within one round of 256 workgroups with >= 8 k-tiles
-    each -- unless the fp32-atomic epilogues of the slices (0.22 us per tile and slice) cost more than the main-loop time they save
-    (1.4 us per k-tile): one or two volumes per step stay unsplit where round 5 split two ways; from 8 volumes on nothing changes
-    (the headline's choices are those of rounds 2-5)."""
-    from octcubem_amd import ops
-    enc_fc, enc_qkv, dec_fc, dec_qkv = 128, 64, 32, 16          # 256 x 256 output tiles of the four weight-gradient pairs of ViT-L
-    kt = lambda rows: (rows + 63) // 64
-    for vols in (8, 16, 32, 64, 128):                           # unchanged from the old rule
-        assert ops._splitk_for(enc_fc, kt(vols * 1281), 256) == 2
-        assert ops._splitk_for(enc_qkv, kt(vols * 1281), 256) == 4
-        assert ops._splitk_for(dec_fc, kt(vols * 5121), 256) == 8
-        assert ops._splitk_for(dec_qkv, kt(vols * 5121), 256) in (15, 16)
-    assert ops._splitk_for(enc_fc, kt(1281), 256) == 1 and ops._splitk_for(enc_qkv, kt(1281), 256) == 1       # one volume: no atomics
-    assert ops._splitk_for(enc_fc, kt(2 * 1281), 256) == 1 and ops._splitk_for(enc_qkv, kt(2 * 1281), 256) == 2
-    assert 3 <= ops._splitk_for(dec_fc, kt(5121), 256) <= 5 and 5 <= ops._splitk_for(dec_qkv, kt(5121), 256) <= 7
-    for tiles in (1, 7, 16, 64, 128, 300):                      # always a legal split
-        for ktiles in (1, 5, 8, 21, 81, 2562):
-            s_ = ops._splitk_for(tiles, ktiles, 256)
-            assert 1 <= s_ <= max(1, 256 // tiles) and (s_ == 1 or ktiles // s_ >= 8)
-            assert ops._splitk_for(tiles, ktiles, 1024) >= 1   # the 128-tile register-staged kernel's target: the old rule
-
-
 def test_bench_parity_compliant_child_failure_is_recorded_not_raised():
     """bench.py's `parity_compliant` record comes from a child process on the half-operand build; whatever goes wrong there (here: no GPU
     in this container, so the child exits with an error) must end up IN the record -- the headline run goes on."""
@@ -485,6 +462,106 @@ def _gemm_plan(lib, kind, NA, NB, K, lda=None, ldb=None, variant=0, splitk=1, ws
 
 def _fits_256(NA, NB, K, kind):
     return NA >= 256 and NB >= 256 and (kind in (PLAN_WGRAD, PLAN_WGRAD_BIAS) or K % 64 == 0)
+
+
+PAIR_FIELDS = ("kernel", "grid", "slices", "per", "kstagger", "atomic1", "nst", "colsum", "tiles_a0", "tiles_b0", "cgroup0", "tiles_a1", "tiles_b1", "cgroup1")
+# (N0, K0, N1, K1) of the four weight-gradient pairs of a ViT-L Block: encoder fc2 + fc1 (128 output tiles of 256 x 256) and proj + qkv (64),
+# decoder fc2 + fc1 (32) and proj + qkv (16)
+ENC_FC, ENC_QKV, DEC_FC, DEC_QKV = (1024, 4096, 4096, 1024), (1024, 1024, 3072, 1024), (512, 2048, 2048, 512), (512, 512, 1536, 512)
+
+
+def _pair_plan(lib, pair, M, splitk=0, cus=256):
+    """(rc, fields) of octmae_wgrad_pair_plan for packed operands"""
+    N0, K0, N1, K1 = pair
+    out = (ctypes.c_int * 14)()
+    rc = lib.octmae_wgrad_pair_plan(N0, K0, N0, K0, N1, K1, N1, K1, M, splitk, cus, out)
+    return rc, dict(zip(PAIR_FIELDS, out))
+
+
+def _splitk_for(n_out_tiles: int, ktiles: int, target_blocks: int) -> int:
+    """The rule as octcubem_amd/ops.py held it before the planner took it over (auto_wgrad_split in csrc/gemm_plan.hpp), verbatim: the
+    reference of test_auto_weight_gradient_split_is_the_rule_ops_had."""
+    # as many k-slices as keep tiles x slices within ONE round of workgroups over the chip (a second, partly filled
+    # round costs more than the slightly lower fill), and >= 8 k-tiles (512 token rows) per slice
+    s = max(1, target_blocks // n_out_tiles)
+    s = max(1, min(s, ktiles // 8 if ktiles >= 8 else 1))
+    if s > 1 and target_blocks == 256:
+        def cost(k):
+            return 1.4 * -(-ktiles // k) + 0.22 * n_out_tiles * k
+        s = min(range(1, s + 1), key=cost)
+    return s
+
+
+def test_weight_gradient_split_rule():
+    """The planner's own k split of a weight gradient (splitk = 0; auto_wgrad_split, host arithmetic): as many k slices as keep tiles x
+    slices within one round of 256 workgroups with >= 8 k-tiles each -- unless the fp32-atomic epilogues of the slices (0.22 us per tile
+    and slice) cost more than the main-loop time they save (1.4 us per k-tile): one or two volumes per step stay unsplit where round 5
+    split two ways; from 8 volumes on nothing changes (the headline's choices are those of rounds 2-5).  Read off the plans on 256 CUs:
+    the four pairs of a Block through octmae_wgrad_pair_plan, single launches through octmae_gemm_plan."""
+    import json
+    pins = {r[0]: r for r in json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_plan_pins.json")))["pair"]}
+    for lib in _both_libraries():
+        slices = lambda pair, rows: _pair_plan(lib, pair, rows)[1]["slices"]     # noqa: E731
+        for small in (1, 0):                                    # 0: the 256-tile pair is the kernel at every size
+            prev = lib.octmae_set_option(b"gemm_small", small)
+            try:
+                for vols in (8, 16, 32, 64, 128):               # unchanged from the old rule
+                    assert all(_pair_plan(lib, pr, vols * rows)[1]["kernel"] == PHASED256
+                               for pr, rows in ((ENC_FC, 1281), (ENC_QKV, 1281), (DEC_FC, 5121), (DEC_QKV, 5121)))
+                    assert slices(ENC_FC, vols * 1281) == 2
+                    assert slices(ENC_QKV, vols * 1281) == 4
+                    assert slices(DEC_FC, vols * 5121) == 8
+                    assert slices(DEC_QKV, vols * 5121) in (15, 16)
+                if small:                                       # one volume: the 128-tile pair, with the slices the pins saw it launch
+                    for name, pr, rows in (("B1_enc_fc2+fc1", ENC_FC, 1281), ("B1_enc_proj+qkv", ENC_QKV, 1281), ("B1_dec_fc2+fc1", DEC_FC, 5121),
+                                           ("B1_dec_proj+qkv", DEC_QKV, 5121)):
+                        rc, p = _pair_plan(lib, pr, rows)
+                        assert (rc, p["kernel"], p["grid"], p["slices"], p["nst"]) == (0, *pins[name][7:11]) and p["kernel"] == SMALL128D, name
+                    continue
+                assert _pair_plan(lib, ENC_FC, 1281)[1]["kernel"] == PHASED256
+                assert slices(ENC_FC, 1281) == 1 and slices(ENC_QKV, 1281) == 1                   # one volume: no atomics
+                assert slices(ENC_FC, 2 * 1281) == 1 and slices(ENC_QKV, 2 * 1281) == 2
+                assert 3 <= slices(DEC_FC, 5121) <= 5 and 5 <= slices(DEC_QKV, 5121) <= 7
+            finally:
+                lib.octmae_set_option(b"gemm_small", prev)
+        for N, K in ((256, 256), (256, 1792), (1024, 1024), (2048, 2048), (2048, 4096), (3840, 5120)):     # 1, 7, 16, 64, 128, 300 tiles: always a legal split
+            tiles = (N // 256) * (K // 256)
+            for ktiles in (1, 5, 8, 21, 81, 2562):
+                rc, p = _gemm_plan(lib, PLAN_WGRAD, N, K, 64 * ktiles, variant=0x4000, splitk=0)
+                s_ = p["slices"]
+                assert rc == 0 and p["kernel"] == PHASED256 and p["grid"] == tiles * s_
+                assert 1 <= s_ <= max(1, 256 // tiles) and (s_ == 1 or ktiles // s_ >= 8)
+        for ktiles in (1, 5, 8, 21, 81, 2562):                  # the 128-tile register-staged kernel's target (1024 blocks): the old rule
+            rc, p = _gemm_plan(lib, PLAN_WGRAD, 128, 384, 64 * ktiles, variant=0x4000, splitk=0)
+            assert rc == 0 and p["kernel"] == TILE128 and p["grid"] == 3 * p["slices"]
+            assert 1 <= p["slices"] <= max(1, ktiles // 8) and (p["slices"] > 1) == (ktiles >= 16)
+
+
+def test_auto_weight_gradient_split_is_the_rule_ops_had():
+    """splitk = 0 (the planner chooses: auto_wgrad_split) gives, field for field, the plan of the split that ops._splitk_for chose
+    before the rule moved into the planner -- for single weight gradients over a grid of shapes and kernel variants and for the
+    pinned pairs on three CU counts.  ops.py took a problem for 256-tiled from N, K >= 256 alone; the planner also asks that each
+    operand lies inside a 32-bit buffer range (fits_256) and computes the split for the tiles it launches: for the 4096-wide operands
+    at 128 x 5121 rows, the one place of this grid where the two differ, the reference is given the 128-tiles the library runs."""
+    import json
+    kt = lambda rows: (rows + 63) // 64     # noqa: E731
+    for lib in _both_libraries():
+        for N in (128, 136, 256, 384, 512, 1024, 1536, 3072, 4096):
+            for K in (128, 136, 256, 384, 512, 1024, 1536, 3072, 4096):
+                for M in (64, 500, 1281, 2 * 1281, 5121, 4 * 1281, 32 * 1281, 32 * 5121, 128 * 5121):
+                    for variant in (0, 0x100, 0x4000):
+                        in_range = 2 * M * max(N, K) < 0xFFF00000           # packed operands: M rows of N and of K 16-bit elements
+                        assert in_range or (M == 128 * 5121 and 4096 in (N, K))     # 5.4 GB: the only operands of this grid beyond the range
+                        big = N >= 256 and K >= 256 and not variant & 0x100 and in_range
+                        t = 256 if big else 128
+                        ref = _splitk_for(-(-N // t) * -(-K // t), kt(M), 256 if big else 1024)
+                        auto, asked = (_gemm_plan(lib, PLAN_WGRAD_BIAS, N, K, M, variant=variant, splitk=s_) for s_ in (0, ref))
+                        assert auto == asked and auto[0] == 0, (N, K, M, variant, ref, auto, asked)
+        for name, N0, K0, N1, K1, M, *_ in json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_plan_pins.json")))["pair"]:
+            ref = _splitk_for(-(-N0 // 256) * -(-K0 // 256) + -(-N1 // 256) * -(-K1 // 256), kt(M), 256)
+            for cus in (64, 256, 304):
+                auto, asked = (_pair_plan(lib, (N0, K0, N1, K1), M, splitk=s_, cus=cus) for s_ in (0, ref))
+                assert auto == asked and auto[0] == 0, (name, cus, ref, auto, asked)
 
 
 def test_gemm_plan_variant_bits_mean_what_they_say():
@@ -571,9 +648,11 @@ def test_gemm_plans_of_the_model_shapes_are_those_the_previous_dispatch_launched
     assert len(pins["gemm"]) >= 340 and len(pins["pair"]) == 16
     for lib in _both_libraries():
         for name, kind, NA, NB, K, splitk, ws, family, grid, cgroup, slices, nst in pins["gemm"]:
-            rc, p = _gemm_plan(lib, kind, NA, NB, K, splitk=splitk, ws=ws)
-            assert (rc, p["kernel"], p["grid"], p["cgroup"], p["slices"], p["nst"]) == (0, family, grid, cgroup, slices, nst), (name, ws, p)
+            for s_ in (splitk, 0) if kind in (PLAN_WGRAD, PLAN_WGRAD_BIAS) else (splitk,):     # 0: the planner's own split must be that commit's
+                rc, p = _gemm_plan(lib, kind, NA, NB, K, splitk=s_, ws=ws)
+                assert (rc, p["kernel"], p["grid"], p["cgroup"], p["slices"], p["nst"]) == (0, family, grid, cgroup, slices, nst), (name, ws, s_, p)
         out = (ctypes.c_int * 14)()
         for name, N0, K0, N1, K1, M, splitk, family, grid, slices, nst, cgroup0, cgroup1 in pins["pair"]:
-            rc = lib.octmae_wgrad_pair_plan(N0, K0, N0, K0, N1, K1, N1, K1, M, splitk, 256, out)
-            assert (rc, out[0], out[1], out[2], out[6], out[10], out[13]) == (0, family, grid, slices, nst, cgroup0, cgroup1), (name, list(out))
+            for s_ in (splitk, 0):                                                             # 0: as above
+                rc = lib.octmae_wgrad_pair_plan(N0, K0, N0, K0, N1, K1, N1, K1, M, s_, 256, out)
+                assert (rc, out[0], out[1], out[2], out[6], out[10], out[13]) == (0, family, grid, slices, nst, cgroup0, cgroup1), (name, s_, list(out))

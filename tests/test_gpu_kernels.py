@@ -319,6 +319,66 @@ def test_wgrad_staggered_split_k_slices(N, K, M, splitk, v):
         ops.set_option("wgrad_stagger", prev)
 
 
+def _auto_wgrad_slices(N, K, M):
+    """k slices of the plan of ops.linear_wgrad_accum(dy [M, N], x [M, K], gw, gb) with the split left to the planner (splitk = 0)"""
+    import ctypes
+    from octcubem_amd._lib import load
+    out = (ctypes.c_int * 13)()
+    assert load().octmae_gemm_plan(6, N, K, M, N, K, ops._variant_bits(), 0, 0, 256, out) == 0     # kind 6: wgrad + bias gradient
+    return out[5]
+
+
+@pytest.mark.parametrize("N,K,M,slices", [(256, 256, 64 * 16 + 17, 2),      # one 256-tile: the smallest problem the planner splits
+                                          (128, 384, 64 * 40 + 5, 5),       # the 128-tile register-staged kernel (target: 1024 workgroups)
+                                          (512, 256, 100, 1)])              # two k-tiles: unsplit
+def test_wgrad_split_chosen_by_the_planner(N, K, M, slices):
+    """ops.linear_wgrad_accum leaves the k split to the library (splitk = 0: auto_wgrad_split in csrc/gemm_plan.hpp): the launch is the
+    one octmae_gemm_plan reports for splitk = 0, i.e. the same as asking for that many slices -- bit for bit where that is one slice
+    (no atomics), otherwise both inside the bound of test_wgrad_staggered_split_k_slices against its fp64 reference."""
+    assert _auto_wgrad_slices(N, K, M) == slices
+    g = torch.Generator().manual_seed(N + K + M)
+    x = bf(torch.randn(M, K, generator=g)).to(DEV)
+    dy = bf(torch.randn(M, N, generator=g)).to(DEV)
+    gw0 = torch.randn(N, K, generator=g).to(DEV)
+    gb0 = torch.randn(N, generator=g).to(DEV)
+    ref, ref_b = gw0.double() + dy.double().t() @ x.double(), gb0.double() + dy.double().sum(0)
+    gw_a, gb_a, gw_s, gb_s = gw0.clone(), gb0.clone(), gw0.clone(), gb0.clone()
+    ops.linear_wgrad_accum(dy, x, gw_a, gb_a)
+    ops._gemm(dy, x, gw_s, N, K, M, N, K, K, 1, 1, ops.EPI_ACCUM, C2=gb_s, splitk=slices)
+    if slices == 1:
+        assert torch.equal(gw_a, gw_s) and torch.equal(gb_a, gb_s)
+    for gw, gb in ((gw_a, gb_a), (gw_s, gb_s)):
+        assert rel(gw, ref) < 1e-5
+        assert rel(gb, ref_b) < 2e-5
+
+
+def test_wgrad_pair_the_library_declines_runs_as_two_launches():
+    """A pair whose second problem has N = 128 does not take the 256-tile kernel: octmae_wgrad_accum_pair answers -2 and writes nothing
+    (ops.py no longer screens shapes itself), and ops.linear_wgrad_accum_pair runs the two single launches -- unsplit here, so bit for
+    bit -- without the 128-tile pair kernel; under ops.KTIMER the declined call leaves no sample."""
+    M, shapes = 100, ((512, 256), (128, 384))
+    g = torch.Generator().manual_seed(M)
+    probs = []
+    for N, K in shapes:
+        assert _auto_wgrad_slices(N, K, M) == 1
+        dy = bf(torch.randn(M, N, generator=g)).to(DEV); x = bf(torch.randn(M, K, generator=g)).to(DEV)
+        probs.append((dy, x, torch.randn(N, K, generator=g).to(DEV), torch.randn(N, generator=g).to(DEV)))
+    single = [(gw.clone(), gb.clone()) for _, _, gw, gb in probs]
+    assert _pair_call(probs, M, 0) == -2
+    assert all(torch.equal(gw, gw1) and torch.equal(gb, gb1) for (_, _, gw, gb), (gw1, gb1) in zip(probs, single))
+    for (dy, x, _, _), (gw1, gb1) in zip(probs, single):
+        ops.linear_wgrad_accum(dy, x, gw1, gb1)
+    n0 = ops.set_option("gemm_small_wgrad_launches", 0)
+    ops.KTIMER = ops.KernelTimer(stride=1)
+    try:
+        ops.linear_wgrad_accum_pair(probs[0], probs[1])
+        assert ops.KTIMER.stats["gemm_wgrad_epi5"][0] == 2 and len(ops.KTIMER.records["gemm_wgrad_epi5"]) == 2
+    finally:
+        ops.KTIMER = None
+    assert ops.set_option("gemm_small_wgrad_launches", 0) == n0
+    assert all(torch.equal(gw, gw1) and torch.equal(gb, gb1) for (_, _, gw, gb), (gw1, gb1) in zip(probs, single))
+
+
 @pytest.mark.parametrize("M,first,second", [(64 * 37 + 5, (1024, 256), (256, 1024)),      # fc2 / fc1 of a Block (C = 256)
                                             (64 * 60, (512, 512), (1536, 512)),           # proj / qkv with the qkv bias gradient
                                             (64 * 200 + 63, (2048, 512), (512, 2048)),    # 32 tiles, split 8

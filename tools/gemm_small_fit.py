@@ -5,7 +5,7 @@
    d4sS  gemm128d_kernel, 4-stage ring (one workgroup per CU), S-way k split
    d2sS  gemm128d_kernel, 2-stage ring (two workgroups per CU)
    auto  what the library picks by itself
-and the weight-gradient pairs with the split rule of ops._splitk_for against the pre-round-6 one.
+and the weight-gradient pairs with the planner's split rule (csrc/gemm_plan.hpp: auto_wgrad_split) against every forced split.
 
     python tools/gemm_small_fit.py [volumes ...]          (default 1 2 4 8)"""
 import os
@@ -87,7 +87,7 @@ def main():
     print("sum over the blocks of one step (us)".ljust(46) + "".join(f"{tot[n]:8.0f}" for n, _, _ in variants))
 
     # weight-gradient pairs: the split rule
-    print("\nweight-gradient pairs (us): the library's choice; the 256-tile pair kernel with the split ops._splitk_for chooses, unsplit with "
+    print("\nweight-gradient pairs (us): the library's choice; the 256-tile pair kernel with the split the planner chooses, unsplit with "
           "each of its three epilogues, and with every split 1 .. 8 forced")
     for B in vols:
         for name, M, D in (("enc", B * 1281, 1024), ("dec", B * 5121, 512)):
@@ -96,23 +96,27 @@ def main():
             gwp = torch.zeros(D, D, device=DEV); gwq = torch.zeros(3 * D, D, device=DEV); gbq = torch.zeros(3 * D, device=DEV)
             for pname, first, second in (("fc2+fc1", (y1, act, gw2, None), (dpre, y1, gw1, None)), ("proj+qkv", (y1, o, gwp, None), (dqkv, y1, gwq, gbq))):
                 tiles = sum(((dy.shape[1] + 255) // 256) * ((xx.shape[1] + 255) // 256) for dy, xx, _, _ in (first, second))
-                chosen = ops._splitk_for(tiles, (M + 63) // 64, 256)
-                orig = ops._splitk_for
-                t_auto = timeit(lambda: ops.linear_wgrad_accum_pair(first, second))          # the library's choice (may be the 128-tile pair kernel)
+                args = []
+                for dy, xx, gw, gb in (first, second):
+                    args += [dy.data_ptr(), xx.data_ptr(), gw.data_ptr(), ops._p(gb), dy.shape[1], xx.shape[1], dy.stride(0), xx.stride(0), gw.stride(0)]
+
+                def pair(S):          # the entry point itself: S = 0 the planner's split, S >= 1 that split
+                    assert lib.octmae_wgrad_accum_pair(*args, M, S, torch.cuda.current_stream().cuda_stream) == 0
+
+                t_auto = timeit(lambda: pair(0))                                                # the library's choice (may be the 128-tile pair kernel)
                 prev_small = ops.set_option("gemm_small", 0)                                    # everything below: the 256-tile pair kernel
-                t_rule256 = timeit(lambda: ops.linear_wgrad_accum_pair(first, second))
-                ops._splitk_for = lambda a, b_, c: 1
+                plan = (ctypes.c_int * 14)()
+                assert lib.octmae_wgrad_pair_plan(*(a for d_, x_, _, _ in (first, second) for a in (d_.shape[1], x_.shape[1], d_.stride(0), x_.stride(0))),
+                                                  M, 0, ncu, plan) == 0
+                chosen = plan[2]
+                t_rule256 = timeit(lambda: pair(0))
                 t_s1 = []
                 prev_opt = ops.set_option("wgrad_s1_atomic", 0)
                 for form in (0, 1, 2):          # guarded read-modify-write / atomics / batched buffer read-modify-write
                     ops.set_option("wgrad_s1_atomic", form)
-                    t_s1.append(timeit(lambda: ops.linear_wgrad_accum_pair(first, second)))
+                    t_s1.append(timeit(lambda: pair(1)))
                 ops.set_option("wgrad_s1_atomic", prev_opt)
-                row = []
-                for S in range(1, 9):
-                    ops._splitk_for = lambda a, b_, c, S=S: S
-                    row.append(timeit(lambda: ops.linear_wgrad_accum_pair(first, second)))
-                ops._splitk_for = orig
+                row = [timeit(lambda S=S: pair(S)) for S in range(1, 9)]
                 ops.set_option("gemm_small", prev_small)
                 print(f"B={B} {name} {pname:9s} tiles {tiles:4d} ktiles {(M + 63) // 64:5d}  library: {t_auto:7.1f}  256-tile pair, rule S={chosen}: {t_rule256:7.1f}  S=1 rmw/atomic/batched: " + "/".join(f"{t:.1f}" for t in t_s1) + "   forced: " +
                       " ".join(f"{t:7.1f}" for t in row), flush=True)
