@@ -31,8 +31,9 @@ extern "C" {
  * 13: octmae_gemm_plan, octmae_wgrad_pair_plan (the GEMM launch planner of csrc/gemm_plan.hpp, queried without a GPU); variant bits 9 / 10
  *     now force the 256-tile main loop they name for forward and dgrad launches too, and never the small-launch kernel.
  * 14: splitk = 0 of a weight gradient (octmae_gemm_bf16[_ws] epilogue 5, octmae_wgrad_accum_pair and the two plan queries) means
- *     "chosen by the planner" (csrc/gemm_plan.hpp: auto_wgrad_split); until now 0 ran as 1.  No new entry points. */
-#define OCTMAE_ABI_VERSION 14
+ *     "chosen by the planner" (csrc/gemm_plan.hpp: auto_wgrad_split); until now 0 ran as 1.  No new entry points.
+ * 15: octmae_volume_box, octmae_volume_resample (the volume transforms in front of the models, csrc/transform3d.hip). */
+#define OCTMAE_ABI_VERSION 15
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -211,6 +212,25 @@ int octmae_slice_pool_fwd(const float* x, const float* gamma, const float* beta,
 int octmae_slice_pool_bwd(const float* dout, const float* pooled, const float* mean, const float* rstd, const float* gamma,
                           float* dx, void* dx_bf16, float* dgamma, float* dbeta, float* dxsum, float* ws, int B, int S, int T,
                           int D, int cls, void* stream);
+
+/* ---- volume transforms ------------------------------------------------------------------------------
+ * The MONAI pipeline of Pre-training/custom_util/PatientDataset_inhouse.py:48-84 (create_3d_transforms; inference_utils.py:10 imports
+ * it) over one raw scan: vol is one contiguous [D][H][W] device volume, dtype 0 = uint8, 1 = float32.  Both entry points are the
+ * same code in the two builds of the library (no 16-bit operands).  -1: a non-positive size or a NULL vol / box6 / out; -2: another dtype.
+ *   octmae_volume_box       CropForegroundd (select_fn = x > 0, margin 0): box6 = int32 {d0, d1, h0, h1, w0, w1} in DEVICE memory,
+ *                           half-open, the bounding box of the voxels > 0 (negative values and NaN are background).  box6 is
+ *                           initialised here; integer atomic min / max only, so the result does not depend on the order.  A volume
+ *                           without a voxel > 0 gives the full extent {0, D, 0, H, 0, W} (MONAI would fail on the empty crop).
+ *   octmae_volume_resample  out f32 [T][OH][OW] = Resized(mode="trilinear") = F.interpolate(align_corners=False) of the volume, or of
+ *                           the sub-volume box6 names when box6 != NULL (read on the device: nothing returns to the host between the
+ *                           two entry points; the six values are clamped into the volume).  Per axis scale = float(in) / float(out),
+ *                           src = max(fma(scale, dst + 0.5f, -0.5f), 0) (one rounding, as ATen's CPU kernel computes it), taps
+ *                           min(floor(src), in - 1) and the next one (clamped), weight src - floor.  flip_d / flip_w reverse the
+ *                           output's first / last axis (RandFlipd spatial_axis 0 / 2, after the resize); normalize != 0 applies
+ *                           NormalizeIntensityd(subtrahend, divisor, nonzero=True): y = (y - subtrahend) / divisor where y != 0. */
+int octmae_volume_box(const void* vol, int dtype, int D, int H, int W, int* box6, void* stream);
+int octmae_volume_resample(const void* vol, int dtype, int D, int H, int W, const int* box6, float* out, int T, int OH, int OW,
+                           int flip_d, int flip_w, int normalize, float subtrahend, float divisor, void* stream);
 
 /* ---- attention -----------------------------------------------------------------------------------
  * softmax(q k^T * scale) v, non-causal, no dropout: video_vit.py:130-134 (flash path: flash_attn MHA,

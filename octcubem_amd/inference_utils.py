@@ -1,7 +1,7 @@
 """Model-side inference helpers: the drop-in counterpart of the reference's ``inference_utils.py`` (repository root), for the part
 that touches the hot path -- build the spatio-temporal ViT from the same ``args``, load a fine-tuned checkpoint into it with both
-positional tables interpolated, and format the per-disease probabilities.  (The DICOM reading and the MONAI transform pipeline of
-that file, ``create_3d_transforms``, are data loading: SURVEY section 2.1 OUT.)
+positional tables interpolated, and format the per-disease probabilities.  (The DICOM reading of that file is data loading: SURVEY
+section 2.1 OUT; the transform pipeline it imports, ``create_3d_transforms``, is octcubem_amd.transforms.)
 
   create_models(args)        inference_utils.py:43-60   -- ``args.model_type == '3D_st_flash_attn'``, ``args.model`` names a factory of
                              models_vit_st; the reference passes ``use_flash_attention=True``, a keyword its VisionTransformer does

@@ -467,6 +467,51 @@ def slice_pool_bwd(dout, pooled, mean, rstd, gamma, T: int, S: int, cls: bool, d
     return dx, dxb
 
 
+_VOL_DTYPES = {torch.uint8: 0, torch.float32: 1}
+
+
+def volume_box(vol: torch.Tensor) -> torch.Tensor:
+    """The bounding box of the voxels > 0 of one [D, H, W] uint8 / float32 volume (MONAI CropForegroundd's default select_fn, margin
+    0): int32 [6] = {d0, d1, h0, h1, w0, w1}, half-open, left on the GPU.  No voxel > 0: the full extent."""
+    if vol.dim() != 3 or vol.dtype not in _VOL_DTYPES:
+        raise RuntimeError(f"volume_box: expected a [D, H, W] uint8 or float32 volume, got {tuple(vol.shape)} {vol.dtype}")
+    _chk(vol, vol.dtype, "volume_box")
+    D, H, W = vol.shape
+    box = torch.empty((6,), dtype=torch.int32, device=vol.device)
+    _launch("volume_box", 0.0, float(vol.numel() * vol.element_size()),
+            lambda: call("octmae_volume_box", vol.data_ptr(), _VOL_DTYPES[vol.dtype], D, H, W, box.data_ptr(), _stream()))
+    return box
+
+
+def volume_resample(vol: torch.Tensor, size, box: Optional[torch.Tensor] = None, flip_d: bool = False, flip_w: bool = False,
+                    normalize=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.interpolate(mode="trilinear", align_corners=False) of one [D, H, W] uint8 / float32 volume (of the sub-volume ``box`` names:
+    volume_box's six device ints) to ``size`` = (T, OH, OW), the result's first / last axis reversed by ``flip_d`` / ``flip_w``, then
+    ``normalize`` = (subtrahend, divisor) applied where the value is not 0.  ``out``: a contiguous float32 [T, OH, OW] tensor, which
+    may be a slice of a batch tensor."""
+    if vol.dim() != 3 or vol.dtype not in _VOL_DTYPES:
+        raise RuntimeError(f"volume_resample: expected a [D, H, W] uint8 or float32 volume, got {tuple(vol.shape)} {vol.dtype}")
+    _chk(vol, vol.dtype, "volume_resample")
+    T, OH, OW = (int(s) for s in size)
+    if out is None:
+        out = torch.empty((T, OH, OW), dtype=F32, device=vol.device)
+    else:
+        _chk(out, F32, "volume_resample out")
+        if tuple(out.shape) != (T, OH, OW) or out.device != vol.device:
+            raise RuntimeError(f"volume_resample: out is {tuple(out.shape)} on {out.device}, expected {(T, OH, OW)} on {vol.device}")
+    if box is not None:
+        _chk(box, torch.int32, "volume_resample box")
+        if box.numel() != 6 or box.device != vol.device:
+            raise RuntimeError("volume_resample: box must be six int32 on the volume's device")
+    sub, div = (0.0, 1.0) if normalize is None else (float(normalize[0]), float(normalize[1]))
+    D, H, W = vol.shape
+    # algorithmic HBM bytes: the (boxed) volume read once, the output written once
+    _launch("volume_resample", 0.0, float(vol.numel() * vol.element_size() + 4 * out.numel()),
+            lambda: call("octmae_volume_resample", vol.data_ptr(), _VOL_DTYPES[vol.dtype], D, H, W, _p(box), out.data_ptr(), T, OH, OW,
+                         int(bool(flip_d)), int(bool(flip_w)), int(normalize is not None), sub, div, _stream()))
+    return out
+
+
 # optimistic (no running max) forward first, safe kernel as the device-side fallback.  Not in the half build: the un-normalised
 # P = exp2(s) of that kernel is an MFMA operand, and half ends at 65 504 = e^11.09 where bfloat16 has fp32's range (the online-max
 # kernel keeps P <= 2^8)
