@@ -16,6 +16,8 @@
 #ifndef OCTMAE_H_
 #define OCTMAE_H_
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -32,8 +34,9 @@ extern "C" {
  *     now force the 256-tile main loop they name for forward and dgrad launches too, and never the small-launch kernel.
  * 14: splitk = 0 of a weight gradient (octmae_gemm_bf16[_ws] epilogue 5, octmae_wgrad_accum_pair and the two plan queries) means
  *     "chosen by the planner" (csrc/gemm_plan.hpp: auto_wgrad_split); until now 0 ran as 1.  No new entry points.
- * 15: octmae_volume_box, octmae_volume_resample (the volume transforms in front of the models, csrc/transform3d.hip). */
-#define OCTMAE_ABI_VERSION 15
+ * 15: octmae_volume_box, octmae_volume_resample (the volume transforms in front of the models, csrc/transform3d.hip).
+ * 16: octmae_mae_compose (the reconstruction volumes of the validation pass, csrc/recon.hip). */
+#define OCTMAE_ABI_VERSION 16
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -319,6 +322,25 @@ int octmae_mse_fwd(const float* pred, const float* imgs, const int* frame_idx, f
 /* dpred bf16 [B][L+1][PD] = *coef * mask * (pred - target), cls rows zero (backward of :649-663) */
 int octmae_mse_bwd(const float* pred, const float* imgs, const int* frame_idx, const float* mask, const float* coef,
                    void* dpred_bf16, int B, int C, int T, int H, int W, int u_sz, int p, int L, int norm_pix, void* stream);
+/* The reconstruction volumes of the validation pass (Pre-training/engine_pretrain.py:207-357 eval_one_epoch ->
+ * custom_util/misc.py:1225-1299 get_visible_images: unpatchify of pred and of the mask, index_select of the frames,
+ * untransform_image :727-728, the two blends) in one pass.  One channel only.
+ *   pred       f32, token 0 of sample 0; [L][PD] per sample, PD = u_sz * p * p, samples pred_batch_stride FLOATS apart (>= L * PD,
+ *              a multiple of 4): a contiguous [B][L][PD] tensor, or the [:, 1:, :] view of the decoder's [B][1 + L][PD] output
+ *   imgs       f32 [B][1][T][H][W];  mask f32 [B][L], != 0 = removed
+ *   frame_idx  NULL (predicted frame f is frame f of the volume; then Tp <= T) or Tp = (L / ((H/p) * (W/p))) * u_sz int32 source
+ *              frames, as octmae_mse_fwd takes them (clamped into [0, T) on the device)
+ *   out        uint8 [B][4][Tp][H][W]: 0 = g(x), 1 = mask ? 0 : g(x), 2 = g(pred), 3 = mask ? g(pred) : g(x), pred un-shuffled from
+ *              (t, h, w | u, py, px) to (frame, y, x);  g(v) = (int) clip((v * s + m) * 255, 0, 255), s = float(76.03 / 255),
+ *              m = float(45.79 / 255), the multiply, the add and the second multiply each rounded to fp32 on its own: bit-equal to
+ *              the reference's three tensor ops.  A non-finite v gives 0 (the reference's .int() of a NaN is undefined).
+ *   denorm     0: the reference's behaviour (the raw prediction, also for a norm_pix_loss model).  1: pred * sqrt(var + 1e-6) + mean
+ *              first, mean / unbiased var of that token's target patch as the norm_pix branch of the loss takes them (fp32).
+ * pred_batch_stride is a long long, as every 64-bit count of this header (octmae_cast_f32_bf16's n): the same type as long on LP64.
+ * -1: NULL / non-positive / misaligned arguments, p % 4, W % 4, PD % 4, H % p, W % p, L not a multiple of the (H/p) * (W/p) grid,
+ * a batch stride below L * PD.  -2: denorm outside {0, 1}, more than 2^31 - 1 tokens. */
+int octmae_mae_compose(const float* pred, long long pred_batch_stride, const float* imgs, const int* frame_idx, const float* mask,
+                       uint8_t* out, int B, int T, int H, int W, int u_sz, int p, int L, int denorm, void* stream);
 
 /* ---- optimizer side --------------------------------------------------------------------------------
  * Multi-tensor tables: tensor_table = device array of {float* p, g, m, v; int64 n}; chunk_tensor/chunk_off map

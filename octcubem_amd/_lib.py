@@ -59,6 +59,7 @@ SIGNATURES = {
     "octmae_dec_assemble_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "octmae_mse_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_mse_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "octmae_mae_compose": [_vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_mt_chunk_elems": [],
     "octmae_mt_sumsq": [_vp, _vp, _vp, _i, _vp, _vp],
     "octmae_mt_finish_norm": [_vp, _i, _f, _vp, _vp, _vp],

@@ -1,6 +1,6 @@
 """Pre-training inner loops with the reference's signatures: ``train_one_epoch`` (3-D volumes only) and
 ``train_one_epoch_joint`` (3-D volumes + 2-D/512 B-scans, per-frame loss feedback for self-paced sampling) plus the two
-epoch schedules of the joint recipe.
+epoch schedules of the joint recipe, and ``eval_one_epoch``, the validation pass with its reconstruction dumps.
 
 ``train_one_epoch``: pre-training inner loop with the reference's signature and per-iteration order of operations
 (OCTCube/engine_pretrain.py:31-91; Pre-training/engine_pretrain.py:29-204 is the same loop plus the 2-D branch):
@@ -16,6 +16,7 @@ optimizer, schedules) is this package's own."""
 from __future__ import annotations
 
 import math
+import os
 import sys
 from typing import Iterable
 
@@ -167,6 +168,67 @@ def train_one_epoch_joint(model: torch.nn.Module, data_loader: Iterable, optimiz
             epoch_1000x = int((data_iter_step / n_iter + epoch) * 1000 * getattr(args, "repeat_aug", 1))
             log_writer.add_scalar("train_loss", loss_value_reduce, epoch_1000x)
             log_writer.add_scalar("lr", lr, epoch_1000x)
+    metric_logger.synchronize_between_processes()
+    print("Averaged stats:", metric_logger)
+    return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
+
+
+@torch.no_grad()
+def eval_one_epoch(model: torch.nn.Module, data_loader: Iterable, device: torch.device, epoch: int, log_writer=None, args=None,
+                   fp32=False, joint=False, mask_ratio_2d=None, data_loader_2d=None, visible_frame_freq=20, all_image_dict=None,
+                   analysis=False, fp16=False, agg_data=False):
+    """Validation pass (Pre-training/engine_pretrain.py:207-357) with the reference's signature and order of operations: eval mode,
+    no grad, per batch ``loss, pred, mask = model(samples, mask_ratio=args.mask_ratio)`` -> non-finite guard -> on the main process,
+    every ``print_freq * visible_frame_freq``-th step, the reconstruction dump of that batch into
+    ``args.output_dir/val_images_<epoch>`` (misc.get_visible_images) -> ``loss`` / ``mask_ratio`` meters, ``val_loss`` to the writer.
+    ``data_loader`` yields ``(samples, img_names)``.  Returns the averaged stats, or None on a non-finite loss (as engine_finetune).
+    Not reproduced: the per-step device synchronise, ``forward_patch_embed`` / ``get_patch_embed_images`` (analysis output nothing
+    reads), the checkpoint deletion on a non-finite loss, and the secondary 2-D loader of the joint recipe -- ``joint`` only picks
+    ``img_names[0]`` as there; ``mask_ratio_2d``, ``data_loader_2d``, ``all_image_dict``, ``analysis``, ``agg_data`` and ``fp32`` /
+    ``fp16`` (bf16 operands, fp32 everything else) are accepted and ignored.
+    The pass leaves ``.grad`` as it found it: the parameter arena attaches its gradient views when a model's first forward creates it
+    (octcubem_amd/arena.py), also under no_grad; parameters that came in without a gradient go out without one, and the next forward
+    with grad enabled re-attaches the views (``arena.rebind_grads``).  Nothing computes a gradient inside the pass, so a parameter that
+    came in with a gradient keeps it untouched, and a model without an arena is left exactly as it was."""
+    no_grad_at_entry = [p for p in model.parameters() if p.grad is None]
+    try:
+        return _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, visible_frame_freq)
+    finally:
+        for p in no_grad_at_entry:
+            p.grad = None
+
+
+def _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, visible_frame_freq):
+    img_save_dir = os.path.join(args.output_dir, f"val_images_{epoch}")
+    os.makedirs(img_save_dir, exist_ok=True)
+    model.eval()
+    metric_logger = misc.MetricLogger(delimiter="  ")
+    metric_logger.add_meter("mask_ratio", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
+    header = "Epoch: [{}]".format(epoch)
+    print_freq = 20
+    accum_iter = args.accum_iter
+    n_iter = len(data_loader)
+    for data_iter_step, (samples, img_names) in enumerate(metric_logger.log_every(data_loader, print_freq, header)):
+        samples = samples.to(device, non_blocking=True)
+        if samples.dim() == 6:
+            b, r, c, t, h, w = samples.shape
+            samples = samples.reshape(b * r, c, t, h, w)
+        loss, pred, mask = model(samples, mask_ratio=args.mask_ratio)
+        loss_value = loss.item()
+        if not math.isfinite(loss_value):
+            print("Loss is {}, stopping evaluation".format(loss_value))
+            return None
+        if data_iter_step % (print_freq * visible_frame_freq) == 0 and misc.is_main_process():
+            if joint:
+                img_names = img_names[0]
+            vars_ = {"reconstruct_imgs": pred, "samples": samples, "mask": mask, "img_names": img_names}
+            misc.get_visible_images(vars_, model, img_save_dir)
+        metric_logger.update(loss=loss_value)
+        metric_logger.update(mask_ratio=args.mask_ratio)
+        loss_value_reduce = misc.all_reduce_mean(loss_value)
+        if log_writer is not None and (data_iter_step + 1) % accum_iter == 0:
+            epoch_1000x = int((data_iter_step / n_iter + epoch) * 1000 * getattr(args, "repeat_aug", 1))
+            log_writer.add_scalar("val_loss", loss_value_reduce, epoch_1000x)
     metric_logger.synchronize_between_processes()
     print("Averaged stats:", metric_logger)
     return {k: meter.global_avg for k, meter in metric_logger.meters.items()}

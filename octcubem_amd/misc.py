@@ -1,6 +1,7 @@
 """Train-step utilities with the reference's call contracts (Pre-training/custom_util/misc.py):
 NativeScalerWithGradNormCount (:308-353), get_grad_norm_ (:356-373), add_weight_decay (:678-696),
-init_distributed_mode (:252-297), all_reduce_mean (:622-630), SmoothedValue / MetricLogger (:42-201).
+init_distributed_mode (:252-297), all_reduce_mean (:622-630), SmoothedValue / MetricLogger (:42-201),
+get_visible_images (:1225-1299).
 """
 from __future__ import annotations
 
@@ -446,3 +447,39 @@ def interpolate_temporal_pos_embed(model, checkpoint_model, smaller_interpolate_
     """OCTCube/util/misc.py:1225-1258 (the same function as util/pos_embed.py's)."""
     from .pos_embed import interpolate_temporal_pos_embed as f
     return f(model, checkpoint_model, smaller_interpolate_type)
+
+
+# ------------------------------------------------------------------------------------------------
+# reconstruction dumps of the validation pass
+# ------------------------------------------------------------------------------------------------
+def get_visible_images(vars_: dict, model, save_dir: str, pad_to_pred_t_dim=True, offset: int = 0, suffix: str = "", high_res: bool = False):
+    """The reference's reconstruction dump (custom_util/misc.py:1225-1299) with its signature and its ``vars_`` keys
+    (``reconstruct_imgs`` = pred, ``samples``, ``mask``, ``img_names``): per volume i and predicted frame z one file
+    ``save_dir/<img_names[i]>/frame_<z + offset><suffix>.png``.  The four panels (original, masked, reconstruction, reconstruction
+    pasted with the visible patches) come from ONE kernel (``model.reconstruct`` -> ops.mae_compose) as uint8 grey levels and are
+    written side by side as one [H, 4 W] grey image: no matplotlib figure (whose colour map the reference rescales per panel).
+    Pillow writes the PNG; without it one ``frames<suffix>.npy`` of [4, Tp, H, W] per volume is written instead.
+    ``pad_to_pred_t_dim`` / ``high_res`` are accepted for call compatibility: the frame selection and the patch embed follow from
+    the shapes, as in the loss.  A DDP-style wrapper is unwrapped through ``.module``.  Returns the uint8 [N, 4, Tp, H, W] tensor."""
+    net = getattr(model, "module", model)
+    names = list(vars_["img_names"])
+    vols = net.reconstruct(vars_["samples"], vars_["reconstruct_imgs"], vars_["mask"])
+    vols = vols.cpu()                                   # the one device -> host copy: 4 bytes per voxel
+    if vols.shape[0] != len(names):
+        raise ValueError(f"get_visible_images: {len(names)} img_names for {vols.shape[0]} volumes")
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    for i, name in enumerate(names):
+        d = os.path.join(save_dir, str(name))
+        os.makedirs(d, exist_ok=True)
+        v = vols[i].numpy()                             # [4, Tp, H, W]
+        if Image is None:
+            import numpy as np
+            np.save(os.path.join(d, f"frames{suffix}.npy"), v)
+            continue
+        for z in range(v.shape[1]):
+            row = v[:, z].transpose(1, 0, 2).reshape(v.shape[2], 4 * v.shape[3])       # [H, 4 W]: the panels left to right
+            Image.fromarray(row).save(os.path.join(d, f"frame_{z + offset}{suffix}.png"))
+    return vols

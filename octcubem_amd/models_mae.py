@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from . import ops, video_vit
 from .arena import get_arena
 from .video_vit import layer_norm
-from ._autocast import autocast_invariant
+from ._autocast import autocast_invariant, no_autocast
 
 
 @autocast_invariant
@@ -312,12 +312,7 @@ class MaskedAutoencoderViT(nn.Module):
         if pred_full is None or pred_full.shape[0] != pred.shape[0] or pred_full.shape[1] != pred.shape[1] + 1 or \
                 pred.data_ptr() != pred_full[:, 1:, :].data_ptr():
             pred_full = torch.cat([torch.zeros_like(pred[:, :1, :]), pred], dim=1).float().contiguous()
-        if T == 3:
-            frame_idx = None
-        else:
-            fi = torch.linspace(0, T - 1, self.pred_t_dim).long()
-            frame_idx = None if (self.pred_t_dim == T and bool((fi == torch.arange(T)).all())) else \
-                fi.to(device=imgs.device, dtype=torch.int32)
+        frame_idx = self._frame_idx(T, imgs.device)
         loss_tok = ops.PatchMSEFn.apply(pred_full, imgs.contiguous(), frame_idx, self.t_pred_patch_size, p, self.norm_pix_loss)
         mask = mask.view(loss_tok.shape)
         t = T // pe_mod.t_patch_size
@@ -328,6 +323,31 @@ class MaskedAutoencoderViT(nn.Module):
         if frame_loss:
             return loss, frame_losses
         return loss
+
+    def _frame_idx(self, T, device):
+        """The frames of a T-frame volume the prediction stands for (:627-642): None = frame f is frame f."""
+        if T == 3:
+            return None
+        fi = torch.linspace(0, T - 1, self.pred_t_dim).long()
+        if self.pred_t_dim == T and bool((fi == torch.arange(T)).all()):
+            return None
+        return fi.to(device=device, dtype=torch.int32)
+
+    @no_autocast
+    @torch.no_grad()
+    def reconstruct(self, imgs, pred, mask, denormalize=False):
+        """What the reference's validation pass draws (custom_util/misc.py:1225-1299 get_visible_images), as one kernel over what
+        ``forward`` returned: uint8 [N, 4, Tp, H, W] = original frames, masked input, reconstruction, reconstruction pasted with the
+        visible patches, in the grey levels of untransform_image (:727-728) and bit-equal to that chain.  Patch size, temporal patch
+        and the frame selection are forward_loss's (the 512^2 B-scan branch by shape alone); ``pred`` may be the strided view
+        ``forward`` returns (no copy).  ``denormalize=False`` is the reference: the raw prediction, also for a norm_pix_loss model;
+        True maps it back through the per-patch mean / variance of the target first.  A non-finite value is drawn as 0."""
+        if self.in_chans != 1:
+            raise NotImplementedError("reconstruct: one channel (every call site of the reference's visualiser has in_chans == 1)")
+        imgs = imgs.float().contiguous()
+        pe_mod = self.high_res_patch_embed if self._is_high_res(imgs) else self.patch_embed
+        return ops.mae_compose(pred.float(), imgs, mask.float(), self._frame_idx(imgs.shape[2], imgs.device),
+                               self.t_pred_patch_size, pe_mod.patch_size[0], bool(denormalize))
 
     def forward(self, imgs, mask_ratio=0.75, frame_loss=False, pre_mask=None, noise=None):
         self.prepare()

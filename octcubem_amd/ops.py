@@ -512,6 +512,42 @@ def volume_resample(vol: torch.Tensor, size, box: Optional[torch.Tensor] = None,
     return out
 
 
+def mae_compose(pred: torch.Tensor, imgs: torch.Tensor, mask: torch.Tensor, frame_idx: Optional[torch.Tensor], u: int, p: int,
+                denorm: bool = False) -> torch.Tensor:
+    """The four reconstruction volumes of the validation pass (custom_util/misc.py:1225-1299 get_visible_images) in one kernel:
+    uint8 [B, 4, Tp, H, W] = original frames, masked input, reconstruction, reconstruction pasted with the visible patches, grey levels
+    of untransform_image (:727-728), bit-equal to the reference's chain.  ``pred`` f32 [B, L, u*p*p]: contiguous, or any view whose
+    samples are contiguous [L, PD] blocks a multiple of 4 floats apart (``pred_full[:, 1:, :]`` of the decoder's output: no copy);
+    ``imgs`` f32 [B, 1, T, H, W]; ``mask`` f32 [B, L], 1 = removed; ``frame_idx`` None or Tp int32 source frames.  ``denorm``: map
+    pred back from per-patch standardised units first (a norm_pix_loss model).  No autograd."""
+    if pred.dim() != 3 or imgs.dim() != 5 or imgs.shape[1] != 1:
+        raise RuntimeError(f"mae_compose: expected pred [B, L, PD] and imgs [B, 1, T, H, W], got {tuple(pred.shape)} and {tuple(imgs.shape)}")
+    pred, mask = pred.detach(), mask.detach()
+    imgs = _chk(imgs.detach(), F32, "mae_compose imgs")
+    if not pred.is_cuda or pred.dtype != F32:
+        raise RuntimeError(f"mae_compose pred: expected a float32 GPU tensor, got {pred.dtype} on {pred.device}")
+    Bn, L, PD = pred.shape
+    _, _, T, Hh, Ww = imgs.shape
+    if pred.stride(2) != 1 or pred.stride(1) != PD or (Bn > 1 and (pred.stride(0) < L * PD or pred.stride(0) % 4)):
+        pred = pred.contiguous()
+    bs = pred.stride(0) if Bn > 1 else L * PD
+    mask = _chk(mask.reshape(Bn, L), F32, "mae_compose mask")
+    if imgs.shape[0] != Bn or PD != u * p * p or Hh % p or Ww % p or L % ((Hh // p) * (Ww // p)):
+        raise RuntimeError(f"mae_compose: pred {tuple(pred.shape)} does not tile imgs {tuple(imgs.shape)} with u={u}, p={p}")
+    Tp = L // ((Hh // p) * (Ww // p)) * u
+    if frame_idx is not None:
+        _chk(frame_idx, torch.int32, "mae_compose frame_idx")
+        if frame_idx.numel() != Tp:
+            raise RuntimeError(f"mae_compose: frame_idx has {frame_idx.numel()} entries, the prediction has {Tp} frames")
+    out = torch.empty((Bn, 4, Tp, Hh, Ww), dtype=torch.uint8, device=imgs.device)
+    # algorithmic HBM bytes: pred, the gathered frames (twice more with denorm) and the mask read, four uint8 panels written
+    nvox = Bn * Tp * Hh * Ww
+    _launch("mae_compose", 0.0, float(4 * Bn * L * PD + 4 * nvox * (2 if denorm else 1) + 4 * Bn * L + 4 * nvox),
+            lambda: call("octmae_mae_compose", pred.data_ptr(), bs, imgs.data_ptr(), _p(frame_idx), mask.data_ptr(), out.data_ptr(),
+                         Bn, T, Hh, Ww, u, p, L, int(bool(denorm)), _stream()))
+    return out
+
+
 # optimistic (no running max) forward first, safe kernel as the device-side fallback.  Not in the half build: the un-normalised
 # P = exp2(s) of that kernel is an MFMA operand, and half ends at 65 504 = e^11.09 where bfloat16 has fp32's range (the online-max
 # kernel keeps P <= 2^8)
