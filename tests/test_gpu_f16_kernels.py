@@ -30,10 +30,12 @@ TIMEOUT_S = 1500
 SUITES = ["tests/test_gpu_kernels.py", "tests/test_gpu_gemm_small.py",
           "tests/test_gpu_slicehead.py::test_slice_pool_kernels_vs_fp32_composition",
           "tests/test_gpu_slicehead.py::test_slice_pool_sidecar_matches_its_gradient",
-          "tests/test_gpu_lp_edges.py", "tests/test_gpu_attention_rows.py", "tests/test_gpu_tokens.py"]
+          "tests/test_gpu_lp_edges.py", "tests/test_gpu_attention_rows.py", "tests/test_gpu_tokens.py",
+          "tests/test_gpu_layernorm_rows.py"]
 # tests per module the child must run (passed + skipped), as collected with -m gpu when this module was written
 MIN_TESTS = {"tests.test_gpu_kernels": 529, "tests.test_gpu_gemm_small": 20, "tests.test_gpu_slicehead": 37,
-             "tests.test_gpu_lp_edges": 64, "tests.test_gpu_attention_rows": 21, "tests.test_gpu_tokens": 31}
+             "tests.test_gpu_lp_edges": 64, "tests.test_gpu_attention_rows": 21, "tests.test_gpu_tokens": 31,
+             "tests.test_gpu_layernorm_rows": 116}
 # (test id, skip reason) pairs the half build may skip: none today
 ALLOWED_SKIPS = set()
 
