@@ -17,9 +17,21 @@ from ._lib import call
 from .ops import _stream
 
 
+def _entry_key(p, g, m=None, v=None):
+    """What a table holds of one tensor, plus what it relies on: the kernels read p, g, m and v as flat memory of p.numel() elements.
+    The element count is part of it (views of one buffer, or an allocator block handed to another model, share pointers and not
+    sizes), and so is the layout (a gradient replaced by a transposed view of itself keeps its pointer)."""
+    return (p.data_ptr(), g.data_ptr() if g is not None else 0, m.data_ptr() if m is not None else 0,
+            v.data_ptr() if v is not None else 0, p.numel(), p.is_contiguous() and (g is None or g.is_contiguous()))
+
+
 class _MultiTensorTable:
     """Device-side tables for a list of (p, g, m, v) tensors: octmae_mt_* calling convention.  ``lps``: per tensor the device
-    address of the 16-bit operand copy of p (0: none) -- the optional table octmae_mt_adamw_fused writes through."""
+    address of the 16-bit operand copy of p (0: none) -- the optional table octmae_mt_adamw_fused writes through.
+    Every tensor must be contiguous and of p's element count: the kernels pair element i of p with element i of g, m and v in
+    memory order, so a transposed or expanded gradient, or a parameter in a permuted layout, would be silently mis-paired
+    (ValueError instead; arena tensors are always contiguous).  Zero-element tensors take part and have no chunks; a table whose
+    tensors are all empty has n_chunks == 0 and must not be launched (the entry points reject an empty grid)."""
 
     def __init__(self, ps: List[torch.Tensor], gs, ms, vs, lps=None):
         from ._lib import load
@@ -29,6 +41,13 @@ class _MultiTensorTable:
         ct, co = [], []
         for i, (p, g, m, v) in enumerate(zip(ps, gs, ms, vs)):
             n = p.numel()
+            for name, t in (("parameter", p), ("gradient", g), ("exp_avg", m), ("exp_avg_sq", v)):
+                if t is None:
+                    continue
+                if t.numel() != n or not t.is_contiguous():
+                    raise ValueError(f"multi-tensor optimizer kernels need contiguous tensors of the parameter's size: {name} {i} has "
+                                     f"shape {tuple(t.shape)}, strides {tuple(t.stride())} (parameter: shape {tuple(p.shape)}); "
+                                     "make it contiguous (e.g. p.grad = p.grad.contiguous())")
             raw += struct.pack("<QQQQq", p.data_ptr(), g.data_ptr() if g is not None else 0,
                                m.data_ptr() if m is not None else 0, v.data_ptr() if v is not None else 0, n)
             for off in range(0, n, chunk):
@@ -42,8 +61,7 @@ class _MultiTensorTable:
         if lps is not None and any(lps):
             self.lp_table = torch.tensor([int(a) for a in lps], dtype=torch.int64, device=dev)
         # every pointer the table holds is part of its identity: a loaded optimizer state replaces exp_avg / exp_avg_sq
-        self.key = tuple((p.data_ptr(), g.data_ptr() if g is not None else 0, m.data_ptr() if m is not None else 0,
-                          v.data_ptr() if v is not None else 0) for p, g, m, v in zip(ps, gs, ms, vs))
+        self.key = tuple(_entry_key(p, g, m, v) for p, g, m, v in zip(ps, gs, ms, vs))
 
 
 def grad_norm_and_coef(params, max_norm: Optional[float], cache: dict):
@@ -52,7 +70,7 @@ def grad_norm_and_coef(params, max_norm: Optional[float], cache: dict):
     ps = [p for p in params if p.grad is not None]
     if not ps:
         return torch.tensor(0.0), None
-    key = tuple((p.data_ptr(), p.grad.data_ptr(), 0, 0) for p in ps)
+    key = tuple(_entry_key(p, p.grad) for p in ps)
     tab = cache.get("norm")
     if tab is None or tab.key != key:
         tab = _MultiTensorTable([p.data for p in ps], [p.grad for p in ps], [None] * len(ps), [None] * len(ps))
@@ -60,8 +78,9 @@ def grad_norm_and_coef(params, max_norm: Optional[float], cache: dict):
     dev = ps[0].device
     sumsq = torch.zeros(tab.n_tensors, dtype=torch.float32, device=dev)
     out = torch.empty(2, dtype=torch.float32, device=dev)
-    call("octmae_mt_sumsq", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(), tab.n_chunks,
-         sumsq.data_ptr(), _stream())
+    if tab.n_chunks:                                       # every gradient empty: the norm of nothing is 0
+        call("octmae_mt_sumsq", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(), tab.n_chunks,
+             sumsq.data_ptr(), _stream())
     call("octmae_mt_finish_norm", sumsq.data_ptr(), tab.n_tensors, float(max_norm) if max_norm is not None else 0.0,
          out.data_ptr(), out.data_ptr() + 4, _stream())
     return out[0], out[1]
@@ -123,6 +142,8 @@ class FusedAdamW(torch.optim.Optimizer):
         from . import arena as _arena
         loss = closure() if closure is not None else None
         sumsq = None
+        # first the tables of every group (a tensor the kernels cannot take raises here, before any group has been stepped) ...
+        work = []
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -133,16 +154,7 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["step"] = 0
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            if "_step" not in group:
-                # a state loaded from torch.optim.AdamW carries the count per parameter ("step", int or tensor), not per
-                # group: continue from it so that the bias correction does not restart
-                steps = [self.state[p].get("step", 0) for p in ps]
-                group["_step"] = int(max(float(s_) for s_ in steps)) if steps else 0
-            group["_step"] += 1
-            for p in ps:
-                self.state[p]["step"] = group["_step"]
-            key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(),
-                         self.state[p]["exp_avg_sq"].data_ptr()) for p in ps)
+            key = tuple(_entry_key(p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in ps)
             tab = self._tables.get(gi)
             if tab is None or tab.key != key or tab.mirror != self.write_mirror:
                 owners = [_arena.arena_of(p) for p in ps]
@@ -153,11 +165,24 @@ class FusedAdamW(torch.optim.Optimizer):
                 # arenas whose parameters this group updates WITHOUT writing their operand copy: they must re-cast
                 tab.stale_arenas = [a for a in {id(a): a for a, lp in zip(owners, lps) if a is not None and lp == 0}.values()]
                 self._tables[gi] = tab
+            work.append((gi, group, ps, tab))
+        # ... then the steps
+        for gi, group, ps, tab in work:
+            if "_step" not in group:
+                # a state loaded from torch.optim.AdamW carries the count per parameter ("step", int or tensor), not per
+                # group: continue from it so that the bias correction does not restart
+                steps = [self.state[p].get("step", 0) for p in ps]
+                group["_step"] = int(max(float(s_) for s_ in steps)) if steps else 0
+            group["_step"] += 1
+            for p in ps:
+                self.state[p]["step"] = group["_step"]
             for a in tab.stale_arenas:
                 a.invalidate_lp()
             if want_norm and sumsq is None:
-                n_max = max(len([p for p in g["params"] if p.grad is not None]) for g in self.param_groups)
-                sumsq = torch.zeros((len(self.param_groups), max(n_max, 1)), dtype=torch.float32, device=ps[0].device)
+                n_max = max(len(w[2]) for w in work)
+                sumsq = torch.zeros((len(self.param_groups), n_max), dtype=torch.float32, device=ps[0].device)
+            if not tab.n_chunks:                           # only zero-element parameters: nothing to update
+                continue
             b1, b2 = group["betas"]
             gs = self._grad_scale
             call("octmae_mt_adamw_fused", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(), tab.n_chunks,
