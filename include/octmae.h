@@ -35,8 +35,9 @@ extern "C" {
  * 14: splitk = 0 of a weight gradient (octmae_gemm_bf16[_ws] epilogue 5, octmae_wgrad_accum_pair and the two plan queries) means
  *     "chosen by the planner" (csrc/gemm_plan.hpp: auto_wgrad_split); until now 0 ran as 1.  No new entry points.
  * 15: octmae_volume_box, octmae_volume_resample (the volume transforms in front of the models, csrc/transform3d.hip).
- * 16: octmae_mae_compose (the reconstruction volumes of the validation pass, csrc/recon.hip). */
-#define OCTMAE_ABI_VERSION 16
+ * 16: octmae_mae_compose (the reconstruction volumes of the validation pass, csrc/recon.hip).
+ * 17: octmae_image_resample, octmae_image_resample_plan (the 2-D image transforms in front of the 2-D towers, csrc/image2d.hip). */
+#define OCTMAE_ABI_VERSION 17
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -234,6 +235,31 @@ int octmae_slice_pool_bwd(const float* dout, const float* pooled, const float* m
 int octmae_volume_box(const void* vol, int dtype, int D, int H, int W, int* box6, void* stream);
 int octmae_volume_resample(const void* vol, int dtype, int D, int H, int W, const int* box6, float* out, int T, int OH, int OW,
                            int flip_d, int flip_w, int normalize, float subtrahend, float divisor, void* stream);
+
+/* ---- 2-D image transforms ---------------------------------------------------------------------------
+ * The reference's torchvision-on-PIL chains over B-scans and fundus / en-face images, in one launch for n equally shaped images:
+ *   Pre-training/main_pretrain_oph_joint_2d512_flash_attn.py:313-317   Resize((S, S), interpolation=3) -> ToTensor -> Normalize
+ *   OCTCube/main_pretrain_oph_new.py:151-156, OCTCube/main_pretrain.py:133-137
+ *                                       RandomResizedCrop(S, scale=(0.2, 1.0), interpolation=3) -> RandomHorizontalFlip -> ToTensor -> Normalize
+ *   OCTCube/util/PatientDataset_inhouse_pretrain.py:247-252            frame.resize((512, h))  (Pillow's default filter: bicubic)
+ * crop -> Pillow's two-pass 8-bit bicubic resize -> horizontal flip -> table, bit-equal to Pillow (Resample.c): per axis, with `in`
+ * the crop's extent, scale = in / out, support = 2 max(scale, 1), window [xmin, xmin + xmax) = [max((int)(c - support + 0.5), 0),
+ * min((int)(c + support + 0.5), in)) around c = (xx + 0.5) scale, bicubic (a = -0.5) weights in IEEE double summed in tap order,
+ * k = (int)(w / sum * 2^22 +- 0.5); a pass is clamp((2^21 + sum pixel * k) >> 22, 0, 255) in 32-bit integers; the horizontal pass
+ * runs first and is rounded to uint8, the vertical pass runs over those values.  The crop is torchvision's resized_crop of a PIL
+ * image (crop, then resize): the windows clamp at the crop's edges.  Same code in the two builds of the library.
+ *   src   uint8 [n][H][W] (C = 1) or [n][H][W][3] (C = 3, interleaved), contiguous
+ *   top, left, ch, cw   the crop rectangle inside H x W; ch = cw = 0 (with top = left = 0): the whole image
+ *   flip_w  reverse the output's last spatial axis (RandomHorizontalFlip, after the resize)
+ *   lut   float32 [3][256] in DEVICE memory: ToTensor -> Normalize of every grey level per output channel; dst is then
+ *         float32 [n][3][OH][OW] (a grey image is replicated: convert("RGB")).  NULL: dst is uint8 [n][OH][OW] / [n][OH][OW][3].
+ * -1, before any launch: a NULL src / dst, n or a size < 1, C not 1 or 3, a crop outside the image or with exactly one of ch, cw
+ * zero, or a reduction so strong that one output row's windows do not fit the kernel's 64 KiB of LDS (a factor in the hundreds).
+ * octmae_image_resample_plan is HOST ONLY: the output rows of a workgroup's tile (32, 16, 8, 4, 2 or 1) and the LDS bytes of the
+ * launch octmae_image_resample would make for this geometry (csrc/image2d_plan.hpp); -1 as above. */
+int octmae_image_resample(const void* src, int n, int H, int W, int C, int top, int left, int ch, int cw, int OH, int OW, int flip_w,
+                          const float* lut, void* dst, void* stream);
+int octmae_image_resample_plan(int H, int W, int C, int ch, int cw, int OH, int OW, int* tile_h, int* lds_bytes);
 
 /* ---- attention -----------------------------------------------------------------------------------
  * softmax(q k^T * scale) v, non-causal, no dropout: video_vit.py:130-134 (flash path: flash_attn MHA,

@@ -512,6 +512,47 @@ def volume_resample(vol: torch.Tensor, size, box: Optional[torch.Tensor] = None,
     return out
 
 
+def image_resample(img: torch.Tensor, size, crop=None, flip: bool = False, lut: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pillow's 8-bit bicubic resize (``Image.resize(..., Image.BICUBIC)``, what torchvision's Resize / resized_crop with
+    interpolation=3 call for a PIL image), bit for bit, of uint8 images [H, W], [H, W, 3], [n, H, W] or [n, H, W, 3] (a 3-D input whose
+    last axis is 3 is ONE RGB image) to ``size`` = (OH, OW), in one launch: ``crop`` = (top, left, height, width) is taken first (the
+    windows clamp at its edges), ``flip`` reverses the result's width axis.  With ``lut`` (float32 [3, 256]: ToTensor -> Normalize of
+    every grey level per channel) the result is float32 [n, 3, OH, OW], a grey input replicated (convert("RGB")); without, uint8 in the
+    layout of the input.  ``out``: a contiguous tensor of the result's shape, which may be a slice of a batch.  No autograd; integer
+    arithmetic, so autocast changes nothing."""
+    if img.dtype != torch.uint8 or img.dim() not in (2, 3, 4) or (img.dim() == 4 and img.shape[-1] != 3):
+        raise RuntimeError(f"image_resample: expected uint8 [H, W], [H, W, 3], [n, H, W] or [n, H, W, 3], got {tuple(img.shape)} {img.dtype}")
+    img = _chk(img.detach(), torch.uint8, "image_resample")
+    C = 3 if img.dim() == 4 or (img.dim() == 3 and img.shape[-1] == 3) else 1
+    batched = img.dim() - (C == 3) == 3
+    n = img.shape[0] if batched else 1
+    H, W = img.shape[1:3] if batched else img.shape[:2]
+    OH, OW = (int(s) for s in size)
+    top, left, ch, cw = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+    if crop is not None and (ch < 1 or cw < 1):
+        raise RuntimeError(f"image_resample: empty crop {tuple(crop)}")
+    if lut is not None:
+        _chk(lut, F32, "image_resample lut")
+        if tuple(lut.shape) != (3, 256) or lut.device != img.device:
+            raise RuntimeError("image_resample: lut must be float32 [3, 256] on the image's device")
+        shape, dtype = (n, 3, OH, OW), F32
+    else:
+        shape, dtype = ((n,) if batched else ()) + (OH, OW) + ((3,) if C == 3 else ()), torch.uint8
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=img.device)
+    else:
+        _chk(out, dtype, "image_resample out")
+        if tuple(out.shape) != shape or out.device != img.device:
+            raise RuntimeError(f"image_resample: out is {tuple(out.shape)} on {out.device}, expected {shape} on {img.device}")
+    # algorithmic HBM bytes: the (cropped) images read once, the output written once
+    nbytes = float(n * (ch or H) * (cw or W) * C + out.numel() * out.element_size())
+    _launch("image_resample", 0.0, nbytes,
+            lambda: call("octmae_image_resample", img.data_ptr(), n, H, W, C, top, left, ch, cw, OH, OW, int(bool(flip)), _p(lut),
+                         out.data_ptr(), _stream()))
+    return out
+
+
 def mae_compose(pred: torch.Tensor, imgs: torch.Tensor, mask: torch.Tensor, frame_idx: Optional[torch.Tensor], u: int, p: int,
                 denorm: bool = False) -> torch.Tensor:
     """The four reconstruction volumes of the validation pass (custom_util/misc.py:1225-1299 get_visible_images) in one kernel:

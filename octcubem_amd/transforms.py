@@ -1,4 +1,6 @@
-"""Volume transforms: the drop-in counterpart of the reference's ``create_3d_transforms``
+"""Volume and image transforms on the GPU.  First the volumes; the 2-D images follow below (``create_2d_transforms``).
+
+Volume transforms: the drop-in counterpart of the reference's ``create_3d_transforms``
 (Pre-training/custom_util/PatientDataset_inhouse.py:48-84, the pipeline inference_utils.py:10 imports), on the GPU.
 
 The reference composes MONAI dictionary transforms on the CPU:
@@ -18,8 +20,10 @@ Deviations from the reference, both deliberate:
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -104,3 +108,170 @@ def create_3d_transforms(input_size, num_frames=64, RandFlipd_prob=0.5, RandRota
     train_transform = Volume3DTransform(size, crop=True, flip_prob=float(RandFlipd_prob), normalize=normalize, generator=generator)
     val_transform = Volume3DTransform(size, crop=False, flip_prob=None, normalize=normalize, generator=generator)
     return train_transform, val_transform
+
+
+# ---- 2-D images --------------------------------------------------------------------------------------------------------------------
+# The reference's torchvision chains on PIL images, per image on the CPU:
+#   joint pre-training (Pre-training/main_pretrain_oph_joint_2d512_flash_attn.py:313-317)
+#       Resize((S, S), interpolation=3) -> ToTensor -> Normalize(ImageNet)
+#   2-D MAE pre-training (OCTCube/main_pretrain_oph_new.py:151-156, OCTCube/main_pretrain.py:133-137)
+#       RandomResizedCrop(S, scale=(0.2, 1.0), interpolation=3) -> RandomHorizontalFlip -> ToTensor -> Normalize
+# Here each is one launch of ops.image_resample (csrc/image2d.hip) over the raw uint8 image: the crop is an offset, the resize is
+# Pillow's integer bicubic bit for bit, the flip an index reversal of the store, ToTensor -> Normalize a 3 x 256 table built with the
+# reference's own float ops -- so the result is bit-equal to the reference's for the same crop and flip decisions.
+# Deviation: those decisions follow torchvision's published rule (RandomResizedCrop.get_params, RandomHorizontalFlip) but are drawn
+# from ``generator`` on the host, crop first and flip second per image: the same distribution, not torchvision's random stream.
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+def normalize_lut(mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+    """ToTensor -> Normalize of the 256 grey levels per channel, float32 [3, 256] on the CPU, computed with the ops the reference's
+    chain runs (uint8 -> float32, div(255), sub(mean), div(std)): equal to it bit for bit for any mean / std."""
+    mean, std = (tuple(float(v) for v in m) if isinstance(m, (tuple, list)) else (float(m),) * 3 for m in (mean, std))
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError(f"mean / std: expected one value or three, got {mean} / {std}")
+    g = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
+    return torch.stack([(g - mean[c]) / std[c] for c in range(3)])
+
+
+def random_resized_crop_params(height: int, width: int, scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0),
+                               generator: Optional[torch.Generator] = None) -> Tuple[int, int, int, int]:
+    """(top, left, h, w) by the rule of torchvision's RandomResizedCrop.get_params: up to ten tries of area = H W U(scale),
+    log r ~ U(log ratio), w = round(sqrt(area r)), h = round(sqrt(area / r)), accepted when it fits, then placed uniformly; after ten
+    rejections the centred crop of the aspect ratio clamped into ``ratio``."""
+    area = height * width
+    lo, hi = math.log(ratio[0]), math.log(ratio[1])
+    for _ in range(10):
+        target = area * float(torch.empty(1).uniform_(scale[0], scale[1], generator=generator))
+        r = math.exp(float(torch.empty(1).uniform_(lo, hi, generator=generator)))
+        w, h = int(round(math.sqrt(target * r))), int(round(math.sqrt(target / r)))
+        if 0 < w <= width and 0 < h <= height:
+            top = int(torch.randint(0, height - h + 1, (1,), generator=generator))
+            left = int(torch.randint(0, width - w + 1, (1,), generator=generator))
+            return top, left, h, w
+    in_ratio = float(width) / float(height)
+    if in_ratio < min(ratio):
+        w = width
+        h = min(max(int(round(w / min(ratio))), 1), height)
+    elif in_ratio > max(ratio):
+        h = height
+        w = min(max(int(round(h * max(ratio))), 1), width)
+    else:
+        w, h = width, height
+    return (height - h) // 2, (width - w) // 2, h, w
+
+
+class Image2DTransform:
+    """Callable on one raw image -- a PIL image (mode L or RGB as it is, any other through ``convert("RGB")``), a numpy array or a
+    tensor, uint8 [H, W] or [H, W, 3], on the CPU or the GPU -- and returns float32 [3, S, S] on the GPU, without grad."""
+
+    def __init__(self, size: Tuple[int, int], mean=IMAGENET_MEAN, std=IMAGENET_STD, random_resized_crop: bool = False,
+                 scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), hflip_prob: float = 0.0, generator: Optional[torch.Generator] = None):
+        self.size = (int(size[0]), int(size[1]))
+        self.random_resized_crop = bool(random_resized_crop)
+        self.scale, self.ratio = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
+        self.hflip_prob = float(hflip_prob)
+        self.generator = generator
+        self.lut = normalize_lut(mean, std)
+        self._luts = {}                     # device -> the table there
+        self.last_params = None             # {"crop": (top, left, h, w) or None, "flip": bool} of the last call; a list after .batch
+
+    @staticmethod
+    def _image(x) -> torch.Tensor:
+        if hasattr(x, "convert") and hasattr(x, "mode"):        # a PIL image
+            x = np.array(x if x.mode in ("L", "RGB") else x.convert("RGB"))
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or not (x.dim() == 2 or (x.dim() == 3 and x.shape[2] == 3)):
+            what = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+            raise ValueError(f"image: expected a PIL image or uint8 [H, W] / [H, W, 3], got {what}")
+        return x.detach()
+
+    def _draw(self, height: int, width: int) -> dict:
+        crop = (random_resized_crop_params(height, width, self.scale, self.ratio, self.generator)
+                if self.random_resized_crop else None)
+        flip = bool(torch.rand(1, generator=self.generator) < self.hflip_prob) if self.hflip_prob > 0.0 else False
+        return {"crop": crop, "flip": flip}
+
+    def _lut_on(self, device) -> torch.Tensor:
+        t = self._luts.get(device)
+        if t is None:
+            t = self._luts[device] = self.lut.to(device)
+        return t
+
+    @torch.no_grad()
+    def __call__(self, image) -> torch.Tensor:
+        out = self.batch([image])[0]
+        self.last_params = self.last_params[0]
+        return out
+
+    @torch.no_grad()
+    def batch(self, images) -> torch.Tensor:
+        """A list of images (shapes may differ), or one uint8 array / tensor [B, H, W] or [B, H, W, 3], -> float32 [B, 3, S, S].  One
+        launch when every image has the same shape, no crop is drawn and nothing is flipped (the joint recipe's Resize chain);
+        otherwise one launch per image into slices of one output.  ``last_params`` is then the list of the images' decisions, drawn
+        in order (``__call__`` leaves the one image's dict there)."""
+        stack = None
+        if isinstance(images, (np.ndarray, torch.Tensor)):
+            stack = torch.from_numpy(np.ascontiguousarray(images)) if isinstance(images, np.ndarray) else images.detach()
+            if stack.dtype != torch.uint8 or not (stack.dim() == 3 or (stack.dim() == 4 and stack.shape[3] == 3)):
+                raise ValueError(f"batch: expected uint8 [B, H, W] or [B, H, W, 3], got {tuple(stack.shape)} {stack.dtype}")
+            imgs = list(stack.unbind(0))
+        else:
+            imgs = [self._image(x) for x in images]
+        if not imgs:
+            raise ValueError("batch: no images")
+        params = [self._draw(int(x.shape[0]), int(x.shape[1])) for x in imgs]
+        plain = all(p["crop"] is None and not p["flip"] for p in params) and all(x.shape == imgs[0].shape for x in imgs)
+        device = next((x.device for x in imgs if x.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+        with torch.cuda.device(device):
+            out = torch.empty((len(imgs), 3, *self.size), dtype=torch.float32, device=device)
+            lut = self._lut_on(device)
+            if plain:
+                if stack is None:
+                    stack = torch.stack(imgs) if len({x.device for x in imgs}) == 1 else torch.stack([x.to(device) for x in imgs])
+                ops.image_resample(stack.to(device).contiguous(), self.size, lut=lut, out=out)
+            else:
+                for b, (x, p) in enumerate(zip(imgs, params)):
+                    ops.image_resample(x.to(device).contiguous(), self.size, crop=p["crop"], flip=p["flip"], lut=lut, out=out[b:b + 1])
+        self.last_params = params
+        return out
+
+
+def create_2d_transforms(input_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, random_resized_crop=False, scale=(0.2, 1.0),
+                         ratio=(3.0 / 4.0, 4.0 / 3.0), hflip_prob=0.0, generator=None) -> Image2DTransform:
+    """The reference's 2-D chains as one object: ``create_2d_transforms(512)`` is the joint recipe's Resize -> ToTensor -> Normalize,
+    ``create_2d_transforms(224, random_resized_crop=True, hflip_prob=0.5)`` the 2-D MAE's RandomResizedCrop -> RandomHorizontalFlip ->
+    ToTensor -> Normalize.  ``generator``: the host torch.Generator the crops and flips are drawn from (None = the default one)."""
+    if isinstance(input_size, int):
+        input_size = (input_size, input_size)
+    return Image2DTransform(input_size, mean, std, random_resized_crop, scale, ratio, hflip_prob, generator)
+
+
+class DeviceTransformLoader:
+    """Iterates ``loader`` and replaces element ``index`` of every batch (a list or stack of raw uint8 images) by
+    ``transform.batch(...)``.  Data-loader workers cannot touch the GPU, so the dataset returns raw arrays and the transform runs here,
+    in the training process; ``train_one_epoch_joint`` takes this object as its ``data_loader_2d`` unchanged."""
+
+    def __init__(self, loader, transform, index=0):
+        self.loader, self.transform, self.index = loader, transform, index
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __getattr__(self, name):            # dataset, sampler, batch_size, ...: whatever the wrapped loader offers
+        if name in ("loader", "transform", "index"):
+            raise AttributeError(name)
+        return getattr(self.loader, name)
+
+    def __iter__(self):
+        for batch in self.loader:
+            if isinstance(batch, dict):
+                batch = dict(batch)
+                batch[self.index] = self.transform.batch(batch[self.index])
+            else:
+                items = list(batch)
+                items[self.index] = self.transform.batch(items[self.index])
+                batch = tuple(items) if isinstance(batch, tuple) else items
+            yield batch
