@@ -36,8 +36,9 @@ extern "C" {
  *     "chosen by the planner" (csrc/gemm_plan.hpp: auto_wgrad_split); until now 0 ran as 1.  No new entry points.
  * 15: octmae_volume_box, octmae_volume_resample (the volume transforms in front of the models, csrc/transform3d.hip).
  * 16: octmae_mae_compose (the reconstruction volumes of the validation pass, csrc/recon.hip).
- * 17: octmae_image_resample, octmae_image_resample_plan (the 2-D image transforms in front of the 2-D towers, csrc/image2d.hip). */
-#define OCTMAE_ABI_VERSION 17
+ * 17: octmae_image_resample, octmae_image_resample_plan (the 2-D image transforms in front of the 2-D towers, csrc/image2d.hip).
+ * 18: octmae_rank_counts (the rank counts behind AUROC / average precision of the fine-tune evaluation, csrc/metrics.hip). */
+#define OCTMAE_ABI_VERSION 18
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -367,6 +368,24 @@ int octmae_mse_bwd(const float* pred, const float* imgs, const int* frame_idx, c
  * a batch stride below L * PD.  -2: denorm outside {0, 1}, more than 2^31 - 1 tokens. */
 int octmae_mae_compose(const float* pred, long long pred_batch_stride, const float* imgs, const int* frame_idx, const float* mask,
                        uint8_t* out, int B, int T, int H, int W, int u_sz, int p, int L, int denorm, void* stream);
+
+/* ---- ranking metrics of the fine-tune evaluation (csrc/metrics.hip) ---------------------------------
+ * OCTCube/engine_finetune.py:251-343 and :786-792 judge a run by scikit-learn's roc_auc_score, average_precision_score and
+ * precision_recall_curve.  All of them follow exactly, ties included, from four integers per sample i and class c:
+ *   counts[i][c] = {gt_all, gt_pos, ge_all, ge_pos}: the samples j with s[j][c] > s[i][c], how many of those have a label != 0, and
+ *                  the same for >= (i counts itself there).
+ * With P positives and N negatives of a class: AUROC = sum over positives of (neg_lt + neg_eq / 2) / (P N), neg_ge = ge_all - ge_pos,
+ * neg_gt = gt_all - gt_pos, neg_lt = N - neg_ge, neg_eq = neg_ge - neg_gt; average precision = sum over positives of ge_pos / ge_all / P;
+ * the precision-recall curve has the points (ge_pos / P, ge_pos / ge_all), one per distinct ge_all (octcubem_amd/metrics.py finishes
+ * on the host in float64).  Integer counting: deterministic, no sort, no float accumulation; O(n^2 C) comparisons.
+ *   scores  f32 [n][C], rows score_stride ELEMENTS apart (>= C: a column slice of a wider buffer passes)
+ *   labels  uint8 [n][C], != 0 = positive, rows label_stride elements apart (>= C)
+ *   counts  int32 [n][C][4], contiguous
+ * Comparisons are IEEE: -0.0 ties with 0.0, +-inf are ordinary values; a NaN compares false with everything, so the caller keeps
+ * NaN out (octcubem_amd.ops.rank_counts raises).  Same code in the two builds of the library.
+ * -2, before any launch: a NULL pointer, n <= 0, C <= 0, a stride below C, n above 2^31 - 1 (a count can reach n), C above 65535. */
+int octmae_rank_counts(const float* scores, long long score_stride, const uint8_t* labels, long long label_stride, int* counts,
+                       long long n, int C, void* stream);
 
 /* ---- optimizer side --------------------------------------------------------------------------------
  * Multi-tensor tables: tensor_table = device array of {float* p, g, m, v; int64 n}; chunk_tensor/chunk_off map

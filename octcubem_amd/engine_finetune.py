@@ -4,9 +4,10 @@ mixup callable, forward, non-finite guard, ``loss_scaler(loss / accum_iter, clip
 zero_grad on step boundaries, min/max group LR logging, scalar loss all-reduce.
 
 Not reproduced: the per-iteration ``torch.cuda.synchronize()`` and logits printing (pipeline stalls with no numerical effect),
-the 2-D/3-D ``variable_joint`` and SLIViT reshapes (models outside SURVEY §8), and the CSV / confusion-matrix reporting of
-the reference's ``evaluate`` -- this one returns loss, top-1 accuracy and the gathered logits / targets for the caller's
-metric code.
+and the 2-D/3-D ``variable_joint`` and SLIViT reshapes (models outside SURVEY §8).  ``evaluate`` returns loss, top-1 accuracy and
+the gathered logits / targets for a caller with metric code of its own; ``evaluate_report`` is the reference's ``evaluate`` (:498-813)
+with its signature, its return value and its CSV files, the ranking metrics from the rank-count kernel (ops.rank_counts,
+octcubem_amd/metrics.py) in place of scikit-learn, and the confusion matrix as a CSV of integers in place of the pycm / matplotlib JPEG.
 
 Provenance, stated once: this file is a RESTATEMENT of the reference's host loop, written to be call-compatible with it -- same
 function signatures, same order of operations per iteration, same ``MetricLogger`` keys -- because it is the caller SURVEY section 8
@@ -14,12 +15,15 @@ function signatures, same order of operations per iteration, same ``MetricLogger
 optimizer, schedules) is this package's own."""
 from __future__ import annotations
 
+import csv
 import math
+import os
 from typing import Iterable, Optional
 
+import numpy as np
 import torch
 
-from . import lr_sched, misc
+from . import lr_sched, metrics, misc
 
 
 def train_one_epoch(model: torch.nn.Module, criterion: torch.nn.Module, data_loader: Iterable, optimizer: torch.optim.Optimizer,
@@ -88,3 +92,132 @@ def evaluate(data_loader: Iterable, model: torch.nn.Module, device: torch.device
     tg = torch.cat(targets_all)
     acc1 = float((logits.argmax(-1) == (tg if tg.dim() == 1 else tg.argmax(-1))).float().mean()) if n else float("nan")
     return {"loss": loss_sum / max(n, 1), "acc1": acc1, "logits": logits, "targets": tg}
+
+
+_REPORT_MODES = ("binary_cls", "multi_cls", "multi_label")
+_UNBUILT_ARGS = ("frame_inference_all", "return_embeddings", "variable_joint")
+METRICS_HEADER = ["acc", "balanced_acc", "sensitivity", "specificity", "precision", "auc_roc", "auc_pr", "F1", "mcc", "loss"]
+MACRO_HEADER = ["Accuracy", "ROC AUC", "Average Precision", "AUPRC", "F1 Score", "Balanced Acc", "MCC", "G-Mean", "Precision", "Recall",
+                "Sensitivity", "Specificity", "Micro AP", "Kappa", "Max F1", "loss"]
+_MACRO_KEYS = ("accuracy", "roc_auc", "AP", "auprc", "f1", "balanced_acc", "mcc", "G", "precision", "recall", "sensitivity", "specificity",
+               "micro_AP", "kappa", "max_f1")
+CLASS_HEADER = ["Accuracy", "ROC AUC", "Average Precision", "AUPRC", "F1 Score", "Balanced Acc", "MCC", "G-Mean", "precision", "recall",
+                "specificity", "sensitivity", "Max F1", "Kappa"]
+_CLASS_KEYS = ("accuracy", "roc_auc", "AP", "auprc", "f1", "balanced_acc", "mcc", "G", "precision", "recall", "specificity", "sensitivity",
+               "max_f1", "kappa")
+
+
+def _append_row(path: str, header, row):
+    """One row appended to a CSV, the header first when the file is empty."""
+    with open(path, mode="a", newline="", encoding="utf8") as f:
+        w = csv.writer(f)
+        if f.tell() == 0:
+            w.writerow(header)
+        w.writerow([float(v) for v in row])
+
+
+def _write_int_matrix(path: str, m):
+    with open(path, mode="w", newline="", encoding="utf8") as f:
+        csv.writer(f).writerows([[int(v) for v in r] for r in np.asarray(m)])
+
+
+@torch.no_grad()
+def evaluate_report(data_loader, model, device, task, epoch, mode, num_class, criterion=torch.nn.CrossEntropyLoss(),
+                    task_mode="binary_cls", disease_list=None, return_bal_acc=False, args=None):
+    """The reference's ``evaluate`` (engine_finetune.py:498-813) for ``task_mode`` binary_cls, multi_cls and multi_label: an eval-mode
+    pass over ``data_loader`` (batch[0] the input, batch[-1] the target), then the report under the directory ``task``.
+
+    Returns ``({"loss", "acc1"}, auc_roc, auc_pr)``, or ``({...}, auc_roc, (auc_pr, balanced_acc))`` with ``return_bal_acc``.  For
+    binary_cls / multi_cls ``auc_roc`` is the macro one-vs-rest AUROC of the softmax scores against the one-hot targets and ``auc_pr``
+    the macro AVERAGE PRECISION (the reference's variable of that name holds average_precision_score); for multi_label they are
+    ``macro["roc_auc"]`` and ``macro["auprc"]`` of ``metrics.misc_measures_multi_label`` on the sigmoid scores.  ``loss`` is the mean
+    over samples and ``acc1`` the top-1 fraction, both as ``evaluate`` above defines them.
+
+    Files: ``metrics_<mode>.csv`` (one row per call: METRICS_HEADER), or for multi_label ``macro_metrics_<mode>.csv`` (MACRO_HEADER) and
+    ``class_<i>_<name>_metrics_<mode>.csv`` per class (CLASS_HEADER; names from ``disease_list``, a dict or a sequence), the header
+    written when the file is empty; and, when ``mode`` starts with "test" and ``args.not_save_figs`` is not set,
+    ``confusion_matrix_<mode>_epoch_<epoch>.csv`` (integers, rows = true class, columns = predicted class) or per class of a
+    multi-label task ``confusion_matrix_<mode>_<i>_<name>_epoch_<epoch>.csv`` ([[tn, fp], [fn, tp]]).
+
+    Logits, scores, targets and the running sums of loss and top-1 stay on the device for the whole loop: no ``.item()`` or ``.cpu()``
+    per step, one synchronisation at the end.  The metrics cover what THIS rank's loader yields, as in the reference.
+    ``regression`` and ``multi_task*`` raise NotImplementedError; ``args.frame_inference_all`` / ``return_embeddings`` /
+    ``variable_joint`` must be unset or falsy."""
+    if task_mode not in _REPORT_MODES:
+        if task_mode == "regression" or str(task_mode).startswith("multi_task"):
+            raise NotImplementedError(f"evaluate_report: task_mode {task_mode!r} is not built (built: {', '.join(_REPORT_MODES)})")
+        raise ValueError(f"evaluate_report: unknown task_mode {task_mode!r}")
+    for name in _UNBUILT_ARGS:
+        assert not getattr(args, name, False), f"evaluate_report: args.{name} is not built"
+    os.makedirs(task, exist_ok=True)
+    device = torch.device(device)
+    float_targets = isinstance(criterion, torch.nn.BCEWithLogitsLoss)
+    model.eval()
+    scores_all, targets_all = [], []
+    loss_sum = torch.zeros((), dtype=torch.float64, device=device)
+    correct = torch.zeros((), dtype=torch.int64, device=device)
+    n = 0
+    for batch in misc.prefetched(data_loader, device, args, only=(0, 1)):
+        samples = batch[0].to(device, non_blocking=True)
+        targets = batch[-1].to(device, non_blocking=True)
+        out = model(samples)
+        with torch.autocast(device.type, enabled=False):
+            out = out.float()
+            loss = criterion(out, targets.float() if float_targets else targets)
+            scores = torch.sigmoid(out) if task_mode == "multi_label" else torch.softmax(out, dim=1)
+        bs = samples.shape[0]
+        loss_sum += loss.double() * bs
+        correct += (out.argmax(-1) == (targets if targets.dim() == 1 else targets.argmax(-1))).sum()
+        n += bs
+        scores_all.append(scores)
+        targets_all.append(targets)
+    if n == 0:
+        raise ValueError("evaluate_report: the loader yielded no sample")
+    scores, targets = torch.cat(scores_all), torch.cat(targets_all)
+    if scores.shape[1] != num_class:
+        raise ValueError(f"evaluate_report: the model has {scores.shape[1]} outputs, num_class is {num_class}")
+
+    if task_mode == "multi_label":
+        res = metrics.misc_measures_multi_label(targets, scores, threshold=0.5)
+        macro, classwise = res["macro"], res["classwise"]
+        stats = {"loss": float(loss_sum) / n, "acc1": int(correct) / n}
+        _append_row(os.path.join(task, f"macro_metrics_{mode}.csv"), MACRO_HEADER, [macro[k] for k in _MACRO_KEYS] + [stats["loss"]])
+        if disease_list is None:
+            disease_list = {i: str(i) for i in range(num_class)}
+        elif not isinstance(disease_list, dict):
+            disease_list = dict(enumerate(disease_list))
+        assert len(disease_list) == num_class
+        pred = (scores > 0.5).cpu().numpy()
+        true = (targets != 0).cpu().numpy()
+        for i, name in disease_list.items():
+            _append_row(os.path.join(task, f"class_{i}_{name}_metrics_{mode}.csv"), CLASS_HEADER, [classwise[k][i] for k in _CLASS_KEYS])
+            if mode.startswith("test") and not getattr(args, "not_save_figs", False):
+                t, p = true[:, i], pred[:, i]
+                _write_int_matrix(os.path.join(task, f"confusion_matrix_{mode}_{i}_{name}_epoch_{epoch}.csv"),
+                                  [[(~t & ~p).sum(), (~t & p).sum()], [(t & ~p).sum(), (t & p).sum()]])
+        print("Metrics - Acc: {:.4f} AUC-roc: {:.4f}, AP: {:4f}, AUC-pr: {:.4f} F1-score: {:.4f}, Max F1: {:.4f}, Balanced Acc: {:.4f}, "
+              "Kappa: {:.4f}, MCC: {:.4f}".format(macro["accuracy"], macro["roc_auc"], macro["AP"], macro["auprc"], macro["f1"],
+                                                  macro["max_f1"], macro["balanced_acc"], macro["kappa"], macro["mcc"]))
+        if return_bal_acc:
+            return stats, macro["roc_auc"], (macro["auprc"], macro["balanced_acc"])
+        return stats, macro["roc_auc"], macro["auprc"]
+
+    true_idx = targets.long()
+    pred_idx = scores.argmax(dim=1)
+    onehot = torch.nn.functional.one_hot(true_idx, num_classes=num_class).to(torch.uint8)
+    from . import ops
+    ranks = metrics.binary_rank_metrics(ops.rank_counts(scores, onehot), onehot)
+    ovr = metrics.multilabel_confusion(true_idx, pred_idx, num_class).cpu().numpy()
+    confusion = metrics.confusion_counts(true_idx, pred_idx, num_class).cpu().numpy()
+    stats = {"loss": float(loss_sum) / n, "acc1": int(correct) / n}
+    acc, sensitivity, specificity, precision, G, F1, mcc, balanced_acc = (float(v) for v in metrics.misc_measures(ovr))
+    auc_roc, auc_pr = float(ranks["roc_auc"].mean()), float(ranks["AP"].mean())
+    print("Metrics - Acc: {:.4f} Balanced-Acc: {:.4f} AUC-roc: {:.4f} AUC-pr: {:.4f} F1-score: {:.4f} MCC: {:.4f}".format(
+        acc, balanced_acc, auc_roc, auc_pr, F1, mcc))
+    _append_row(os.path.join(task, f"metrics_{mode}.csv"), METRICS_HEADER,
+                [acc, balanced_acc, sensitivity, specificity, precision, auc_roc, auc_pr, F1, mcc, stats["loss"]])
+    if mode.startswith("test") and not getattr(args, "not_save_figs", False):
+        _write_int_matrix(os.path.join(task, f"confusion_matrix_{mode}_epoch_{epoch}.csv"), confusion)
+    if return_bal_acc:
+        return stats, auc_roc, (auc_pr, balanced_acc)
+    return stats, auc_roc, auc_pr

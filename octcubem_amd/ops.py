@@ -589,6 +589,41 @@ def mae_compose(pred: torch.Tensor, imgs: torch.Tensor, mask: torch.Tensor, fram
     return out
 
 
+def rank_counts(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """int32 [n, C, 4] = {gt_all, gt_pos, ge_all, ge_pos} per sample i and class c: the samples j with scores[j, c] > scores[i, c], how
+    many of those are positive, and the same for >= (i counts itself).  AUROC, average precision and the precision-recall curve
+    follow exactly from them (octcubem_amd/metrics.py).  ``scores`` float32 [n, C], ``labels`` bool or uint8 [n, C] (!= 0 = positive);
+    both may be column slices of wider buffers (unit column stride, any row stride >= C).  IEEE comparisons: -0.0 ties with 0.0 and
+    +-inf are ordinary values; a NaN raises ValueError before the launch (scikit-learn raises there too, and a NaN would silently count
+    as zero).  That check reads one flag back from the device.  No autograd; no 16-bit operand, so autocast changes nothing."""
+    if not scores.is_cuda or not labels.is_cuda:
+        raise RuntimeError("rank_counts: expected GPU tensors (the HIP path has no CPU fallback)")
+    if scores.dtype != F32:
+        raise TypeError(f"rank_counts: scores must be float32, got {scores.dtype}")
+    if labels.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"rank_counts: labels must be bool or uint8, got {labels.dtype}")
+    if scores.dim() != 2 or labels.shape != scores.shape or scores.device != labels.device:
+        raise ValueError(f"rank_counts: expected scores and labels [n, C] on one device, got {tuple(scores.shape)} and {tuple(labels.shape)}")
+    n, C = scores.shape
+    if n < 1 or C < 1:
+        raise ValueError(f"rank_counts: empty input {tuple(scores.shape)}")
+    scores, labels = scores.detach(), labels.detach()
+    if labels.dtype == torch.bool:
+        labels = labels.view(torch.uint8)          # same bytes: a bool is stored as 0 / 1
+    for t, name in ((scores, "scores"), (labels, "labels")):
+        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
+            raise ValueError(f"rank_counts: {name} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
+    if bool(torch.isnan(scores).any()):
+        raise ValueError("rank_counts: scores contain NaN")
+    ss = scores.stride(0) if n > 1 else C
+    ls = labels.stride(0) if n > 1 else C
+    counts = torch.empty((n, C, 4), dtype=torch.int32, device=scores.device)
+    # algorithmic HBM bytes: scores and labels read once (the re-reads of the j stream hit the caches), the counts written once
+    _launch("rank_counts", 0.0, float(n * C * (4 + 1 + 16)),
+            lambda: call("octmae_rank_counts", scores.data_ptr(), ss, labels.data_ptr(), ls, counts.data_ptr(), n, C, _stream()))
+    return counts
+
+
 # optimistic (no running max) forward first, safe kernel as the device-side fallback.  Not in the half build: the un-normalised
 # P = exp2(s) of that kernel is an MFMA operand, and half ends at 65 504 = e^11.09 where bfloat16 has fp32's range (the online-max
 # kernel keeps P <= 2^8)
