@@ -37,8 +37,9 @@ extern "C" {
  * 15: octmae_volume_box, octmae_volume_resample (the volume transforms in front of the models, csrc/transform3d.hip).
  * 16: octmae_mae_compose (the reconstruction volumes of the validation pass, csrc/recon.hip).
  * 17: octmae_image_resample, octmae_image_resample_plan (the 2-D image transforms in front of the 2-D towers, csrc/image2d.hip).
- * 18: octmae_rank_counts (the rank counts behind AUROC / average precision of the fine-tune evaluation, csrc/metrics.hip). */
-#define OCTMAE_ABI_VERSION 18
+ * 18: octmae_rank_counts (the rank counts behind AUROC / average precision of the fine-tune evaluation, csrc/metrics.hip).
+ * 19: octmae_retrieval_ranks (the retrieval ranks of the COEM validation off f32 MFMA tiles, csrc/retrieval.hip). */
+#define OCTMAE_ABI_VERSION 19
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -386,6 +387,30 @@ int octmae_mae_compose(const float* pred, long long pred_batch_stride, const flo
  * -2, before any launch: a NULL pointer, n <= 0, C <= 0, a stride below C, n above 2^31 - 1 (a count can reach n), C above 65535. */
 int octmae_rank_counts(const float* scores, long long score_stride, const uint8_t* labels, long long label_stride, int* counts,
                        long long n, int C, void* stream);
+
+/* ---- retrieval ranks of the COEM validation (csrc/retrieval.hip) -------------------------------------
+ * retinal-COEM/src/training/train_retclip.py:409-469 ranks every sample's partner among all candidates by sorting the rows of the
+ * [n][m] logit matrix on the CPU.  Mean / median rank, R@k and the corrected variants need four integers per row; this entry point
+ * counts them off f32-input MFMA tiles of a . b^T and stores no score.
+ *   a       f32 [n][d], rows a_stride ELEMENTS apart (>= d);  b  f32 [m][d], rows b_stride elements apart (>= d)
+ *   s(i, j) the f32 chain acc = 0; for k = 0 .. d-1: acc = fmaf(a[i][k], b[j][k], acc)  (what v_mfma_f32_32x32x2_f32 computes, bit
+ *           for bit; symmetric in a and b);  t_i = s(i, target[i]), the same bits as the tile's value
+ *   target  int32 [n], a column in [0, m); NULL: target[i] = i (needs n == m)
+ *   keep    uint8 [m], != 0: the column takes part in the ranking; NULL: all
+ *   row_group int32 [n], col_group int32 [m]: both NULL or both given
+ *   out     int32 [n][4], contiguous:
+ *             0  #{ j kept, j != target[i] : s(i, j) >  t_i }
+ *             1  #{ j kept, j <  target[i] : s(i, j) == t_i }          0 + 1 = the target's place in a STABLE descending sort
+ *             2  #{ j : col_group[j] == row_group[i] and s(i, j) >= 0 }   (0 without groups)
+ *             3  #{ j : col_group[j] == row_group[i] }                    (0 without groups)
+ * IEEE comparisons; the caller keeps non-finite features out (octcubem_amd.ops.retrieval_ranks raises).  Deterministic: integer
+ * counts, combined across workgroups with integer atomics into the zeroed `out`.  Same code in the two builds of the library.
+ * -2: a NULL a / b / out, n, m or d <= 0, a stride below d, m above 2^31 - 1, target == NULL with n != m, one group pointer without
+ * the other (all before any launch), and a target that is no column of b or is not kept (found by a check launch whose flag is read
+ * back on `stream` -- one synchronisation, only when target or keep is given; `out` is left zeroed). */
+int octmae_retrieval_ranks(const float* a, long long a_stride, const float* b, long long b_stride, const int* target,
+                           const uint8_t* keep, const int* row_group, const int* col_group, int* out, long long n, long long m,
+                           int d, void* stream);
 
 /* ---- optimizer side --------------------------------------------------------------------------------
  * Multi-tensor tables: tensor_table = device array of {float* p, g, m, v; int64 n}; chunk_tensor/chunk_off map

@@ -361,3 +361,214 @@ def train_step(model, loss_fn, images, texts, optimizers, loss_scalers=None, cli
         o.step()
     clamp_logit_scale(model)
     return loss.detach()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# validation: retrieval ranks (training/train_retclip.py:243-469, train_retclip_3modalities.py:542-604)
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The reference moves the features to the CPU, forms the [N, N] logits there and argsorts every row twice (its own FIXME: "this does not
+# scale past small eval datasets").  Everything it reports follows from one integer per sample and direction -- the number of candidates
+# ranked before the true partner -- which ops.retrieval_ranks counts off f32 MFMA tiles of the feature product without storing it
+# (csrc/retrieval.hip).  The host finishes in float64 with the reference's own expressions.  ``ranks=`` replaces the kernel by any
+# function of the same signature (tests/retrieval_ref.py: numpy), as metrics.misc_measures_multi_label takes ``rank_counts=``.
+def _device_ranks(a, b, **kw):
+    if not (isinstance(a, torch.Tensor) and a.is_cuda):
+        raise RuntimeError("retrieval metrics: the ranks come from the HIP kernel (ops.retrieval_ranks), which has no CPU fallback: pass "
+                           "features on the device, or a ranks function")
+    from . import ops
+    return ops.retrieval_ranks(a, b, **kw)
+
+
+def _feat(x):
+    x = x.detach()
+    return x if x.dtype == torch.float32 else x.float()
+
+
+def _check_scale(name, logit_scale):
+    v = float(logit_scale)
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError(f"{name} must be finite and > 0, got {v}")
+    return v
+
+
+def _positions(ranks, pairs):
+    """[(a, b), ...] -> one int64 numpy array per pair: the place of sample i's partner (column i) among the rows of b under a stable
+    descending sort of the UNSCALED scores.  One device-to-host copy for all pairs together."""
+    cols = [torch.as_tensor(ranks(a, b))[:, :2].sum(dim=1) for a, b in pairs]
+    flat = torch.cat(cols).cpu().numpy().astype(np.int64)
+    return np.split(flat, np.cumsum([c.shape[0] for c in cols])[:-1])
+
+
+def _rank_summary(metrics, name, preds):
+    metrics[f"{name}_mean_rank"] = preds.mean() + 1
+    metrics[f"{name}_median_rank"] = np.floor(np.median(preds)) + 1
+    for k in [1, 5, 10]:
+        metrics[f"{name}_R@{k}"] = np.mean(preds < k)
+
+
+def get_metrics(image_features, text_features, logit_scale, ranks=None):
+    """train_retclip.get_metrics: ``{image_to_text, text_to_image}_{mean_rank, median_rank, R@1, R@5, R@10}``.  ``logit_scale`` is
+    checked (finite, > 0) and does not enter the ranking: a positive factor changes no order.  Ties resolve by column index."""
+    _check_scale("logit_scale", logit_scale)
+    ranks = ranks or _device_ranks
+    img, txt = _feat(image_features), _feat(text_features)
+    if img.dim() != 2 or img.shape != txt.shape:
+        raise ValueError(f"get_metrics: expected two [N, D] feature matrices, got {tuple(img.shape)} and {tuple(txt.shape)}")
+    metrics = {}
+    for name, preds in zip(("image_to_text", "text_to_image"), _positions(ranks, [(img, txt), (txt, img)])):
+        _rank_summary(metrics, name, preds)
+    return metrics
+
+
+def get_metrics_3modalities(image_features, text1_features, text2_features, logit_scale, logit_scale1, logit_scale2, t_weight1,
+                            t_weight2, ranks=None):
+    """train_retclip_3modalities.get_metrics_3modalities: the six directions among (image, text1, text2); every sample is ranked against
+    ALL candidates and the summary is taken over the samples whose modality is present (``t_weight > 0``; ``t_weight1 * t_weight2``
+    for the text1 / text2 pair).  A direction with no sample left raises ValueError."""
+    for nm, s in (("logit_scale", logit_scale), ("logit_scale1", logit_scale1), ("logit_scale2", logit_scale2)):
+        _check_scale(nm, s)
+    ranks = ranks or _device_ranks
+    img, t1, t2 = _feat(image_features), _feat(text1_features), _feat(text2_features)
+    if img.dim() != 2 or img.shape != t1.shape or img.shape != t2.shape:
+        raise ValueError(f"get_metrics_3modalities: expected three [N, D] feature matrices, got {tuple(img.shape)}, {tuple(t1.shape)}, "
+                         f"{tuple(t2.shape)}")
+    w1 = torch.as_tensor(t_weight1).detach().cpu().numpy().reshape(-1)
+    w2 = torch.as_tensor(t_weight2).detach().cpu().numpy().reshape(-1)
+    if w1.shape[0] != img.shape[0] or w2.shape[0] != img.shape[0]:
+        raise ValueError(f"get_metrics_3modalities: t_weight1 / t_weight2 need {img.shape[0]} entries, got {w1.shape[0]} and {w2.shape[0]}")
+    directions = (("image_to_text1", img, t1, w1), ("text1_to_image", t1, img, w1), ("image_to_text2", img, t2, w2),
+                  ("text2_to_image", t2, img, w2), ("text1_to_text2", t1, t2, w1 * w2), ("text2_to_text1", t2, t1, w1 * w2))
+    for name, _, _, w in directions:
+        if not (w > 0).any():
+            raise ValueError(f"get_metrics_3modalities: no sample with t_weight > 0 is left for {name}")
+    metrics = {}
+    for (name, _, _, w), preds in zip(directions, _positions(ranks, [(a, b) for _, a, b, _ in directions])):
+        _rank_summary(metrics, name, preds[w > 0])
+    return metrics
+
+
+def _label_ids(labels):
+    """labels of any hashable type -> (int ids in order of first occurrence [N], index of the LAST occurrence of each sample's label [N])."""
+    if isinstance(labels, (torch.Tensor, np.ndarray)):
+        labels = labels.tolist()
+    ids, last, out = {}, {}, []
+    for i, l in enumerate(labels):
+        k = ids.setdefault(l, len(ids))
+        last[k] = i
+        out.append(k)
+    ids_np = np.asarray(out, dtype=np.int32)
+    return ids_np, np.asarray([last[k] for k in out], dtype=np.int32)
+
+
+def get_corrected_metrics(image_features, text_features, logit_scale, labels, ranks=None):
+    """train_retclip.get_corrected_metrics for evaluation sets in which one report (``labels[i]``) belongs to several images.
+    Image-to-text: the sample's report ranked among the DISTINCT reports, each represented by its last occurrence (make_correct_labels).
+    Text-to-image: micro and macro recall of ``logit >= 0`` against "same label" (the reference thresholds f32 sigmoid(logit) at 0.5)."""
+    _check_scale("logit_scale", logit_scale)
+    ranks = ranks or _device_ranks
+    img, txt = _feat(image_features), _feat(text_features)
+    ids, target = _label_ids(labels)
+    if img.dim() != 2 or img.shape != txt.shape or ids.shape[0] != img.shape[0]:
+        raise ValueError(f"get_corrected_metrics: expected two [N, D] feature matrices and N labels, got {tuple(img.shape)}, "
+                         f"{tuple(txt.shape)} and {ids.shape[0]} labels")
+    keep = np.zeros(ids.shape[0], dtype=np.uint8)
+    keep[target] = 1
+    dev = img.device
+    group = torch.from_numpy(ids).to(dev)
+    out = torch.as_tensor(ranks(img, txt, target=torch.from_numpy(target).to(dev), keep=torch.from_numpy(keep).to(dev), row_group=group,
+                                col_group=group)).cpu().numpy().astype(np.int64)
+    metrics = {}
+    _rank_summary(metrics, "corrected_image_to_text", out[:, 0] + out[:, 1])
+    metrics["corrected_text_to_image_micro_recall"] = out[:, 2].sum() / out[:, 3].sum()
+    metrics["corrected_text_to_image_macro_recall"] = np.mean(out[:, 2] / out[:, 3])
+    return metrics
+
+
+def _eval_corrected_label(text_features, t=10 ** (-8)):
+    """evaluate's own get_corrected_label (train_retclip.py:257-263): 1 where two reports of the batch have the same features."""
+    f = text_features.detach()
+    d = torch.sqrt(((f.unsqueeze(1) - f.unsqueeze(0)) ** 2).sum(dim=-1))
+    return (d <= t).to(text_features.dtype)
+
+
+def evaluate(model, data, epoch, args, tb_writer=None):
+    """The validation half of train_retclip.evaluate: features of ``data['val'].dataloader`` stay ON THE DEVICE, the per-batch loss
+    (symmetric cross entropy, or BCE against the duplicate-report targets with ``args.correct_label``) is weighted by batch size and
+    summed on the device with one synchronisation at the end, and the retrieval metrics come from ``get_metrics``.  Returns ``{}``
+    off the main process or when validation is not due; otherwise the ten metrics plus ``val_loss``, ``epoch``, ``num_samples``.
+    Zero-shot evaluation and wandb are not part of this package."""
+    import json
+    import logging
+    import os
+    from . import misc
+    metrics = {}
+    if not misc.is_main_process():
+        return metrics
+    mm = getattr(args, "multimodal_type", "default")
+    if mm not in (None, "default"):
+        raise NotImplementedError(f"evaluate: multimodal_type {mm!r} is not supported (only 'default')")
+    val_frequency = getattr(args, "val_frequency", 0)
+    if not ("val" in data and (val_frequency and ((epoch % val_frequency) == 0 or epoch == getattr(args, "epochs", None)))):
+        return metrics
+    device = torch.device(getattr(args, "device", "cuda"))
+    model.eval()
+    dataloader = data["val"].dataloader
+    samples_per_val = getattr(dataloader, "num_samples", None)
+    correct_label = bool(getattr(args, "correct_label", 0))
+    return_metainfo = bool(getattr(args, "return_metainfo", False))
+    num_samples = 0
+    cumulative_loss = torch.zeros((), dtype=torch.float32, device=device)
+    all_image, all_text, all_scale, all_labels = [], [], [], []
+    logit_scale = None
+    with torch.no_grad():
+        for i, batch in enumerate(dataloader):
+            if return_metainfo:
+                images, texts, labels = batch
+                all_labels.extend(labels.tolist() if isinstance(labels, (torch.Tensor, np.ndarray)) else list(labels))
+            else:
+                images, texts = batch
+            images = images.to(device=device, non_blocking=True)
+            texts = texts.to(device=device, non_blocking=True)
+            image_features, text_features, logit_scale = model(images, texts)
+            with torch.autocast(device_type=device.type, enabled=False):
+                image_features, text_features = image_features.float(), text_features.float()
+                logit_scale = logit_scale.float().mean()
+                logits_per_image = logit_scale * image_features @ text_features.t()
+                logits_per_text = logits_per_image.t()
+                batch_size = images.shape[0]
+                if correct_label:
+                    targets = _eval_corrected_label(text_features)
+                    total_loss = (F.binary_cross_entropy_with_logits(logits_per_image, targets)
+                                  + F.binary_cross_entropy_with_logits(logits_per_text, targets)) / 2
+                else:
+                    targets = torch.arange(batch_size, device=device).long()
+                    total_loss = (F.cross_entropy(logits_per_image, targets) + F.cross_entropy(logits_per_text, targets)) / 2
+                cumulative_loss += total_loss * batch_size
+            all_image.append(image_features)
+            all_text.append(text_features)
+            all_scale.append(logit_scale)
+            num_samples += batch_size
+            if (i % 100) == 0:
+                logging.info(f"Eval Epoch: {epoch} [{num_samples} / {samples_per_val}]")
+        if num_samples == 0:
+            raise ValueError("evaluate: the validation loader is empty")
+        image_all, text_all = torch.cat(all_image), torch.cat(all_text)
+        val_metrics = get_metrics(image_features=image_all, text_features=text_all, logit_scale=logit_scale)
+        loss = cumulative_loss / num_samples
+        metrics.update({**{k: float(v) for k, v in val_metrics.items()}, "val_loss": loss.item(), "epoch": epoch,
+                        "num_samples": num_samples})
+    logging.info(f"Eval Epoch: {epoch} " + "\t".join([f"{k}: {round(v, 4):.4f}" for k, v in metrics.items()]))
+    if getattr(args, "save_logs", False):
+        for name, val in metrics.items():
+            if tb_writer is not None:
+                tb_writer.add_scalar(f"val/{name}", val, epoch)
+        with open(os.path.join(args.checkpoint_path, "results.jsonl"), "a+") as f:
+            f.write(json.dumps(metrics))
+            f.write("\n")
+        if getattr(args, "save_retrieval_results", False):
+            arrays = {"image_features": image_all.cpu().numpy(), "text_features": text_all.cpu().numpy(),
+                      "logit_scale": torch.stack(all_scale).cpu().numpy()}
+            if all_labels:
+                arrays["labels"] = np.asarray(all_labels)
+            np.savez(os.path.join(args.checkpoint_path, f"retrieval_results_{epoch}.npz"), **arrays)
+    return metrics

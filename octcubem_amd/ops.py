@@ -624,6 +624,79 @@ def rank_counts(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return counts
 
 
+def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                    row_group: Optional[torch.Tensor] = None, col_group: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [n, 4] per row i of ``a`` float32 [n, d] against the rows of ``b`` float32 [m, d], with s(i, j) the f32 fmaf chain over k
+    (f32-input MFMA tiles, csrc/retrieval.hip; the [n, m] matrix is never stored) and t_i = s(i, target[i]):
+
+      0  the kept columns j != target[i] with s(i, j) > t_i        1  the kept columns j < target[i] with s(i, j) == t_i
+      2  the columns with col_group[j] == row_group[i], s(i, j) >= 0   3  the columns with col_group[j] == row_group[i]
+
+    ``[:, 0] + [:, 1]`` is the target's place under a stable descending sort.  ``target`` int32 [n] (None: the diagonal, needs n == m),
+    ``keep`` bool / uint8 [m] (None: every column), ``row_group`` int32 [n] and ``col_group`` int32 [m] (both or neither; without them
+    columns 2 and 3 are 0).  ``a`` and ``b`` may be slices of wider buffers (unit column stride, any row stride >= d).  Non-finite
+    features raise ValueError before the launch (that check reads one flag back from the device; a target that is not kept is refused
+    the same way).  No autograd; no 16-bit operand, so autocast changes nothing."""
+    name = "retrieval_ranks"
+    for t, nm in ((a, "a"), (b, "b"), (target, "target"), (keep, "keep"), (row_group, "row_group"), (col_group, "col_group")):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name}: {nm} must be a GPU tensor (the HIP path has no CPU fallback)")
+    for t, nm in ((a, "a"), (b, "b")):
+        if t.dtype != F32:
+            raise TypeError(f"{name}: {nm} must be float32, got {t.dtype}")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.device != b.device:
+        raise ValueError(f"{name}: expected a [n, d] and b [m, d] on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, d = a.shape
+    m = b.shape[0]
+    if n < 1 or m < 1 or d < 1:
+        raise ValueError(f"{name}: empty input {tuple(a.shape)} / {tuple(b.shape)}")
+    if m > 2 ** 31 - 1:
+        raise ValueError(f"{name}: b has {m} rows, a count must fit int32")
+    a, b = a.detach(), b.detach()
+    for t, nm, rows in ((a, "a", n), (b, "b", m)):
+        if (d > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < d):
+            raise ValueError(f"{name}: {nm} needs unit column stride and a row stride >= {d}, got strides {tuple(t.stride())}")
+    if target is None and n != m:
+        raise ValueError(f"{name}: without target the partner of row i is column i, which needs n == m; got n={n}, m={m}")
+    if (row_group is None) != (col_group is None):
+        raise ValueError(f"{name}: row_group and col_group are given together or not at all")
+    for t, nm, rows in ((target, "target", n), (row_group, "row_group", n), (col_group, "col_group", m)):
+        if t is None:
+            continue
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name}: {nm} must be int32, got {t.dtype}")
+        if tuple(t.shape) != (rows,) or t.device != a.device:
+            raise ValueError(f"{name}: {nm} must be [{rows}] on {a.device}, got {tuple(t.shape)} on {t.device}")
+    if keep is not None:
+        if keep.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{name}: keep must be bool or uint8, got {keep.dtype}")
+        if tuple(keep.shape) != (m,) or keep.device != a.device:
+            raise ValueError(f"{name}: keep must be [{m}] on {a.device}, got {tuple(keep.shape)} on {keep.device}")
+        keep = keep.detach().contiguous()
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+    target, row_group, col_group = (None if t is None else t.detach().contiguous() for t in (target, row_group, col_group))
+    # one flag for every host-side refusal that needs the data: a single read-back
+    bad = torch.stack([(~torch.isfinite(a)).any(), (~torch.isfinite(b)).any(),
+                       ((target < 0) | (target >= m)).any() if target is not None else a.new_zeros((), dtype=torch.bool)]).tolist()
+    if bad[0] or bad[1]:
+        raise ValueError(f"{name}: {'a' if bad[0] else 'b'} contains non-finite values")
+    if bad[2]:
+        raise ValueError(f"{name}: target must lie in [0, {m})")
+    if keep is not None:
+        kept = keep[target.long()] if target is not None else keep
+        if not bool((kept != 0).all()):
+            raise ValueError(f"{name}: every target must be a kept column")
+    sa = a.stride(0) if n > 1 else d
+    sb = b.stride(0) if m > 1 else d
+    out = torch.empty((n, 4), dtype=torch.int32, device=a.device)
+    # algorithmic HBM bytes: a and b read once (the re-reads per tile hit the caches), the counts written once
+    _launch(name, 2.0 * n * m * d, float(4 * (n + m) * d + 16 * n),
+            lambda: call("octmae_retrieval_ranks", a.data_ptr(), sa, b.data_ptr(), sb, _p(target), _p(keep), _p(row_group), _p(col_group),
+                         out.data_ptr(), n, m, d, _stream()))
+    return out
+
+
 # optimistic (no running max) forward first, safe kernel as the device-side fallback.  Not in the half build: the un-normalised
 # P = exp2(s) of that kernel is an MFMA operand, and half ends at 65 504 = e^11.09 where bfloat16 has fp32's range (the online-max
 # kernel keeps P <= 2^8)
