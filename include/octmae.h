@@ -38,8 +38,9 @@ extern "C" {
  * 16: octmae_mae_compose (the reconstruction volumes of the validation pass, csrc/recon.hip).
  * 17: octmae_image_resample, octmae_image_resample_plan (the 2-D image transforms in front of the 2-D towers, csrc/image2d.hip).
  * 18: octmae_rank_counts (the rank counts behind AUROC / average precision of the fine-tune evaluation, csrc/metrics.hip).
- * 19: octmae_retrieval_ranks (the retrieval ranks of the COEM validation off f32 MFMA tiles, csrc/retrieval.hip). */
-#define OCTMAE_ABI_VERSION 19
+ * 19: octmae_retrieval_ranks (the retrieval ranks of the COEM validation off f32 MFMA tiles, csrc/retrieval.hip).
+ * 20: octmae_mix_batch (mixup / cutmix of a fine-tune batch in place, csrc/mixup.hip). */
+#define OCTMAE_ABI_VERSION 20
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -411,6 +412,22 @@ int octmae_rank_counts(const float* scores, long long score_stride, const uint8_
 int octmae_retrieval_ranks(const float* a, long long a_stride, const float* b, long long b_stride, const int* target,
                            const uint8_t* keep, const int* row_group, const int* col_group, int* out, long long n, long long m,
                            int d, void* stream);
+
+/* ---- mixup / cutmix of a fine-tune batch (csrc/mixup.hip) ---------------------------------------------
+ * timm.data.Mixup's three modes on the device, in place, in one launch; the decisions are the host's (octcubem_amd/mixup.py).
+ *   x     f32 [B][S], contiguous, B even; S = C (T) H W, the box is taken over the last two dimensions (H, W) of every plane
+ *   kind  int32 [B]: 0 = sample untouched (neither read nor written on its own account), 1 = mixup, 2 = cutmix
+ *   lam, oml  f32 [B]: kind 1 gives x[i] = x[i] * lam[i] + x0[j] * oml[i], j = B - 1 - i, x0 the batch before the launch; each product
+ *         rounded to fp32 on its own, then the sum: bit-equal to torch's mul followed by add.  oml is the host's 1 - lam.
+ *   box   int32 [B][4] = yl, yh, xl, xh: kind 2 gives x[i][.., yl:yh, xl:xh] = x0[j][.., yl:yh, xl:xh]; nothing outside the box is
+ *         loaded or stored for it.  A box is clamped into [0, H] x [0, W] on the device (the caller refuses one outside it).
+ * Both samples of a pair are handled by the same threads, originals loaded before either store: no copy of the batch, and the two
+ * may differ in kind, lam and box (timm's elem mode).  16-byte accesses where x[i] and x[j] share their phase against a 16-byte
+ * line, scalar ones at the ends and otherwise; any S, W and box.  All tables are DEVICE pointers.  Same code in the two builds.
+ * -1, before any launch: a NULL pointer, B odd or <= 0, S, H or W <= 0, H * W not dividing S, x not 4-byte aligned.
+ * -2: S above 2^30 elements, more than 65535 pairs. */
+int octmae_mix_batch(float* x, const int* kind, const float* lam, const float* oml, const int* box, int B, long long S, int H, int W,
+                     void* stream);
 
 /* ---- optimizer side --------------------------------------------------------------------------------
  * Multi-tensor tables: tensor_table = device array of {float* p, g, m, v; int64 n}; chunk_tensor/chunk_off map

@@ -4,5 +4,6 @@ Only what the path needs: HIP kernels + C ABI (csrc/, liboctmae.so), and the hos
 reference's Python interface for this path (video_vit, models_mae, misc, lr_sched, engine_pretrain).
 """
 from . import _lib  # noqa: F401  (does not load the shared library until first use)
+from .mixup import Mixup  # noqa: F401  (the fine-tune loop's mixup_fn; host decisions + one launch of csrc/mixup.hip)
 
-__all__ = ["models_mae", "video_vit", "misc", "lr_sched", "engine_pretrain", "optim", "parallel", "ops"]
+__all__ = ["models_mae", "video_vit", "misc", "lr_sched", "engine_pretrain", "optim", "parallel", "ops", "Mixup"]

@@ -14,6 +14,7 @@ from __future__ import annotations
 import os
 from typing import Callable, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from ._lib import OctmaeError, call, load
@@ -695,6 +696,75 @@ def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Ten
             lambda: call("octmae_retrieval_ranks", a.data_ptr(), sa, b.data_ptr(), sb, _p(target), _p(keep), _p(row_group), _p(col_group),
                          out.data_ptr(), n, m, d, _stream()))
     return out
+
+
+def mix_tables(kind, lam, oml, box, Bn: int, H: int, W: int):
+    """The host tables of ``mix_batch`` checked and brought to their device types: (kind int32 [B], lam f32 [B], oml f32 [B],
+    box int32 [B, 4]).  ValueError for a wrong length, a kind outside {0, 1, 2}, or a cutmix box (yl, yh, xl, xh) that does not
+    satisfy 0 <= yl <= yh <= H and 0 <= xl <= xh <= W.  Needs no GPU."""
+    name = "mix_batch"
+    kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(-1)
+    lam = np.ascontiguousarray(lam, dtype=np.float32).reshape(-1)
+    oml = np.ascontiguousarray(oml, dtype=np.float32).reshape(-1)
+    box = np.ascontiguousarray(box, dtype=np.int32)
+    if kind.shape != (Bn,) or lam.shape != (Bn,) or oml.shape != (Bn,) or box.shape != (Bn, 4):
+        raise ValueError(f"{name}: kind, lam, oml must have {Bn} entries and box [{Bn}, 4], got {kind.shape}, {lam.shape}, {oml.shape}, "
+                         f"{box.shape}")
+    if ((kind < 0) | (kind > 2)).any():
+        raise ValueError(f"{name}: kind must be 0 (untouched), 1 (mixup) or 2 (cutmix)")
+    b = box[kind == 2]
+    if ((b[:, 0] < 0) | (b[:, 0] > b[:, 1]) | (b[:, 1] > H) | (b[:, 2] < 0) | (b[:, 2] > b[:, 3]) | (b[:, 3] > W)).any():
+        raise ValueError(f"{name}: a cutmix box (yl, yh, xl, xh) must satisfy 0 <= yl <= yh <= {H} and 0 <= xl <= xh <= {W}")
+    return kind, lam, oml, box
+
+
+def mix_bytes(kind, box, S: int, H: int, W: int) -> float:
+    """The bytes one ``mix_batch`` launch moves: a pair with a mixing side reads both samples and writes each side that mixes (and the
+    partner's box where that side cuts); a pair that only cuts reads and writes its boxes, in every plane; kind 0 moves nothing."""
+    Bn = len(kind)
+    area = np.where(kind == 2, (box[:, 1] - box[:, 0]).astype(np.int64) * (box[:, 3] - box[:, 2]), 0) * (S // (H * W))
+    ki, kj = kind[:Bn // 2], kind[::-1][:Bn // 2]
+    ai, aj = area[:Bn // 2], area[::-1][:Bn // 2]
+    full = (ki == 1) | (kj == 1)
+    return 4.0 * float(np.where(full, 2 * S + np.where(ki == 1, S, ai) + np.where(kj == 1, S, aj), 2 * (ai + aj)).sum())
+
+
+def mix_batch(x: torch.Tensor, kind, lam, oml, box, H: int, W: int) -> torch.Tensor:
+    """Mixup / cutmix of the contiguous float32 GPU batch ``x`` [B, ..., H, W] in place, one launch (csrc/mixup.hip); returns ``x``.
+    Per sample i, with partner j = B - 1 - i and x0 the batch before the call: ``kind[i]`` 0 leaves it untouched, 1 gives
+    ``x[i] = x[i] * lam[i] + x0[j] * oml[i]`` (each product rounded on its own: bit-equal to torch's mul and add), 2 gives
+    ``x[i][..., yl:yh, xl:xh] = x0[j][..., yl:yh, xl:xh]`` with ``box[i] = (yl, yh, xl, xh)`` over the last two dimensions.  ``kind``,
+    ``lam``, ``oml`` and ``box`` are HOST tables (sequences or numpy arrays of length B; [B, 4] for the boxes): they are checked
+    (``mix_tables``), packed and uploaded in one copy from pinned memory, without a device synchronisation.  A wrong table raises
+    ValueError before the launch.  No autograd; no 16-bit operand, so autocast changes nothing."""
+    name = "mix_batch"
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError(f"{name}: x must be a GPU tensor (the HIP path has no CPU fallback)")
+    if x.dtype != F32:
+        raise TypeError(f"{name}: x must be float32, got {x.dtype}")
+    if x.dim() < 2 or not x.is_contiguous():
+        raise ValueError(f"{name}: x must be a contiguous [B, ..., H, W] tensor, got {tuple(x.shape)} with strides {tuple(x.stride())}")
+    Bn = x.shape[0]
+    S = x.numel() // max(Bn, 1)
+    H, W = int(H), int(W)
+    if Bn < 2 or Bn % 2 or H < 1 or W < 1 or S < 1 or S % (H * W):
+        raise ValueError(f"{name}: needs an even batch of samples that are whole [{H}, {W}] planes, got {tuple(x.shape)}")
+    kind, lam, oml, box = mix_tables(kind, lam, oml, box, Bn, H, W)
+    if not kind.any():
+        return x                                        # nothing to do: no upload, no launch
+    # one table, one copy: kind | lam | oml | box as 7 B 32-bit words in pinned memory (the caching host allocator keeps the block
+    # until the copy has run)
+    host = torch.empty(7 * Bn, dtype=torch.int32, pin_memory=True)
+    h = host.numpy()
+    h[:Bn] = kind
+    h[Bn:2 * Bn] = lam.view(np.int32)
+    h[2 * Bn:3 * Bn] = oml.view(np.int32)
+    h[3 * Bn:] = box.reshape(-1)
+    dev = host.to(x.device, non_blocking=True)
+    base = dev.data_ptr()
+    _launch(name, 0.0, mix_bytes(kind, box, S, H, W),
+            lambda: call("octmae_mix_batch", x.data_ptr(), base, base + 4 * Bn, base + 8 * Bn, base + 12 * Bn, Bn, S, H, W, _stream()))
+    return x
 
 
 # optimistic (no running max) forward first, safe kernel as the device-side fallback.  Not in the half build: the un-normalised
