@@ -18,6 +18,7 @@ if torch.cuda.is_available():
     from octcubem_amd import ops, optim as foptim
     from octcubem_amd._lib import call
 from oracle import mae3d_ref as O
+from tests import gemm_elem as GE
 
 DEV = "cuda"
 BF16 = ops.BF16 if torch.cuda.is_available() else torch.bfloat16   # the library's 16-bit operand type (OCTMAE_LIB)
@@ -232,6 +233,12 @@ def test_gemm_dgrad_and_wgrad(M, N, K, tile_variant):
     cs_at = cs0.clone()                                     # epilogue 4 of octmae_gemm_bf16 with a C2 vector: fp32 atomics
     dxg3 = ops.linear_dgrad(dy, w, pre=pre, colsum=cs_at, atomic_colsum=True)
     assert torch.equal(dxg3, dxg) and rel(cs_at, cs0.double() + dxg.double().sum(0)) < 2e-5
+    # ... and per column (tests/gemm_elem.py): a norm over the vector hides a slab missing from one column
+    dxd = dxg.double().cpu()
+    cs_bound = (M + 8) * GE.EPS32 * (cs0.double().cpu().abs() + dxd.abs().sum(0))
+    for name, got in (("workspace", cs), ("atomic", cs_at)):
+        r, at = GE.worst(got, cs0.double().cpu() + dxd.sum(0), cs_bound)
+        assert r <= 1.0, f"{tile_variant}: column sum ({name}) {r:.2f} x its bound at column {at}"
     gw0 = torch.randn(N, K, generator=g).to(DEV)
     gw = gw0.clone()
     ops.linear_wgrad_accum(dy, x, gw)
@@ -241,9 +248,12 @@ def test_gemm_dgrad_and_wgrad(M, N, K, tile_variant):
     ops._gemm(dy, x, gw2, N, K, M, N, K, K, 1, 1, ops.EPI_ACCUM, splitk=1)   # deterministic single-slice path
     assert rel(gw2, gw_ref) < 1e-5
     gw3, gb3 = gw0.clone(), torch.randn(N, generator=g).to(DEV)        # bias gradient from the dY tiles of the same kernel
-    gb_ref = gb3.double() + dy.double().sum(0)
+    gb_ref, gb0_abs = gb3.double() + dy.double().sum(0), gb3.double().abs()
     ops.linear_wgrad_accum(dy, x, gw3, gb3)
     assert rel(gw3, gw_ref) < 1e-5 and rel(gb3, gb_ref) < 2e-5
+    # per column (the weight gradient itself is held per element in tests/test_gpu_gemm_elements.py)
+    r, at = GE.worst(gb3, gb_ref, (M + _auto_wgrad_slices(N, K, M) + 4) * GE.EPS32 * (gb0_abs + dy.double().abs().sum(0)).cpu())
+    assert r <= 1.0, f"{tile_variant}: bias gradient {r:.2f} x its bound at column {at}"
 
 
 @pytest.mark.parametrize("M,N,K", [(1281, 512, 256), (600, 4096, 256), (130, 768, 512), (2562, 1024, 1024)])
@@ -272,6 +282,12 @@ def test_stored_gelu_prime_epilogues(M, N, K, tile_variant):
     exact = (dy.double() @ w.double()) * pk.grad
     assert rel(dx_a, exact) < 4e-3 and rel(dx_b, exact) < 5e-3 and rel(dx_b, dx_a) < 4e-3
     assert rel(cs_b, dx_b.double().sum(0)) < 2e-5 and rel(cs_b, cs_a) < 4e-3
+    for name, got, dxv in (("gelu' evaluated", cs_a, dx_a), ("gelu' stored", cs_b, dx_b)):      # per column, of the stored dx
+        dxd = dxv.double().cpu()
+        r, at = GE.worst(got, dxd.sum(0), (M + 8) * GE.EPS32 * dxd.abs().sum(0))
+        assert r <= 1.0, f"{tile_variant}: column sum ({name}) {r:.2f} x its bound at column {at}"
+    r, at = GE.worst(dg, xg.grad, GE.dgelu_bounds(pre, 2.0 ** -12 if BF16 == torch.float16 else 2.0 ** -9, torch.finfo(BF16).tiny)[1])
+    assert r <= 1.0, f"{tile_variant}: stored gelu' {r:.2f} x (one rounding + 1e-6) at element {at}"
     dx_c = ops.linear_dgrad(dy, w, pre=stored, pre_is_dgelu=True)   # octmae_gemm_bf16's epilogue 4 without the column sums
     assert torch.equal(dx_c, dx_b)
 
