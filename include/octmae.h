@@ -39,8 +39,9 @@ extern "C" {
  * 17: octmae_image_resample, octmae_image_resample_plan (the 2-D image transforms in front of the 2-D towers, csrc/image2d.hip).
  * 18: octmae_rank_counts (the rank counts behind AUROC / average precision of the fine-tune evaluation, csrc/metrics.hip).
  * 19: octmae_retrieval_ranks (the retrieval ranks of the COEM validation off f32 MFMA tiles, csrc/retrieval.hip).
- * 20: octmae_mix_batch (mixup / cutmix of a fine-tune batch in place, csrc/mixup.hip). */
-#define OCTMAE_ABI_VERSION 20
+ * 20: octmae_mix_batch (mixup / cutmix of a fine-tune batch in place, csrc/mixup.hip).
+ * 21: octmae_rank_counts_masked (rank counts over a per-column population: the multi-task evaluation, csrc/metrics.hip). */
+#define OCTMAE_ABI_VERSION 21
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -388,6 +389,17 @@ int octmae_mae_compose(const float* pred, long long pred_batch_stride, const flo
  * -2, before any launch: a NULL pointer, n <= 0, C <= 0, a stride below C, n above 2^31 - 1 (a count can reach n), C above 65535. */
 int octmae_rank_counts(const float* scores, long long score_stride, const uint8_t* labels, long long label_stride, int* counts,
                        long long n, int C, void* stream);
+
+/* OCTCube/engine_finetune.py:130-157 (misc_measures_multi_task): every task ranks its own subset of the samples -- those that carry
+ * the shared "normal" label or the task's label -- which the reference selects by boolean indexing on the CPU before one scikit-learn
+ * call per task.  Here the subset is a per-sample, per-column mask and all tasks are counted in one launch:
+ *   valid   uint8 [n][C], != 0 = the sample belongs to column c's population, rows valid_stride elements apart (>= C)
+ *   counts[i][c] as octmae_rank_counts, over the j with valid[j][c] != 0 only, for an i with valid[i][c] != 0; {0, 0, 0, 0} for an i
+ *                outside the population (every byte of counts is written).
+ * Everything else -- strides, IEEE comparisons, the caller keeping NaN out of VALID positions, the same code in the two builds -- as
+ * octmae_rank_counts.  -2, before any launch: the conditions of octmae_rank_counts, a NULL valid, valid_stride below C. */
+int octmae_rank_counts_masked(const float* scores, long long score_stride, const uint8_t* labels, long long label_stride,
+                              const uint8_t* valid, long long valid_stride, int* counts, long long n, int C, void* stream);
 
 /* ---- retrieval ranks of the COEM validation (csrc/retrieval.hip) -------------------------------------
  * retinal-COEM/src/training/train_retclip.py:409-469 ranks every sample's partner among all candidates by sorting the rows of the

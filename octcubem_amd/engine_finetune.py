@@ -12,7 +12,10 @@ octcubem_amd/metrics.py) in place of scikit-learn, and the confusion matrix as a
 Provenance, stated once: this file is a RESTATEMENT of the reference's host loop, written to be call-compatible with it -- same
 function signatures, same order of operations per iteration, same ``MetricLogger`` keys -- because it is the caller SURVEY section 8
 (R14 / N1, N3) requires and the reference's drivers import it by name.  It holds no kernel logic; everything it calls (models, scaler,
-optimizer, schedules) is this package's own."""
+optimizer, schedules) is this package's own.
+
+``evaluate_task_report`` is that ``evaluate`` for all five task modes: the three of ``evaluate_report``, ``multi_task*`` (per-task
+metrics over per-task populations from ops.rank_counts_masked, metrics.misc_measures_multi_task) and ``regression``."""
 from __future__ import annotations
 
 import csv
@@ -23,7 +26,7 @@ from typing import Iterable, Optional
 import numpy as np
 import torch
 
-from . import lr_sched, metrics, misc
+from . import losses, lr_sched, metrics, misc
 
 
 def train_one_epoch(model: torch.nn.Module, criterion: torch.nn.Module, data_loader: Iterable, optimizer: torch.optim.Optimizer,
@@ -37,6 +40,9 @@ def train_one_epoch(model: torch.nn.Module, criterion: torch.nn.Module, data_loa
     optimizer.zero_grad()
     n_iter = len(data_loader)
     float_targets = isinstance(criterion, torch.nn.BCEWithLogitsLoss) or getattr(args, "task_mode", "") == "regression"
+    # the reference's multi_task_loss (:45-70, called at :443): one two-class problem per task out of multi-label targets
+    multi_task = (str(getattr(args, "task_mode", "")).startswith("multi_task")
+                  and isinstance(criterion, losses.WeightedLabelSmoothingCrossEntropy))
     for data_iter_step, (samples, targets) in enumerate(metric_logger.log_every(misc.prefetched(data_loader, device, args, only=(0, 1)), print_freq, header)):
         if data_iter_step % accum_iter == 0:
             lr_sched.adjust_learning_rate(optimizer, data_iter_step / n_iter + epoch, args)
@@ -47,7 +53,7 @@ def train_one_epoch(model: torch.nn.Module, criterion: torch.nn.Module, data_loa
         if mixup_fn is not None:
             samples, targets = mixup_fn(samples, targets)
         outputs = model(samples)
-        loss = criterion(outputs, targets)
+        loss = losses.multi_task_loss(outputs, targets, criterion, args.task_mode) if multi_task else criterion(outputs, targets)
         loss_value = loss.item()
         if not math.isfinite(loss_value):
             print("Loss is {}, stopping training".format(loss_value))
@@ -141,8 +147,9 @@ def evaluate_report(data_loader, model, device, task, epoch, mode, num_class, cr
 
     Logits, scores, targets and the running sums of loss and top-1 stay on the device for the whole loop: no ``.item()`` or ``.cpu()``
     per step, one synchronisation at the end.  The metrics cover what THIS rank's loader yields, as in the reference.
-    ``regression`` and ``multi_task*`` raise NotImplementedError; ``args.frame_inference_all`` / ``return_embeddings`` /
-    ``variable_joint`` must be unset or falsy."""
+    ``regression`` and ``multi_task*`` raise NotImplementedError here: ``evaluate_task_report`` below serves them and hands the three
+    modes of this function on unchanged, so a driver binds that one as ``evaluate``.  ``args.frame_inference_all`` /
+    ``return_embeddings`` / ``variable_joint`` must be unset or falsy."""
     if task_mode not in _REPORT_MODES:
         if task_mode == "regression" or str(task_mode).startswith("multi_task"):
             raise NotImplementedError(f"evaluate_report: task_mode {task_mode!r} is not built (built: {', '.join(_REPORT_MODES)})")
@@ -221,3 +228,107 @@ def evaluate_report(data_loader, model, device, task, epoch, mode, num_class, cr
     if return_bal_acc:
         return stats, auc_roc, (auc_pr, balanced_acc)
     return stats, auc_roc, auc_pr
+
+
+REGRESSION_HEADER = ["Pearsonr", "R\u00b2", "ExplainedVariance", "MSE", "MAE", "R2", "Loss"]
+_REGRESSION_KEYS = ("pearsonr", "r2", "explained_variance", "mse", "mae", "R2", "loss")
+
+
+@torch.no_grad()
+def evaluate_task_report(data_loader, model, device, task, epoch, mode, num_class, criterion=torch.nn.CrossEntropyLoss(),
+                         task_mode="binary_cls", disease_list=None, return_bal_acc=False, args=None):
+    """The reference's ``evaluate`` (engine_finetune.py:498-813) for all five task modes, the function a driver binds as ``evaluate``.
+    ``binary_cls``, ``multi_cls`` and ``multi_label`` go to ``evaluate_report`` unchanged; an unknown mode raises ValueError;
+    ``args.frame_inference_all`` / ``return_embeddings`` / ``variable_joint`` must be unset or falsy.
+
+    ``multi_task*`` (targets [n, T + 1], column 0 the shared "normal" label; ``num_class`` model outputs: 2T for
+    'multi_task_default', T + 1 otherwise): returns ``({"loss", "acc1"}, macro roc_auc, macro auprc)`` of
+    ``metrics.misc_measures_multi_task`` on the logits, ``acc1`` the macro accuracy as in the reference, and with ``return_bal_acc``
+    ``(..., (auprc, balanced_acc))``.  Logits and targets stay on the device for the whole loop, one synchronisation at the end.
+    Files: ``macro_metrics_<mode>.csv`` (MACRO_HEADER), ``class_<i+1>_<name>_metrics_<mode>.csv`` per task (CLASS_HEADER) and, when
+    ``mode`` starts with "test" and ``args.not_save_figs`` is not set, ``confusion_matrix_<mode>_<i+1>_<name>_epoch_<epoch>.csv``
+    ([[tn, fp], [fn, tp]] of the task over its own population).  Names: ``disease_list[args.multi_task_idx[i]]`` when
+    ``args.multi_task_idx`` is given, else ``disease_list[i + 1]`` (without a list, ``str(i + 1)``).
+    Two departures from the reference, both on purpose.  The loss: with ``WeightedLabelSmoothingCrossEntropy`` it is
+    ``losses.multi_task_loss`` of ALL gathered logits and targets as one batch (the loss the mode trains, whose per-task means do not
+    split over batches); the reference calls the criterion on the unsplit [B, 2T] / [B, T + 1] pair, which any other criterion still
+    gets here, averaged over samples.  The confusion matrices: thresholded task softmax scores over the task's population; the
+    reference thresholds raw logit columns of all samples.
+
+    ``regression``: column 0 of a 2-D target with ``output[:, 0]``, both flattened; ``metrics.regression_measures`` in float64 on the
+    host (ValueError for constant targets or predictions).  Appends ``regression_metrics_<mode>.csv`` (REGRESSION_HEADER, four
+    decimals as in the reference) and returns the flat dict ``pearsonr, r2, explained_variance, mse, mae, R2, loss``, ``loss`` the
+    mean over samples of ``criterion(output, target.float())``."""
+    if task_mode in _REPORT_MODES:
+        return evaluate_report(data_loader, model, device, task, epoch, mode, num_class, criterion=criterion, task_mode=task_mode,
+                               disease_list=disease_list, return_bal_acc=return_bal_acc, args=args)
+    multi_task = str(task_mode).startswith("multi_task")
+    if not multi_task and task_mode != "regression":
+        raise ValueError(f"evaluate_task_report: unknown task_mode {task_mode!r}")
+    for name in _UNBUILT_ARGS:
+        assert not getattr(args, name, False), f"evaluate_task_report: args.{name} is not built"
+    os.makedirs(task, exist_ok=True)
+    device = torch.device(device)
+    whole_set_loss = multi_task and isinstance(criterion, losses.WeightedLabelSmoothingCrossEntropy)
+    float_targets = task_mode == "regression" or isinstance(criterion, torch.nn.BCEWithLogitsLoss)
+    model.eval()
+    out_all, targets_all = [], []
+    loss_sum = torch.zeros((), dtype=torch.float64, device=device)
+    n = 0
+    for batch in misc.prefetched(data_loader, device, args, only=(0, 1)):
+        samples = batch[0].to(device, non_blocking=True)
+        targets = batch[-1].to(device, non_blocking=True)
+        out = model(samples)
+        with torch.autocast(device.type, enabled=False):
+            out = out.float()
+            if not whole_set_loss:
+                loss_sum += criterion(out, targets.float() if float_targets else targets).double() * samples.shape[0]
+        n += samples.shape[0]
+        if task_mode == "regression":
+            if targets.dim() > 1:
+                targets, out = targets[:, 0], out[:, 0]
+            targets, out = targets.reshape(-1), out.reshape(-1)
+        out_all.append(out)
+        targets_all.append(targets)
+    if n == 0:
+        raise ValueError("evaluate_task_report: the loader yielded no sample")
+    logits, targets = torch.cat(out_all), torch.cat(targets_all)
+
+    if task_mode == "regression":
+        res = metrics.regression_measures(logits, targets)
+        res["loss"] = float(loss_sum) / n
+        print("Regression Metrics - Pearsonr: {:.4f} R\u00b2: {:.4f} ExplainedVariance: {:.4f} MSE: {:.4f} MAE: {:.4f}, R2: {:.4f}, "
+              "Loss: {:.4f}".format(*(res[k] for k in _REGRESSION_KEYS)))
+        with open(os.path.join(task, f"regression_metrics_{mode}.csv"), mode="a", newline="", encoding="utf8") as f:
+            w = csv.writer(f)
+            if f.tell() == 0:
+                w.writerow(REGRESSION_HEADER)
+            w.writerow([f"{res[k]:.4f}" for k in _REGRESSION_KEYS])
+        return {k: res[k] for k in _REGRESSION_KEYS}
+
+    if logits.shape[1] != num_class:
+        raise ValueError(f"evaluate_task_report: the model has {logits.shape[1]} outputs, num_class is {num_class}")
+    with torch.autocast(device.type, enabled=False):
+        if whole_set_loss:
+            loss_sum = losses.multi_task_loss(logits, targets, criterion, task_mode).double() * n
+        res = metrics.misc_measures_multi_task(targets, logits, threshold=0.5, multi_task_type=task_mode)
+        confusion = metrics.multi_task_confusion(*metrics.multi_task_problem(targets, logits, task_mode), threshold=0.5)
+    macro, classwise = res["macro"], res["classwise"]
+    stats = {"loss": float(loss_sum) / n, "acc1": macro["accuracy"]}
+    _append_row(os.path.join(task, f"macro_metrics_{mode}.csv"), MACRO_HEADER, [macro[k] for k in _MACRO_KEYS] + [stats["loss"]])
+    T = len(classwise["accuracy"])
+    idx = getattr(args, "multi_task_idx", None)
+    if disease_list is None:
+        names = [str(i + 1) for i in range(T)]
+    else:
+        names = [disease_list[idx[i]] if idx is not None else disease_list[i + 1] for i in range(T)]
+    for i, name in enumerate(names):
+        _append_row(os.path.join(task, f"class_{i + 1}_{name}_metrics_{mode}.csv"), CLASS_HEADER, [classwise[k][i] for k in _CLASS_KEYS])
+        if mode.startswith("test") and not getattr(args, "not_save_figs", False):
+            _write_int_matrix(os.path.join(task, f"confusion_matrix_{mode}_{i + 1}_{name}_epoch_{epoch}.csv"), confusion[i])
+    print("Metrics - Acc: {:.4f} AUC-roc: {:.4f}, AP: {:4f}, AUC-pr: {:.4f} F1-score: {:.4f}, Max F1: {:.4f}, Balanced Acc: {:.4f}, "
+          "Kappa: {:.4f}, MCC: {:.4f}".format(macro["accuracy"], macro["roc_auc"], macro["AP"], macro["auprc"], macro["f1"],
+                                              macro["max_f1"], macro["balanced_acc"], macro["kappa"], macro["mcc"]))
+    if return_bal_acc:
+        return stats, macro["roc_auc"], (macro["auprc"], macro["balanced_acc"])
+    return stats, macro["roc_auc"], macro["auprc"]

@@ -13,7 +13,8 @@ For one class with P positives and N negatives, and per sample the counts {gt_al
                             2 p r / (p + r + 1e-8).  (Newer scikit-learn keeps the points past full recall: they have zero width and a
                             smaller F1, so neither number depends on the version.)
 The reference's own ``1e-8`` deltas stand exactly where it has them.  Provenance: a RESTATEMENT of the reference's formulas, call-compatible
-with its two functions; nothing here is on a hot path."""
+with its functions; nothing here is on a hot path.  ``misc_measures_multi_task`` (:86-242) ranks every task over its own population
+from the masked counts of ``ops.rank_counts_masked``; ``regression_measures`` restates the scipy / scikit-learn values of :642-660."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Optional
@@ -28,31 +29,42 @@ def _host(a) -> np.ndarray:
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
-def binary_rank_metrics(counts, labels) -> Dict[str, np.ndarray]:
+def binary_rank_metrics(counts, labels, valid=None) -> Dict[str, np.ndarray]:
     """``counts`` int [n, C, 4] (ops.rank_counts), ``labels`` [n, C] (!= 0 = positive)  ->  dict(roc_auc, AP, auprc, max_f1), each a
     float64 [C] array: per class (one-vs-rest) roc_auc_score, average_precision_score, auc(recall, precision) of
     precision_recall_curve, and the reference's best F1 along that curve.  ValueError when a class has no positive or no negative
-    (roc_auc_score raises there)."""
+    (roc_auc_score raises there).  ``valid`` [n, C] (!= 0 = in the population) goes with the counts of ops.rank_counts_masked: class c
+    is finished over its valid rows alone, as if the others had been filtered out first; an empty population raises ValueError."""
     cnt = _host(counts).astype(np.int64)
     lab = _host(labels) != 0
     if cnt.ndim != 3 or cnt.shape[2] != 4 or lab.shape != cnt.shape[:2]:
         raise ValueError(f"binary_rank_metrics: expected counts [n, C, 4] and labels [n, C], got {cnt.shape} and {lab.shape}")
+    val = None
+    if valid is not None:
+        val = _host(valid) != 0
+        if val.shape != lab.shape:
+            raise ValueError(f"binary_rank_metrics: expected valid {lab.shape}, got {val.shape}")
     n, C = lab.shape
     out = {k: np.empty(C, dtype=np.float64) for k in ("roc_auc", "AP", "auprc", "max_f1")}
     for c in range(C):
-        pos = lab[:, c]
+        rows, pos, m = cnt[:, c], lab[:, c], n
+        if val is not None:
+            rows, pos = rows[val[:, c]], pos[val[:, c]]
+            m = int(val[:, c].sum())
+            if m == 0:
+                raise ValueError(f"class {c}: the population is empty")
         P = int(pos.sum())
-        N = n - P
+        N = m - P
         if P == 0 or N == 0:
-            raise ValueError(f"class {c}: only one label value present ({P} positives of {n}); AUROC is not defined")
-        gt_all, gt_pos, ge_all, ge_pos = (cnt[pos, c, k] for k in range(4))
+            raise ValueError(f"class {c}: only one label value present ({P} positives of {m}); AUROC is not defined")
+        gt_all, gt_pos, ge_all, ge_pos = (rows[pos, k] for k in range(4))
         neg_ge, neg_gt = ge_all - ge_pos, gt_all - gt_pos
         # twice the Mann-Whitney statistic, an exact integer
         out["roc_auc"][c] = float(np.sum(2 * (N - neg_ge) + (neg_ge - neg_gt))) / (2.0 * P * N)
         out["AP"][c] = float(np.sum(ge_pos / ge_all)) / P
         # one curve point per distinct score, from the highest threshold down; every sample of a tie carries the same pair
-        ga, first = np.unique(cnt[:, c, 2], return_index=True)
-        gp = cnt[first, c, 3]
+        ga, first = np.unique(rows[:, 2], return_index=True)
+        gp = rows[first, 3]
         recall = np.concatenate(([0.0], gp / P))
         precision = np.concatenate(([1.0], gp / ga))
         out["auprc"][c] = float(np.sum(np.diff(recall) * (precision[1:] + precision[:-1]) / 2.0))
@@ -102,6 +114,16 @@ def _device_rank_counts(scores, labels):
                         "device, or a rank_counts function")
     from . import ops
     return ops.rank_counts(scores, labels)
+
+
+def _device_rank_counts_masked(scores, labels, valid=None):
+    if valid is None:
+        return _device_rank_counts(scores, labels)
+    if not all(isinstance(t, torch.Tensor) for t in (scores, labels, valid)):
+        raise TypeError("the rank counts come from the HIP kernel, which takes GPU tensors (there is no CPU path): pass tensors on the "
+                        "device, or a rank_counts function")
+    from . import ops
+    return ops.rank_counts_masked(scores, labels, valid)
 
 
 def _safe_div(a, b):
@@ -159,3 +181,125 @@ def misc_measures_multi_label(y_true, y_prob, threshold: float = 0.5, rank_count
         macro[k] = float(np.mean(cw[k]))
     classwise = {k: cw[k] for k in order + ("balanced_acc", "kappa", "max_f1")}
     return {"macro": macro, "classwise": classwise}
+
+
+_TASK_KEYS = ("accuracy", "roc_auc", "precision", "recall", "f1", "max_f1", "AP", "auprc", "balanced_acc", "specificity", "sensitivity", "mcc",
+              "G", "kappa")
+
+
+def multi_task_problem(y_true, y_pred, multi_task_type: str = "multi_task_default"):
+    """The per-task binary problems of the multi-task modes as three [n, 2T] arrays ``(scores float32, labels uint8, valid uint8)``,
+    torch tensors where ``y_pred`` lives when it is a tensor and numpy arrays otherwise.  Columns (2i, 2i + 1) belong to task i: the
+    float32 softmax over its logit pair (``y_pred`` [n, 2T] read as [n, T, 2] for 'multi_task_default', columns (0, i + 1) of
+    ``y_pred`` [n, T + 1] for any other type), the labels (y_true[:, 0], y_true[:, i + 1]), and twice the task's population
+    ``y_true[:, 0] + y_true[:, i + 1] > 0`` (engine_finetune.py:95-111)."""
+    as_tensor = isinstance(y_pred, torch.Tensor)
+    logits = y_pred.detach().float() if as_tensor else torch.from_numpy(np.ascontiguousarray(y_pred, dtype=np.float32))
+    truth = y_true.detach().to(logits.device) if isinstance(y_true, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y_true))
+    if logits.dim() != 2 or truth.dim() != 2 or truth.shape[0] != logits.shape[0] or truth.shape[1] < 2:
+        raise ValueError(f"misc_measures_multi_task: expected y_true [n, T + 1] and y_pred [n, ...], got {tuple(truth.shape)} and "
+                         f"{tuple(logits.shape)}")
+    n, T = truth.shape[0], truth.shape[1] - 1
+    if multi_task_type == "multi_task_default":
+        if logits.shape[1] != 2 * T:
+            raise ValueError(f"misc_measures_multi_task: {T} tasks need y_pred [n, {2 * T}] in the default layout, got {tuple(logits.shape)}")
+        pairs = logits.reshape(n, T, 2)
+    else:
+        if logits.shape[1] != T + 1:
+            raise ValueError(f"misc_measures_multi_task: {T} tasks need y_pred [n, {T + 1}] in the shared-column layout, got "
+                             f"{tuple(logits.shape)}")
+        pairs = torch.stack([logits[:, :1].expand(n, T), logits[:, 1:]], dim=2)
+    scores = torch.softmax(pairs, dim=2).reshape(n, 2 * T).contiguous()
+    pos = truth != 0
+    labels = torch.stack([pos[:, :1].expand(n, T), pos[:, 1:]], dim=2)
+    valid = ((truth[:, :1] + truth[:, 1:]) > 0).unsqueeze(2).expand(n, T, 2)
+    labels = labels.reshape(n, 2 * T).to(torch.uint8).contiguous()
+    valid = valid.reshape(n, 2 * T).to(torch.uint8).contiguous()
+    if as_tensor:
+        return scores, labels, valid
+    return scores.numpy(), labels.numpy(), valid.numpy()
+
+
+def multi_task_confusion(scores, labels, valid, threshold: float = 0.5) -> np.ndarray:
+    """int64 [T, 2, 2]: [[tn, fp], [fn, tp]] of every task from the arrays of ``multi_task_problem`` -- the task's column-1 score
+    against ``threshold`` and its column-1 label, over the task's own population."""
+    s, y, v = _host(scores)[:, 1::2], _host(labels)[:, 1::2] != 0, _host(valid)[:, 1::2] != 0
+    p = s > threshold
+    return np.stack([(~y & ~p & v).sum(0), (~y & p & v).sum(0), (y & ~p & v).sum(0), (y & p & v).sum(0)], axis=1).reshape(-1, 2, 2)
+
+
+def misc_measures_multi_task(y_true, y_pred, threshold: float = 0.5, multi_task_type: str = "multi_task_default",
+                             rank_counts: Optional[Callable] = None):
+    """engine_finetune.py:86-242: ``{"macro": {...}, "classwise": {...}}`` with the reference's keys for multi-task targets ``y_true``
+    [n, T + 1] (column 0 the shared "normal" label) and LOGITS ``y_pred`` (see ``multi_task_problem`` for the two layouts).  Task i is
+    judged over its own population, the samples with ``y_true[:, 0] + y_true[:, i + 1] > 0``: the threshold entries from the column-1
+    softmax score against ``threshold`` with the reference's own formulas and ``1e-8`` terms, roc_auc / AP / auprc / max_f1 as the mean
+    over the task's two columns, ``micro_AP`` as the average precision over the flattened pairs of all populations.
+
+    The ranking entries come from rank counts: ``rank_counts(scores, labels, valid)`` once over the 2T columns (by default
+    ops.rank_counts_masked) and ``rank_counts(scores, labels)`` once on the flattened micro problem (ops.rank_counts); the default needs
+    GPU tensors, tests pass a numpy restatement.  ValueError, naming the task: an empty population, or a population in which a column
+    has no positive or no negative (roc_auc_score raises there in the reference)."""
+    rank_counts = rank_counts or _device_rank_counts_masked
+    scores, lab, valid = multi_task_problem(y_true, y_pred, multi_task_type)
+    s, y, v = _host(scores), _host(lab) != 0, _host(valid) != 0
+    T = y.shape[1] // 2
+    for i in range(T):
+        m = int(v[:, 2 * i].sum())
+        if m == 0:
+            raise ValueError(f"task {i}: no sample carries the normal label or the task's label: its population is empty")
+        for col in (0, 1):
+            P = int((y[:, 2 * i + col] & v[:, 2 * i + col]).sum())
+            if P == 0 or P == m:
+                raise ValueError(f"task {i}, column {col}: only one label value present ({P} positives of {m}); AUROC is not defined")
+    ranks = binary_rank_metrics(rank_counts(scores, lab, valid), y, valid=v)
+    keep = valid != 0
+    flat_s, flat_l = scores[keep].reshape(-1, 1), lab[keep].reshape(-1, 1)
+    micro = binary_rank_metrics(rank_counts(flat_s, flat_l), flat_l)
+    cm = multi_task_confusion(s, y, v, threshold).astype(np.float64)
+    tn, fp, fn, tp = cm[:, 0, 0], cm[:, 0, 1], cm[:, 1, 0], cm[:, 1, 1]
+    m = tn + fp + fn + tp
+    cw = {}
+    cw["accuracy"] = (tp + tn) / (m + DELTA)
+    cw["sensitivity"] = tp / (tp + fn + DELTA)
+    cw["specificity"] = tn / (tn + fp + DELTA)
+    cw["precision"] = tp / (tp + fp + DELTA)
+    cw["recall"] = tp / (tp + fn + DELTA)
+    cw["f1"] = 2 * cw["precision"] * cw["recall"] / (cw["precision"] + cw["recall"] + DELTA)
+    cw["mcc"] = (tp * tn - fp * fn) / np.sqrt((tp + fp) * (tp + fn) * (tn + fp) * (tn + fn) + DELTA)
+    cw["G"] = np.sqrt(cw["sensitivity"] * cw["specificity"])
+    cw["balanced_acc"] = (cw["sensitivity"] + cw["specificity"]) / 2
+    # Cohen's kappa of [[tn, fp], [fn, tp]], as in misc_measures_multi_label (0 / 0: nan)
+    expected = ((tn + fp) * (fp + tp) + (fn + tp) * (tn + fn)) / m
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cw["kappa"] = 1.0 - (fp + fn) / expected
+    for key in ("roc_auc", "AP", "auprc", "max_f1"):
+        cw[key] = ranks[key].reshape(T, 2).mean(axis=1)
+    macro = {"micro_AP": float(micro["AP"][0])}
+    macro.update({k: float(np.mean(cw[k])) for k in _TASK_KEYS})
+    return {"macro": macro, "classwise": {k: [float(x) for x in cw[k]] for k in _TASK_KEYS}}
+
+
+def regression_measures(pred, target) -> Dict[str, float]:
+    """The regression block of the reference's ``evaluate`` (engine_finetune.py:642-660) on two vectors of equal length:
+    ``pearsonr`` (scipy.stats.pearsonr), ``r2`` (r2_score), ``explained_variance`` (explained_variance_score), ``mse``, ``mae`` and
+    ``R2 = pearsonr ** 2``, restated from their definitions in float64 in two-pass centred form (means first, then sums of centred
+    terms): no scipy, no scikit-learn.  ValueError for fewer than two samples, and for constant targets or constant predictions --
+    for the whole block, not only for the correlation, which is undefined there."""
+    x = _host(pred).astype(np.float64).reshape(-1)
+    y = _host(target).astype(np.float64).reshape(-1)
+    if x.shape != y.shape or x.size < 2:
+        raise ValueError(f"regression_measures: expected two vectors of one length >= 2, got {x.size} and {y.size}")
+    if not (np.isfinite(x).all() and np.isfinite(y).all()):
+        raise ValueError("regression_measures: non-finite predictions or targets")
+    xc, yc = x - x.mean(), y - y.mean()
+    sxx, syy = float(np.sum(xc * xc)), float(np.sum(yc * yc))
+    if sxx == 0.0 or syy == 0.0:
+        raise ValueError("regression_measures: constant " + ("predictions" if sxx == 0.0 else "targets") + ": the correlation and "
+                         "the explained shares are not defined")
+    r = float(np.sum(xc * yc)) / float(np.sqrt(sxx) * np.sqrt(syy))
+    r = max(-1.0, min(1.0, r))
+    d = y - x
+    dc = d - d.mean()
+    return {"pearsonr": r, "r2": 1.0 - float(np.sum(d * d)) / syy, "explained_variance": 1.0 - float(np.sum(dc * dc)) / syy,
+            "mse": float(np.mean(d * d)), "mae": float(np.mean(np.abs(d))), "R2": r * r}

@@ -590,6 +590,47 @@ def mae_compose(pred: torch.Tensor, imgs: torch.Tensor, mask: torch.Tensor, fram
     return out
 
 
+def _rank_counts(name: str, scores: torch.Tensor, labels: torch.Tensor, valid: Optional[torch.Tensor]) -> torch.Tensor:
+    """The checks and the launch that ``rank_counts`` (valid None) and ``rank_counts_masked`` share."""
+    flags = (("labels", labels),) if valid is None else (("labels", labels), ("valid", valid))
+    if not scores.is_cuda or not all(t.is_cuda for _, t in flags):
+        raise RuntimeError(f"{name}: expected GPU tensors (the HIP path has no CPU fallback)")
+    if scores.dtype != F32:
+        raise TypeError(f"{name}: scores must be float32, got {scores.dtype}")
+    for what, t in flags:
+        if t.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{name}: {what} must be bool or uint8, got {t.dtype}")
+    if scores.dim() != 2 or any(t.shape != scores.shape or t.device != scores.device for _, t in flags):
+        raise ValueError(f"{name}: expected scores and {' and '.join(w for w, _ in flags)} [n, C] on one device, got "
+                         f"{tuple(scores.shape)} and {' and '.join(str(tuple(t.shape)) for _, t in flags)}")
+    n, C = scores.shape
+    if n < 1 or C < 1:
+        raise ValueError(f"{name}: empty input {tuple(scores.shape)}")
+    scores = scores.detach()
+    # a bool is stored as 0 / 1: the same bytes
+    flags = tuple((what, t.detach().view(torch.uint8) if t.dtype == torch.bool else t.detach()) for what, t in flags)
+    for what, t in (("scores", scores),) + flags:
+        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
+            raise ValueError(f"{name}: {what} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
+    nan = torch.isnan(scores)
+    if valid is not None:
+        nan = nan & (flags[1][1] != 0)
+    if bool(nan.any()):
+        raise ValueError(f"{name}: scores contain NaN" + ("" if valid is None else " at a valid position"))
+    ss, ls = (t.stride(0) if n > 1 else C for t in (scores, flags[0][1]))
+    counts = torch.empty((n, C, 4), dtype=torch.int32, device=scores.device)
+    # algorithmic HBM bytes: scores, labels (and the mask) read once (the re-reads of the j stream hit the caches), the counts written once
+    if valid is None:
+        _launch(name, 0.0, float(n * C * (4 + 1 + 16)),
+                lambda: call("octmae_rank_counts", scores.data_ptr(), ss, flags[0][1].data_ptr(), ls, counts.data_ptr(), n, C, _stream()))
+    else:
+        vs = flags[1][1].stride(0) if n > 1 else C
+        _launch(name, 0.0, float(n * C * (4 + 1 + 1 + 16)),
+                lambda: call("octmae_rank_counts_masked", scores.data_ptr(), ss, flags[0][1].data_ptr(), ls, flags[1][1].data_ptr(), vs,
+                             counts.data_ptr(), n, C, _stream()))
+    return counts
+
+
 def rank_counts(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """int32 [n, C, 4] = {gt_all, gt_pos, ge_all, ge_pos} per sample i and class c: the samples j with scores[j, c] > scores[i, c], how
     many of those are positive, and the same for >= (i counts itself).  AUROC, average precision and the precision-recall curve
@@ -597,32 +638,17 @@ def rank_counts(scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     both may be column slices of wider buffers (unit column stride, any row stride >= C).  IEEE comparisons: -0.0 ties with 0.0 and
     +-inf are ordinary values; a NaN raises ValueError before the launch (scikit-learn raises there too, and a NaN would silently count
     as zero).  That check reads one flag back from the device.  No autograd; no 16-bit operand, so autocast changes nothing."""
-    if not scores.is_cuda or not labels.is_cuda:
-        raise RuntimeError("rank_counts: expected GPU tensors (the HIP path has no CPU fallback)")
-    if scores.dtype != F32:
-        raise TypeError(f"rank_counts: scores must be float32, got {scores.dtype}")
-    if labels.dtype not in (torch.bool, torch.uint8):
-        raise TypeError(f"rank_counts: labels must be bool or uint8, got {labels.dtype}")
-    if scores.dim() != 2 or labels.shape != scores.shape or scores.device != labels.device:
-        raise ValueError(f"rank_counts: expected scores and labels [n, C] on one device, got {tuple(scores.shape)} and {tuple(labels.shape)}")
-    n, C = scores.shape
-    if n < 1 or C < 1:
-        raise ValueError(f"rank_counts: empty input {tuple(scores.shape)}")
-    scores, labels = scores.detach(), labels.detach()
-    if labels.dtype == torch.bool:
-        labels = labels.view(torch.uint8)          # same bytes: a bool is stored as 0 / 1
-    for t, name in ((scores, "scores"), (labels, "labels")):
-        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
-            raise ValueError(f"rank_counts: {name} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
-    if bool(torch.isnan(scores).any()):
-        raise ValueError("rank_counts: scores contain NaN")
-    ss = scores.stride(0) if n > 1 else C
-    ls = labels.stride(0) if n > 1 else C
-    counts = torch.empty((n, C, 4), dtype=torch.int32, device=scores.device)
-    # algorithmic HBM bytes: scores and labels read once (the re-reads of the j stream hit the caches), the counts written once
-    _launch("rank_counts", 0.0, float(n * C * (4 + 1 + 16)),
-            lambda: call("octmae_rank_counts", scores.data_ptr(), ss, labels.data_ptr(), ls, counts.data_ptr(), n, C, _stream()))
-    return counts
+    return _rank_counts("rank_counts", scores, labels, None)
+
+
+def rank_counts_masked(scores: torch.Tensor, labels: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:
+    """``rank_counts`` over a per-column population: column c ranks the samples with ``valid[:, c] != 0`` among themselves, and a
+    sample outside the population gets four zeros (the output is fully written).  One launch for all the tasks of the multi-task
+    evaluation, whose populations differ per task (OCTCube/engine_finetune.py:130-139 filters by boolean indexing on the CPU).
+    ``scores`` float32 [n, C], ``labels`` and ``valid`` bool or uint8 [n, C]; each may be a column slice of a wider buffer (unit column
+    stride, any row stride >= C).  Comparisons as in ``rank_counts``; a NaN raises ValueError before the launch only where it is VALID
+    (the reference filters first, so a NaN in an excluded row is legal).  No autograd; no 16-bit operand."""
+    return _rank_counts("rank_counts_masked", scores, labels, valid)
 
 
 def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
