@@ -40,8 +40,9 @@ extern "C" {
  * 18: octmae_rank_counts (the rank counts behind AUROC / average precision of the fine-tune evaluation, csrc/metrics.hip).
  * 19: octmae_retrieval_ranks (the retrieval ranks of the COEM validation off f32 MFMA tiles, csrc/retrieval.hip).
  * 20: octmae_mix_batch (mixup / cutmix of a fine-tune batch in place, csrc/mixup.hip).
- * 21: octmae_rank_counts_masked (rank counts over a per-column population: the multi-task evaluation, csrc/metrics.hip). */
-#define OCTMAE_ABI_VERSION 21
+ * 21: octmae_rank_counts_masked (rank counts over a per-column population: the multi-task evaluation, csrc/metrics.hip).
+ * 22: octmae_image_stats, octmae_image_augment, octmae_aug_desc (RandAugment's image operations on the device, csrc/augment2d.hip). */
+#define OCTMAE_ABI_VERSION 22
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -264,6 +265,42 @@ int octmae_volume_resample(const void* vol, int dtype, int D, int H, int W, cons
 int octmae_image_resample(const void* src, int n, int H, int W, int C, int top, int left, int ch, int cw, int OH, int OW, int flip_w,
                           const float* lut, void* dst, void* stream);
 int octmae_image_resample_plan(int H, int W, int C, int ch, int cw, int OH, int OW, int* tile_h, int* lds_bytes);
+
+/* ---- RandAugment's image operations (csrc/augment2d.hip) -------------------------------------------
+ * The Pillow operations of the reference's OCTCube/util/rand_augment.py (timm's auto_augment; the train chain of util/datasets.py
+ * build_transform), on n equally sized uint8 [n][H][W][3] images in device memory, bit-equal to Pillow.  The host draws the
+ * decisions (octcubem_amd/rand_augment.py) and writes one descriptor per image; nothing returns to the host in between.
+ *
+ * octmae_aug_desc, one per image:
+ *   kind 0 none       copy (or normalise only)
+ *        1 table      mode 0 Invert, 1 Posterize(iarg bits), 2 Solarize(iarg threshold), 3 SolarizeAdd(iarg, threshold 128),
+ *                     4 Brightness(factor), 5 Contrast(factor), 6 AutoContrast, 7 Equalize; modes 5-7 read the image's histograms
+ *        2 colour     blend(L replicated, pixel, factor)
+ *        3 sharpness  blend(ImageFilter.SMOOTH, pixel, factor)
+ *        4 affine     Image.transform(size, AFFINE, m, mode, fillcolor = fill): mode 2 bilinear, 3 bicubic (Pillow's numbers);
+ *                     source position m0 (x + 0.5) + m1 (y + 0.5) + m2, m3 (x + 0.5) + m4 (y + 0.5) + m5 in double
+ *   blend = Pillow's ImagingBlend with factor as a C float.
+ *
+ * octmae_image_stats: hist uint32 [n][4][256] (device) = the histograms of R, G, B and L = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16
+ * of every image i with needed[i] != 0 (needed: n device bytes, or NULL = all); the rows of the other images are zero.
+ * octmae_image_augment: dst = the image's op applied; uint8 [n][H][W][3], or with lut (float32 [3][256], device: ToTensor -> Normalize
+ * as in octmae_image_resample) float32 [n][3][H][W].  desc: n descriptors in DEVICE memory; desc_host: the same n descriptors in host
+ * memory, or NULL -- when given they are checked before the launch.  hist: octmae_image_stats' output, NULL when no op reads it.
+ * src and dst must not overlap.
+ * -1, before any launch: a NULL src / dst / desc / hist (stats), src == dst, n or a size < 1, H W > 2^30; for desc_host, an unknown
+ * kind or mode, a negative Posterize, a SolarizeAdd outside 0..255, a NaN factor, a non-finite matrix, or a mode 5-7 table op
+ * without hist. */
+typedef struct {
+  int kind, mode;
+  double m[6];
+  float factor;
+  int iarg;
+  unsigned char fill[4];     /* R, G, B, unused */
+  int reserved;
+} octmae_aug_desc;           /* 72 bytes */
+int octmae_image_stats(const void* src, int n, int H, int W, const unsigned char* needed, unsigned* hist, void* stream);
+int octmae_image_augment(const void* src, int n, int H, int W, const octmae_aug_desc* desc, const octmae_aug_desc* desc_host,
+                         const unsigned* hist, const float* lut, void* dst, void* stream);
 
 /* ---- attention -----------------------------------------------------------------------------------
  * softmax(q k^T * scale) v, non-causal, no dropout: video_vit.py:130-134 (flash path: flash_attn MHA,

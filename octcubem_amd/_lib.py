@@ -34,6 +34,8 @@ SIGNATURES = {
     "octmae_volume_resample": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp],
     "octmae_image_resample": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "octmae_image_resample_plan": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "octmae_image_stats": [_vp, _i, _i, _i, _vp, _vp, _vp],
+    "octmae_image_augment": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "octmae_rank_counts": [_vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
     "octmae_rank_counts_masked": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
     "octmae_retrieval_ranks": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _vp],

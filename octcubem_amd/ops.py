@@ -554,6 +554,92 @@ def image_resample(img: torch.Tensor, size, crop=None, flip: bool = False, lut: 
     return out
 
 
+# one octmae_aug_desc (include/octmae.h) per image: 72 bytes
+AUG_DESC = np.dtype([("kind", "<i4"), ("mode", "<i4"), ("m", "<f8", (6,)), ("factor", "<f4"), ("iarg", "<i4"), ("fill", "u1", (4,)),
+                     ("reserved", "<i4")])
+AUG_NONE, AUG_TABLE, AUG_COLOR, AUG_SHARPNESS, AUG_AFFINE = range(5)
+(AUG_LUT_INVERT, AUG_LUT_POSTERIZE, AUG_LUT_SOLARIZE, AUG_LUT_SOLARIZE_ADD, AUG_LUT_BRIGHTNESS, AUG_LUT_CONTRAST, AUG_LUT_AUTOCONTRAST,
+ AUG_LUT_EQUALIZE) = range(8)
+
+
+def aug_needs_stats(desc: np.ndarray) -> np.ndarray:
+    """bool [n]: the descriptors whose op reads the image's histograms (Contrast, AutoContrast, Equalize)."""
+    return (desc["kind"] == AUG_TABLE) & (desc["mode"] >= AUG_LUT_CONTRAST)
+
+
+def _upload(a: np.ndarray, device) -> torch.Tensor:
+    # through pinned memory, so that the copy is asynchronous: the chain never waits for the device
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).pin_memory().to(device, non_blocking=True)
+
+
+def _chk_images(img: torch.Tensor, name: str):
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] != 3:
+        raise RuntimeError(f"{name}: expected uint8 [n, H, W, 3], got {tuple(img.shape)} {img.dtype}")
+    return _chk(img.detach(), torch.uint8, name)
+
+
+def image_stats(img: torch.Tensor, needed=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 256-bin histograms of R, G, B and L = convert("L") of uint8 images [n, H, W, 3], in one launch: int32 [n, 4, 256], left on
+    the GPU.  ``needed``: n booleans on the host; the images whose flag is unset are skipped and their rows are zero."""
+    img = _chk_images(img, "image_stats")
+    n, H, W, _ = img.shape
+    if out is None:
+        out = torch.empty((n, 4, 256), dtype=torch.int32, device=img.device)
+    else:
+        _chk(out, torch.int32, "image_stats out")
+        if tuple(out.shape) != (n, 4, 256) or out.device != img.device:
+            raise RuntimeError(f"image_stats: out is {tuple(out.shape)} on {out.device}, expected {(n, 4, 256)} on {img.device}")
+    flags = None
+    if needed is not None:
+        needed = np.asarray(needed, dtype=np.uint8).reshape(-1)
+        if needed.shape[0] != n:
+            raise RuntimeError(f"image_stats: {needed.shape[0]} flags for {n} images")
+        flags = _upload(needed, img.device)
+    _launch("image_stats", 0.0, float(img.numel()),
+            lambda: call("octmae_image_stats", img.data_ptr(), n, H, W, _p(flags), out.data_ptr(), _stream()))
+    return out
+
+
+def image_augment(img: torch.Tensor, desc: np.ndarray, hist: Optional[torch.Tensor] = None, lut: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One Pillow operation per image, bit for bit, on uint8 images [n, H, W, 3] in one launch.  ``desc``: n ``AUG_DESC`` records on
+    the host (octcubem_amd.rand_augment.describe_op writes them); ``hist``: image_stats' output, needed when an op reads the image's
+    statistics.  The result is uint8 [n, H, W, 3], or with ``lut`` (float32 [3, 256], ToTensor -> Normalize as in image_resample)
+    float32 [n, 3, H, W].  ``out`` must not alias ``img``.  No autograd."""
+    img = _chk_images(img, "image_augment")
+    n, H, W, _ = img.shape
+    if not isinstance(desc, np.ndarray) or desc.dtype != AUG_DESC or desc.shape != (n,):
+        raise RuntimeError(f"image_augment: expected {n} AUG_DESC records on the host")
+    desc = np.ascontiguousarray(desc)
+    if hist is not None:
+        _chk(hist, torch.int32, "image_augment hist")
+        if tuple(hist.shape) != (n, 4, 256) or hist.device != img.device:
+            raise RuntimeError("image_augment: hist must be int32 [n, 4, 256] on the images' device")
+    elif bool(aug_needs_stats(desc).any()):
+        raise RuntimeError("image_augment: an op reads the image statistics and hist is missing")
+    if lut is not None:
+        _chk(lut, F32, "image_augment lut")
+        if tuple(lut.shape) != (3, 256) or lut.device != img.device:
+            raise RuntimeError("image_augment: lut must be float32 [3, 256] on the images' device")
+        shape, dtype = (n, 3, H, W), F32
+    else:
+        shape, dtype = (n, H, W, 3), torch.uint8
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=img.device)
+    else:
+        _chk(out, dtype, "image_augment out")
+        if tuple(out.shape) != shape or out.device != img.device:
+            raise RuntimeError(f"image_augment: out is {tuple(out.shape)} on {out.device}, expected {shape} on {img.device}")
+        if out.data_ptr() == img.data_ptr():
+            raise RuntimeError("image_augment: out aliases img")
+    dev = _upload(desc, img.device)
+    # algorithmic HBM bytes: the images read once, the output written once
+    _launch("image_augment", 0.0, float(img.numel() + out.numel() * out.element_size()),
+            lambda: call("octmae_image_augment", img.data_ptr(), n, H, W, dev.data_ptr(), desc.ctypes.data, _p(hist), _p(lut),
+                         out.data_ptr(), _stream()))
+    return out
+
+
 def mae_compose(pred: torch.Tensor, imgs: torch.Tensor, mask: torch.Tensor, frame_idx: Optional[torch.Tensor], u: int, p: int,
                 denorm: bool = False) -> torch.Tensor:
     """The four reconstruction volumes of the validation pass (custom_util/misc.py:1225-1299 get_visible_images) in one kernel:

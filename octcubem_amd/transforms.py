@@ -167,7 +167,9 @@ class Image2DTransform:
     tensor, uint8 [H, W] or [H, W, 3], on the CPU or the GPU -- and returns float32 [3, S, S] on the GPU, without grad."""
 
     def __init__(self, size: Tuple[int, int], mean=IMAGENET_MEAN, std=IMAGENET_STD, random_resized_crop: bool = False,
-                 scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), hflip_prob: float = 0.0, generator: Optional[torch.Generator] = None):
+                 scale=(0.2, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), hflip_prob: float = 0.0, generator: Optional[torch.Generator] = None,
+                 auto_augment=None, aa_hparams: Optional[dict] = None, re_prob: float = 0.0, re_mode: str = "const", re_count: int = 1,
+                 center_crop=None):
         self.size = (int(size[0]), int(size[1]))
         self.random_resized_crop = bool(random_resized_crop)
         self.scale, self.ratio = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
@@ -176,6 +178,19 @@ class Image2DTransform:
         self.lut = normalize_lut(mean, std)
         self._luts = {}                     # device -> the table there
         self.last_params = None             # {"crop": (top, left, h, w) or None, "flip": bool} of the last call; a list after .batch
+        # The fine-tune chain (build_transform): all off by default, and then nothing below changes.  auto_augment: a config string
+        # for rand_augment_transform (with aa_hparams) or a RandAugment; its decisions join last_params under "ops".  re_prob > 0:
+        # RandomErasing(re_prob, mode=re_mode, max_count=re_count, cube=False) on the normalised batch ("erased" in last_params).
+        # center_crop = (h, w): the resize goes to ``size`` and the centre h x w of it is the result (the eval chain).
+        if isinstance(auto_augment, str):
+            from .rand_augment import rand_augment_transform
+            auto_augment = rand_augment_transform(auto_augment, dict(aa_hparams or {}))
+        self.auto_augment = auto_augment
+        self.random_erasing = None
+        if re_prob > 0.0:
+            from .random_erasing import RandomErasing
+            self.random_erasing = RandomErasing(re_prob, mode=re_mode, max_count=re_count, num_splits=0, cube=False)
+        self.center_crop = None if center_crop is None else (int(center_crop[0]), int(center_crop[1]))
 
     @staticmethod
     def _image(x) -> torch.Tensor:
@@ -223,6 +238,8 @@ class Image2DTransform:
         if not imgs:
             raise ValueError("batch: no images")
         params = [self._draw(int(x.shape[0]), int(x.shape[1])) for x in imgs]
+        if self.auto_augment is not None or self.random_erasing is not None or self.center_crop is not None:
+            return self._batch_augmented(imgs, params)
         plain = all(p["crop"] is None and not p["flip"] for p in params) and all(x.shape == imgs[0].shape for x in imgs)
         device = next((x.device for x in imgs if x.is_cuda), torch.device("cuda", torch.cuda.current_device()))
         with torch.cuda.device(device):
@@ -237,6 +254,62 @@ class Image2DTransform:
                     ops.image_resample(x.to(device).contiguous(), self.size, crop=p["crop"], flip=p["flip"], lut=lut, out=out[b:b + 1])
         self.last_params = params
         return out
+
+
+    def _batch_augmented(self, imgs, params) -> torch.Tensor:
+        """The fine-tune chains: image_resample to uint8 (crop, flip) -> [centre crop] -> the RandAugment layers, whose last launch
+        writes through the normalisation table (kind "none" where there is nothing else to do) -> erasing.  No launch of this path
+        waits for the device."""
+        from .rand_augment import RandAugment
+        device = next((x.device for x in imgs if x.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+        with torch.cuda.device(device):
+            u8 = torch.empty((len(imgs), *self.size, 3), dtype=torch.uint8, device=device)
+            for b, (x, p) in enumerate(zip(imgs, params)):
+                x = x.to(device)
+                if x.dim() == 2:                        # convert("RGB") of a grey image: three equal channels
+                    x = x[:, :, None].expand(-1, -1, 3)
+                ops.image_resample(x.contiguous(), self.size, crop=p["crop"], flip=p["flip"], out=u8[b])
+            if self.center_crop is not None:
+                ch, cw = self.center_crop
+                top, left = int(round((self.size[0] - ch) / 2.0)), int(round((self.size[1] - cw) / 2.0))     # torchvision's center_crop
+                u8 = u8[:, top:top + ch, left:left + cw].contiguous()
+            aug = self.auto_augment if self.auto_augment is not None else RandAugment([], 0)
+            decisions = aug.draw(len(imgs)) if self.auto_augment is not None else [[] for _ in imgs]
+            out = aug.apply(u8, decisions, lut=self._lut_on(device))
+            aug.last_params = decisions
+            for p, d in zip(params, decisions):
+                p["ops"] = d
+            if self.random_erasing is not None:
+                self.random_erasing(out)
+                for b, p in enumerate(params):
+                    p["erased"] = [box[1:] for box in self.random_erasing.last_boxes if box[0] == b]
+        self.last_params = params
+        return out
+
+
+def build_transform(is_train, args, generator=None) -> Image2DTransform:
+    """The reference's OCTCube/util/datasets.py build_transform (timm's create_transform for training), as one device transform.
+    ``is_train`` is compared with 'train' as there; ``args`` carries input_size, aa, reprob, remode, recount, color_jitter.
+      train  RandomResizedCrop(scale=(0.08, 1), bicubic) -> flip(0.5) -> RandAugment(args.aa; translate_const = int(0.45 input_size),
+             img_mean = round(255 mean), bicubic) -> ToTensor -> Normalize -> RandomErasing(reprob, remode, recount) per image
+      eval   Resize(int(input_size / crop_pct), bicubic) -> CenterCrop(input_size) -> ToTensor -> Normalize, crop_pct = 224 / 256 up
+             to 224 and 1.0 above
+    timm applies ``color_jitter`` only when ``aa`` is unset; that chain is not built here."""
+    size = int(args.input_size)
+    if is_train == "train":
+        aa = getattr(args, "aa", None)
+        if not aa and getattr(args, "color_jitter", None) is not None:
+            raise NotImplementedError("color_jitter without aa: ColorJitter has no device form; set args.aa or color_jitter=None")
+        if aa and not str(aa).startswith("rand"):
+            raise NotImplementedError(f"auto_augment {aa!r}: only RandAugment ('rand-...') is built")
+        hparams = dict(translate_const=int(size * 0.45), img_mean=tuple(min(255, round(255 * m)) for m in IMAGENET_MEAN), interpolation=3)
+        return Image2DTransform((size, size), IMAGENET_MEAN, IMAGENET_STD, random_resized_crop=True, scale=(0.08, 1.0), hflip_prob=0.5,
+                                generator=generator, auto_augment=aa or None, aa_hparams=hparams,
+                                re_prob=float(getattr(args, "reprob", 0.0) or 0.0), re_mode=getattr(args, "remode", "const"),
+                                re_count=getattr(args, "recount", 1))
+    crop_pct = 224 / 256 if size <= 224 else 1.0
+    full = int(size / crop_pct)
+    return Image2DTransform((full, full), IMAGENET_MEAN, IMAGENET_STD, center_crop=(size, size))
 
 
 def create_2d_transforms(input_size, mean=IMAGENET_MEAN, std=IMAGENET_STD, random_resized_crop=False, scale=(0.2, 1.0),
