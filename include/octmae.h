@@ -41,8 +41,10 @@ extern "C" {
  * 19: octmae_retrieval_ranks (the retrieval ranks of the COEM validation off f32 MFMA tiles, csrc/retrieval.hip).
  * 20: octmae_mix_batch (mixup / cutmix of a fine-tune batch in place, csrc/mixup.hip).
  * 21: octmae_rank_counts_masked (rank counts over a per-column population: the multi-task evaluation, csrc/metrics.hip).
- * 22: octmae_image_stats, octmae_image_augment, octmae_aug_desc (RandAugment's image operations on the device, csrc/augment2d.hip). */
-#define OCTMAE_ABI_VERSION 22
+ * 22: octmae_image_stats, octmae_image_augment, octmae_aug_desc (RandAugment's image operations on the device, csrc/augment2d.hip).
+ * 23: octmae_patch_scatter, octmae_cam_weights (+ octmae_cam_ws_floats), octmae_cam_tokens, octmae_heatmap (input gradients, Grad-CAM
+ *     and heat volumes, csrc/saliency.hip). */
+#define OCTMAE_ABI_VERSION 23
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -408,6 +410,36 @@ int octmae_mse_bwd(const float* pred, const float* imgs, const int* frame_idx, c
  * a batch stride below L * PD.  -2: denorm outside {0, 1}, more than 2^31 - 1 tokens. */
 int octmae_mae_compose(const float* pred, long long pred_batch_stride, const float* imgs, const int* frame_idx, const float* mask,
                        uint8_t* out, int B, int T, int H, int W, int u_sz, int p, int L, int denorm, void* stream);
+
+/* ---- saliency: input gradients, Grad-CAM, heat volumes (csrc/saliency.hip) ---------------------------
+ * retinal-COEM/src/oph_vis_util/base_cam_retclip_3mod.py (the reference's Grad-CAM base class over pytorch_grad_cam) and its
+ * compute_input_gradient=True.  All four are deterministic (no floating-point atomics).
+ *
+ * The adjoint of octmae_patch_gather: dimgs f32 [B][C][T][H][W] receives, at the voxels of kept token ids[b][i], row b * nkeep + i of
+ * dpatch ([B*nkeep][C*tp*p*p] of the library's 16-bit operand type, conv-weight order (c,u,py,px): what the PatchEmbed dgrad GEMM
+ * writes), widened exactly; every voxel of a token that was not kept is +0.0f.  The result does not depend on what dimgs held before:
+ * with ids and nkeep < L a zero-fill pass runs first on `stream`; with ids == NULL (tokens 0..nkeep-1) or nkeep == L the one pass
+ * writes every voxel.  CONTRACT: the ids of one sample are distinct (the masking kernel's); not checked on the device (an id outside
+ * [0, L) is clamped into the volume).  -1: the argument rules of octmae_patch_gather (NULL, p % 8, H % p, W % p, T % tp, W % 4,
+ * nkeep > L), non-positive sizes, pointers that are not 16-byte aligned.  -2: C*tp*p*p or B * L above 2^31 - 1. */
+int octmae_patch_scatter(const void* dpatch_lp, const void* ids, int ids_is_i64, float* dimgs, int B, int C, int T, int H, int W,
+                         int tp, int p, int nkeep, void* stream);
+/* Grad-CAM's reduction (pytorch_grad_cam GradCAM.get_cam_weights + BaseCAM.get_cam_image + the ReLU) over f32 token streams
+ * [B][n_prefix + L][C]; the n_prefix leading rows (the cls token; 0 allowed) are never read.
+ *   w[b][c]   = (sum_l G[b][n_prefix + l][c]) / L          f32 [B][C]; rows split over workgroups, the partial sums in ws folded in
+ *               ascending order by a second launch.  ws: octmae_cam_ws_floats(B, L, C) floats (-1 / -2 for sizes it refuses).
+ *   cam[b][l] = max(0, sum_c w[b][c] * A[b][n_prefix + l][c])   f32 [B][L]; one wave per token row.
+ * -1, before any launch: NULL, non-positive B / L / C, n_prefix < 0, C % 4, pointers not 16-byte aligned.  -2: B above 65535. */
+int octmae_cam_ws_floats(int B, int L, int C);
+int octmae_cam_weights(const float* G, float* w, float* ws, int B, int L, int n_prefix, int C, void* stream);
+int octmae_cam_tokens(const float* A, const float* w, float* cam, int B, int L, int n_prefix, int C, void* stream);
+/* Heat volume of a coarse saliency map: m f32 [B][t][h][w] -> out uint8 [B][F][H][W].  Per sample mn = min m, mx = max m (written to
+ * mnmx f32 [B][2] by a first launch), v = (m - mn) / (1e-7f + (mx - mn)) on the COARSE map, then v resampled linearly along t -> F and
+ * bilinearly over (h, w) -> (H, W) with F.interpolate's align_corners=False positions (src = (dst + 0.5) in / out - 0.5, negative -> 0,
+ * upper neighbour clamped; equal sizes on an axis are the identity on it), out = (uint8) floorf(255 v).  A constant map gives 0.
+ * pytorch_grad_cam upsamples before it scales; here the order is the other way round so that min / max run over the coarse map only.
+ * -1, before any launch: NULL, a non-positive size, W % 4, out not 4-byte aligned.  -2: t * h * w above 2^31 - 1. */
+int octmae_heatmap(const float* m, float* mnmx, uint8_t* out, int B, int t, int h, int w, int F, int H, int W, void* stream);
 
 /* ---- ranking metrics of the fine-tune evaluation (csrc/metrics.hip) ---------------------------------
  * OCTCube/engine_finetune.py:251-343 and :786-792 judge a run by scikit-learn's roc_auc_score, average_precision_score and

@@ -6,4 +6,6 @@ reference's Python interface for this path (video_vit, models_mae, misc, lr_sche
 from . import _lib  # noqa: F401  (does not load the shared library until first use)
 from .mixup import Mixup  # noqa: F401  (the fine-tune loop's mixup_fn; host decisions + one launch of csrc/mixup.hip)
 
-__all__ = ["models_mae", "video_vit", "misc", "lr_sched", "engine_pretrain", "optim", "parallel", "ops", "Mixup"]
+from . import saliency  # noqa: F401  (input gradients, Grad-CAM and heat volumes; csrc/saliency.hip)
+
+__all__ = ["models_mae", "video_vit", "misc", "lr_sched", "engine_pretrain", "optim", "parallel", "ops", "Mixup", "saliency"]

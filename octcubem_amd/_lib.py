@@ -68,6 +68,11 @@ SIGNATURES = {
     "octmae_mse_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_mse_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_mae_compose": [_vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "octmae_patch_scatter": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "octmae_cam_ws_floats": [_i, _i, _i],
+    "octmae_cam_weights": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "octmae_cam_tokens": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "octmae_heatmap": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_mt_chunk_elems": [],
     "octmae_mt_sumsq": [_vp, _vp, _vp, _i, _vp, _vp],
     "octmae_mt_finish_norm": [_vp, _i, _f, _vp, _vp, _vp],

@@ -103,6 +103,39 @@ def notify_grad_ready(params):
             cb(ps)
 
 
+# ------------------------------------------------------------------------------------------------
+# weight-gradient switch (saliency passes: only the activation gradients are wanted)
+# ------------------------------------------------------------------------------------------------
+_weight_grads = True       # module-level, not thread-local: a backward runs on autograd's worker thread
+
+
+def weight_grads_enabled() -> bool:
+    return _weight_grads
+
+
+class weight_grads:
+    """Context manager: ``with ops.weight_grads(False):`` -- a backward that RUNS inside launches no weight-gradient GEMM, no bias
+    column sum, no LayerNorm parameter gradient and no positional / cls / mask-token gradient from any Function of this file, touches no
+    gradient buffer (``ctx.grads()`` is not called) and notifies no reducer.  The activation-gradient launches are the same ones, so
+    the input gradient is bit-identical either way.  Read when a backward runs, not when the forward ran; nests, and restores the
+    previous state on exit, also when the body raises."""
+
+    def __init__(self, enabled: bool):
+        self.enabled = bool(enabled)
+        self._prev: List[bool] = []
+
+    def __enter__(self):
+        global _weight_grads
+        self._prev.append(_weight_grads)
+        _weight_grads = self.enabled
+        return self
+
+    def __exit__(self, *exc):
+        global _weight_grads
+        _weight_grads = self._prev.pop()
+        return False
+
+
 def grad_buf(p: torch.nn.Parameter) -> torch.Tensor:
     """The fp32 buffer weight gradients are accumulated into (``p.grad``; created zeroed if absent)."""
     if p.grad is None:
@@ -304,7 +337,8 @@ def linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], m
 
 
 def linear_dgrad(dy: torch.Tensor, w: torch.Tensor, pre: Optional[torch.Tensor] = None,
-                 colsum: Optional[torch.Tensor] = None, atomic_colsum: bool = False, pre_is_dgelu: bool = False) -> torch.Tensor:
+                 colsum: Optional[torch.Tensor] = None, atomic_colsum: bool = False, pre_is_dgelu: bool = False,
+                 fold_entry: bool = False) -> torch.Tensor:
     """dx[M,K] = dy[M,N] @ w[N,K]  (optionally * gelu'(pre[M,K])), bf16.  With ``pre``, ``colsum`` (fp32 [K]) receives
     += the column sums of dx -- the bias gradient of the Linear that produced ``pre`` -- from the same call: per-slab partial
     sums through a workspace and a folding launch (octmae_linear_dgrad_dgelu); ``atomic_colsum`` selects the
@@ -315,14 +349,18 @@ def linear_dgrad(dy: torch.Tensor, w: torch.Tensor, pre: Optional[torch.Tensor] 
     if pre is None:
         assert colsum is None
         _gemm(w, dy, dx, K, M, N, w.stride(0), dy.stride(0), K, 1, 0, EPI_BF16)
-    elif colsum is None or atomic_colsum:
+    elif (colsum is None and not fold_entry) or atomic_colsum:
         _gemm(w, dy, dx, K, M, N, w.stride(0), dy.stride(0), K, 1, 0, EPI_DGELU | (0x8000 if pre_is_dgelu else 0), C2=colsum, aux=pre,
               ldaux=pre.stride(0))
     else:
-        rows = load().octmae_dgelu_colsum_ws_rows(M)
-        ws = torch.empty((rows, K), dtype=F32, device=dy.device)
+        # fold_entry without colsum (weight gradients switched off, and the Linear that produced ``pre`` has a bias): the entry point
+        # the switched-on backward takes, the side output a null pointer.  A bias-free Linear takes the branch above either way.
+        ws = None
+        if colsum is not None:
+            rows = load().octmae_dgelu_colsum_ws_rows(M)
+            ws = torch.empty((rows, K), dtype=F32, device=dy.device)
         st = _stream()
-        args = (w.data_ptr(), dy.data_ptr(), dx.data_ptr(), pre.data_ptr(), ws.data_ptr(), colsum.data_ptr(), M, N, K, w.stride(0),
+        args = (w.data_ptr(), dy.data_ptr(), dx.data_ptr(), pre.data_ptr(), _p(ws), _p(colsum), M, N, K, w.stride(0),
                 dy.stride(0), K, pre.stride(0), _variant_bits() | (0x8000 if pre_is_dgelu else 0), *_split_ws_for(st), st)
         if KTIMER is None:
             call("octmae_linear_dgrad_dgelu", *args)
@@ -997,6 +1035,92 @@ def patch_gather(imgs: torch.Tensor, ids_keep: Optional[torch.Tensor], tp: int, 
     return out
 
 
+def patch_scatter(dpatch: torch.Tensor, ids_keep: Optional[torch.Tensor], shape, tp: int, p: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The adjoint of ``patch_gather``: 16-bit ``dpatch`` [B*nkeep, C*tp*p*p] -> float32 [B, C, T, H, W] = ``shape``; the voxels of a
+    kept token are its row widened exactly, every other voxel is +0.0 (whatever ``out`` held).  ``ids_keep``: int64 or int32
+    [B, nkeep] with distinct ids per sample (the masking kernel's; not checked), or None = tokens 0 .. nkeep-1."""
+    _chk(dpatch, BF16, "patch_scatter dpatch")
+    Bn, Cc, T, Hh, Ww = (int(v) for v in shape)
+    kdim = Cc * tp * p * p
+    if dpatch.dim() != 2 or dpatch.shape[1] != kdim or dpatch.shape[0] % Bn:
+        raise RuntimeError(f"patch_scatter: dpatch {tuple(dpatch.shape)} does not hold whole samples of [nkeep, {kdim}] rows for {Bn} samples")
+    nkeep = dpatch.shape[0] // Bn
+    is64 = 1
+    if ids_keep is not None:
+        if ids_keep.dtype not in (torch.int64, torch.int32):
+            raise RuntimeError(f"patch_scatter ids_keep: expected int64 or int32, got {ids_keep.dtype}")
+        _chk(ids_keep, ids_keep.dtype, "patch_scatter ids_keep")
+        if tuple(ids_keep.shape) != (Bn, nkeep) or ids_keep.device != dpatch.device:
+            raise RuntimeError(f"patch_scatter: ids_keep is {tuple(ids_keep.shape)} on {ids_keep.device}, expected {(Bn, nkeep)} on {dpatch.device}")
+        is64 = int(ids_keep.dtype == torch.int64)
+    if out is None:
+        out = torch.empty((Bn, Cc, T, Hh, Ww), dtype=F32, device=dpatch.device)
+    else:
+        _chk(out, F32, "patch_scatter out")
+        if tuple(out.shape) != (Bn, Cc, T, Hh, Ww) or out.device != dpatch.device:
+            raise RuntimeError(f"patch_scatter: out is {tuple(out.shape)} on {out.device}, expected {(Bn, Cc, T, Hh, Ww)} on {dpatch.device}")
+    # algorithmic HBM bytes: the kept rows read once (2 B), the whole volume written once (4 B)
+    _launch("patch_scatter", 0.0, 2.0 * dpatch.numel() + 4.0 * out.numel(),
+            lambda: call("octmae_patch_scatter", dpatch.data_ptr(), _p(ids_keep), is64, out.data_ptr(), Bn, Cc, T, Hh, Ww, tp, p, nkeep,
+                         _stream()))
+    return out
+
+
+def _chk_stream(t: torch.Tensor, n_prefix: int, name: str):
+    _chk(t, F32, name)
+    if t.dim() != 3 or n_prefix < 0 or t.shape[1] <= n_prefix or t.shape[2] % 4 or t.shape[0] < 1:
+        raise RuntimeError(f"{name}: expected float32 [B, {n_prefix} + L, C] with L >= 1 and C % 4 == 0, got {tuple(t.shape)}")
+    return t.shape[0], t.shape[1] - n_prefix, t.shape[2]
+
+
+def cam_weights(G: torch.Tensor, n_prefix: int = 1) -> torch.Tensor:
+    """Grad-CAM's channel weights: float32 [B, C] = the mean of ``G`` float32 [B, n_prefix + L, C] over its L patch rows (the
+    ``n_prefix`` leading rows -- the cls token -- are not read).  Two deterministic launches; no autograd."""
+    G = G.detach()
+    Bn, L, C = _chk_stream(G, n_prefix, "cam_weights G")
+    n = load().octmae_cam_ws_floats(Bn, L, C)
+    if n < 0:
+        raise RuntimeError(f"cam_weights: unsupported size {tuple(G.shape)}")
+    ws = torch.empty((n,), dtype=F32, device=G.device)
+    w = torch.empty((Bn, C), dtype=F32, device=G.device)
+    _launch("cam_weights", float(Bn * L * C), 4.0 * Bn * L * C + 4.0 * Bn * C,
+            lambda: call("octmae_cam_weights", G.data_ptr(), w.data_ptr(), ws.data_ptr(), Bn, L, n_prefix, C, _stream()))
+    return w
+
+
+def cam_tokens(A: torch.Tensor, w: torch.Tensor, n_prefix: int = 1) -> torch.Tensor:
+    """float32 [B, L]: cam[b, l] = max(0, sum_c w[b, c] * A[b, n_prefix + l, c]) for ``A`` float32 [B, n_prefix + L, C] and the
+    ``cam_weights`` output ``w`` float32 [B, C].  One launch; no autograd."""
+    A, w = A.detach(), w.detach()
+    Bn, L, C = _chk_stream(A, n_prefix, "cam_tokens A")
+    _chk(w, F32, "cam_tokens w")
+    if tuple(w.shape) != (Bn, C) or w.device != A.device:
+        raise RuntimeError(f"cam_tokens: w is {tuple(w.shape)} on {w.device}, expected {(Bn, C)} on {A.device}")
+    cam = torch.empty((Bn, L), dtype=F32, device=A.device)
+    _launch("cam_tokens", 2.0 * Bn * L * C, 4.0 * Bn * L * C + 4.0 * Bn * L,
+            lambda: call("octmae_cam_tokens", A.data_ptr(), w.data_ptr(), cam.data_ptr(), Bn, L, n_prefix, C, _stream()))
+    return cam
+
+
+def heatmap(m: torch.Tensor, size) -> torch.Tensor:
+    """uint8 [B, F, H, W] heat volume of the float32 map ``m`` [B, t, h, w], ``size`` = (F, H, W) with W % 4 == 0: per sample
+    v = (m - min) / (1e-7 + (max - min)) on the coarse map, resampled linearly along t and bilinearly over (h, w)
+    (``F.interpolate``'s align_corners=False positions), then floor(255 v).  A constant map gives zeros.  Two launches; no autograd."""
+    m = m.detach()
+    _chk(m, F32, "heatmap map")
+    Fo, Ho, Wo = (int(v) for v in size)
+    if m.dim() != 4 or min(m.shape) < 1 or min(Fo, Ho, Wo) < 1 or Wo % 4:
+        raise RuntimeError(f"heatmap: expected a float32 [B, t, h, w] map and a size (F, H, W) with W % 4 == 0, got {tuple(m.shape)} and "
+                           f"{(Fo, Ho, Wo)}")
+    Bn, t, h, w = m.shape
+    mnmx = torch.empty((Bn, 2), dtype=F32, device=m.device)
+    out = torch.empty((Bn, Fo, Ho, Wo), dtype=torch.uint8, device=m.device)
+    _launch("heatmap", 0.0, 4.0 * m.numel() + float(out.numel()),
+            lambda: call("octmae_heatmap", m.data_ptr(), mnmx.data_ptr(), out.data_ptr(), Bn, t, h, w, Fo, Ho, Wo, _stream()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd Functions
 # ------------------------------------------------------------------------------------------------
@@ -1022,8 +1146,11 @@ class LayerNormFn(torch.autograd.Function):
         D = x2.shape[1]
         dyb = _as2d_bf16(dy, D)
         colsum = torch.zeros(D, dtype=F32, device=x2.device)
-        dx, dxb = layernorm_bwd(dyb, x2, mean, rstd, gamma, grad_buf(gamma), grad_buf(beta), want_bf16=True, dxsum=colsum)
-        notify_grad_ready((gamma, beta))
+        wg = _weight_grads
+        dx, dxb = layernorm_bwd(dyb, x2, mean, rstd, gamma, grad_buf(gamma) if wg else None, grad_buf(beta) if wg else None,
+                                want_bf16=True, dxsum=colsum)
+        if wg:
+            notify_grad_ready((gamma, beta))
         dx = dx.view(ctx.shp)
         _sidecar_put(dx, dxb.view(ctx.shp), colsum)      # the producing Block's backward takes these instead of redoing them
         return dx, None, None, None
@@ -1053,9 +1180,10 @@ class SlicePoolFn(torch.autograd.Function):
         want_dx = ctx.needs_input_grad[0]
         colsum = torch.zeros(D, dtype=F32, device=dout.device) if want_dx else None
         dx, dxb = slice_pool_bwd(dout, pooled, mean, rstd, gamma, shp[1], S, cls,
-                                 grad_buf(gamma) if ctx.needs_input_grad[1] else None,
-                                 grad_buf(beta) if ctx.needs_input_grad[2] else None, want_bf16=want_dx, dxsum=colsum)
-        notify_grad_ready((gamma, beta))
+                                 grad_buf(gamma) if ctx.needs_input_grad[1] and _weight_grads else None,
+                                 grad_buf(beta) if ctx.needs_input_grad[2] and _weight_grads else None, want_bf16=want_dx, dxsum=colsum)
+        if _weight_grads:
+            notify_grad_ready((gamma, beta))
         if not want_dx:
             return None, None, None, None, None, None
         _sidecar_put(dx, dxb, colsum)      # the producing Block's backward takes these instead of redoing them
@@ -1080,9 +1208,10 @@ class LinearFn(torch.autograd.Function):
         x2, w_lp = ctx.saved_tensors
         N = w_lp.shape[0]
         dyb = _as2d_bf16(dy, N)
-        gw, gb = ctx.gw(), ctx.gb()
-        linear_wgrad_accum(dyb, x2, gw, gb)
-        notify_grad_ready(ctx.params)
+        if _weight_grads:
+            gw, gb = ctx.gw(), ctx.gb()
+            linear_wgrad_accum(dyb, x2, gw, gb)
+            notify_grad_ready(ctx.params)
         dx = linear_dgrad(dyb, w_lp).view(ctx.shp) if ctx.needs_input_grad[0] else None
         return (dx, None, None, None, None, None) + (None,) * len(ctx.params)
 
@@ -1094,18 +1223,28 @@ class PatchEmbedFn(torch.autograd.Function):
     def forward(ctx, imgs, ids_keep, w_lp, b32, gw, gb, tp, p, nkeep, weight, bias):
         patches = patch_gather(imgs, ids_keep, tp, p, nkeep)
         tok = linear_fwd(patches, w_lp, b32, "bf16")
-        ctx.save_for_backward(patches)
+        if ctx.needs_input_grad[0]:      # the image gradient is wanted (saliency): its dgrad needs the weight and the kept ids as well
+            ctx.save_for_backward(patches, w_lp, ids_keep)
+            ctx.geom = (tuple(imgs.shape), tp, p)
+        else:
+            ctx.save_for_backward(patches)
         ctx.gw, ctx.gb, ctx.params = gw, gb, (weight, bias)
         return tok
 
     @staticmethod
     def backward(ctx, dtok):
-        (patches,) = ctx.saved_tensors
+        patches = ctx.saved_tensors[0]
         dyb = _as2d_bf16(dtok, dtok.shape[-1])
-        gw = ctx.gw()
-        linear_wgrad_accum(dyb, patches, gw.view(gw.shape[0], -1), ctx.gb())
-        notify_grad_ready(ctx.params)
-        return (None,) * 11
+        if _weight_grads:
+            gw = ctx.gw()
+            linear_wgrad_accum(dyb, patches, gw.view(gw.shape[0], -1), ctx.gb())
+            notify_grad_ready(ctx.params)
+        dimgs = None
+        if ctx.needs_input_grad[0]:      # adjoint of the gather applied to the GEMM's 16-bit activation gradient
+            _, w_lp, ids_keep = ctx.saved_tensors
+            shape, tp, p = ctx.geom
+            dimgs = patch_scatter(linear_dgrad(dyb, w_lp), ids_keep, shape, tp, p)
+        return (dimgs,) + (None,) * 10
 
 
 class AttentionFn(torch.autograd.Function):
@@ -1135,19 +1274,22 @@ class AttentionFn(torch.autograd.Function):
         y2, qkv, o, lse, wqkv_lp, wproj_lp = ctx.saved_tensors
         Bn, N, H, HD, scale, has_res = ctx.meta
         Cc = H * HD
-        gwqkv, gbqkv, gwproj, gbproj = ctx.grads()
+        wg = _weight_grads
+        gwqkv, gbqkv, gwproj, gbproj = ctx.grads() if wg else (None,) * 4
         d2 = dout.reshape(-1, Cc)
         if not d2.is_contiguous():
             d2 = d2.contiguous()
         dob = cast_bf16(d2)
         if gbproj is not None:
             colsum_accum(d2 if d2.dtype in (F32, BF16) else dob, gbproj)
-        linear_wgrad_accum(dob, o, gwproj)
+        if wg:
+            linear_wgrad_accum(dob, o, gwproj)
         fused_bwd = attn_bwd_use_fused(Bn, H, HD, qkv.device)
         do, delta = linear_dgrad_delta(dob, wproj_lp, o, H, HD) if fused_bwd else (linear_dgrad(dob, wproj_lp), None)
         dqkv = attn_bwd(qkv, o, do, lse, Bn, N, H, HD, scale, fused=fused_bwd, delta=delta)
-        linear_wgrad_accum(dqkv, y2, gwqkv, gbqkv)
-        notify_grad_ready(ctx.params)
+        if wg:
+            linear_wgrad_accum(dqkv, y2, gwqkv, gbqkv)
+            notify_grad_ready(ctx.params)
         dy = linear_dgrad(dqkv, wqkv_lp).view(ctx.shp)
         dres = dout if has_res else None
         return (dy, dres, None, None, None, None, None, None) + (None,) * len(ctx.params)
@@ -1161,7 +1303,7 @@ class MlpFn(torch.autograd.Function):
         shp = y.shape
         Cc = shp[-1]
         y2 = cast_bf16(y.reshape(-1, Cc))
-        ctx.pre_is_dgelu = GELU_PRIME_FWD
+        ctx.pre_is_dgelu, ctx.fc1_bias = GELU_PRIME_FWD, b1_32 is not None
         pre, act = linear_fwd(y2, w1_lp, b1_32, "gelu", store_dgelu=ctx.pre_is_dgelu)
         if res is not None:
             out = linear_fwd(act, w2_lp, b2_32, "resid", res=_chk(res.reshape(-1, Cc), F32, "residual"))
@@ -1175,17 +1317,20 @@ class MlpFn(torch.autograd.Function):
     def backward(ctx, dout):
         y2, pre, act, w1_lp, w2_lp = ctx.saved_tensors
         Cc = ctx.shp[-1]
-        gw1, gb1, gw2, gb2 = ctx.grads()
+        wg = _weight_grads
+        gw1, gb1, gw2, gb2 = ctx.grads() if wg else (None,) * 4
         d2 = dout.reshape(-1, Cc)
         if not d2.is_contiguous():
             d2 = d2.contiguous()
         dob = cast_bf16(d2)
         if gb2 is not None:
             colsum_accum(d2, gb2)
-        linear_wgrad_accum(dob, act, gw2)
-        dpre = linear_dgrad(dob, w2_lp, pre=pre, colsum=gb1, pre_is_dgelu=ctx.pre_is_dgelu)
-        linear_wgrad_accum(dpre, y2, gw1)
-        notify_grad_ready(ctx.params)
+        if wg:
+            linear_wgrad_accum(dob, act, gw2)
+        dpre = linear_dgrad(dob, w2_lp, pre=pre, colsum=gb1, pre_is_dgelu=ctx.pre_is_dgelu, fold_entry=ctx.fc1_bias and not wg)
+        if wg:
+            linear_wgrad_accum(dpre, y2, gw1)
+            notify_grad_ready(ctx.params)
         dy = linear_dgrad(dpre, w1_lp).view(ctx.shp)
         return (dy, dout if ctx.has_res else None, None, None, None, None, None) + (None,) * len(ctx.params)
 
@@ -1253,7 +1398,7 @@ class BlockFn(torch.autograd.Function):
         o, lse = attn_fwd(qkv, Bn, N, H, HD, scale)
         x2 = linear_fwd(o, wproj, bproj, "resid", res=x2d, rowscale=s1, rows_per_scale=N)
         y2, mean2, rstd2 = layernorm_fwd(x2, g2, be2, eps2)
-        ctx.pre_is_dgelu = GELU_PRIME_FWD
+        ctx.pre_is_dgelu, ctx.fc1_bias = GELU_PRIME_FWD, b1 is not None
         pre, act = linear_fwd(y2, w1, b1, "gelu", store_dgelu=ctx.pre_is_dgelu)
         if final_residual:
             x3 = linear_fwd(act, w2, b2, "resid", res=x2, rowscale=s2, rows_per_scale=N)
@@ -1273,7 +1418,8 @@ class BlockFn(torch.autograd.Function):
         x2d, mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act, wqkv, wproj, w1, w2, g1, g2 = ctx.saved_tensors
         Bn, N, H, HD, scale, shp = ctx.meta
         C = H * HD
-        (gg1, gb1n, gg2, gb2n, gwqkv, gbqkv, gwproj, gbproj, gw1, gb1, gw2, gb2) = ctx.grads()
+        wg = _weight_grads      # off: every parameter-gradient side output below is a null pointer, the launches are the same
+        (gg1, gb1n, gg2, gb2n, gwqkv, gbqkv, gwproj, gbproj, gw1, gb1, gw2, gb2) = ctx.grads() if wg else (None,) * 12
         if dx3.dtype != F32 or not dx3.is_contiguous():
             dx3 = dx3.contiguous().float()
         s1, s2 = ctx.scales
@@ -1293,8 +1439,9 @@ class BlockFn(torch.autograd.Function):
             if gb2 is not None:
                 colsum_accum(d3, gb2)
         # ---- MLP
-        dpre = linear_dgrad(d3b, w2, pre=pre, colsum=gb1, pre_is_dgelu=ctx.pre_is_dgelu)          # GELU' and fc1's bias gradient in the epilogue
-        linear_wgrad_accum_pair((d3b, act, gw2, None), (dpre, y2, gw1, None))
+        dpre = linear_dgrad(d3b, w2, pre=pre, colsum=gb1, pre_is_dgelu=ctx.pre_is_dgelu, fold_entry=ctx.fc1_bias and not wg)   # GELU' and fc1's bias gradient in the epilogue
+        if wg:
+            linear_wgrad_accum_pair((d3b, act, gw2, None), (dpre, y2, gw1, None))
         dy2 = linear_dgrad(dpre, w1)
         # ---- LN2 backward + residual add + bf16 copy + proj bias gradient
         if ctx.final_residual:
@@ -1314,12 +1461,14 @@ class BlockFn(torch.autograd.Function):
         dqkv = attn_bwd(qkv, o, do, lse, Bn, N, H, HD, scale, fused=fused_bwd, delta=delta)
         # the qkv bias gradient rides in the weight-gradient GEMM (column sums of its dY operand); fusing it into the attention
         # backward kernels had been measured and dropped (+10..25 % on their main loops for a 2 % pass)
-        linear_wgrad_accum_pair((dx2b, o, gwproj, None), (dqkv, y1, gwqkv, gbqkv))
+        if wg:
+            linear_wgrad_accum_pair((dx2b, o, gwproj, None), (dqkv, y1, gwqkv, gbqkv))
         dy1 = linear_dgrad(dqkv, wqkv)
         # ---- LN1 backward + residual add; its bf16 copy / column sums are what the previous Block's backward needs
         colsum = torch.zeros(C, dtype=F32, device=dx3.device)
         dx, dxb = layernorm_bwd(dy1, x2d, mean1, rstd1, g1, gg1, gb1n, dres=dx2, want_bf16=True, dxsum=colsum)
-        notify_grad_ready(ctx.params)
+        if wg:
+            notify_grad_ready(ctx.params)
         dx = dx.view(shp)
         _sidecar_put(dx, dxb.view(shp), colsum)
         return (dx, None, None, None, None, None, None, None, None) + (None,) * len(ctx.params)
@@ -1363,6 +1512,8 @@ class EncAssembleFn(torch.autograd.Function):
         nkeep = n1 - 1
         dtok = torch.empty((Bn * nkeep, D), dtype=BF16, device=dx.device)
         call("octmae_gather_rows_cast", dx.data_ptr(), None, dtok.data_ptr(), Bn, nkeep, n1, D, _stream())
+        if not _weight_grads:        # no positional / cls table gradient
+            return dtok, None, None, None, None, None
         if ctx.has_restore:
             L = ids_restore.shape[1]
             dpos = torch.empty(ctx.pos_shape, dtype=F32, device=dx.device)
@@ -1409,6 +1560,8 @@ class DecAssembleFn(torch.autograd.Function):
         else:
             demb = torch.empty((Bn * nkeep, D), dtype=BF16, device=dx.device)
             call("octmae_gather_rows_cast", dx.data_ptr(), ids_keep.data_ptr(), demb.data_ptr(), Bn, nkeep, L1, D, _stream())
+        if not _weight_grads:        # no mask-token, positional / cls table gradient
+            return demb, None, None, None, None, None, None
         if Bn <= 1024 and D % 4 == 0:
             # one pass over dx: positional-table gradient and, per table row, the sum over the samples that masked it
             L = L1 - 1
@@ -1446,6 +1599,12 @@ class PatchMSEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dl):
+        if ctx.needs_input_grad[1]:
+            # the reference's loss is differentiable through its target patchify(imgs) as well; that term is not built, and the
+            # encoder-side gradient alone would be a partial one
+            raise RuntimeError("PatchMSEFn: the gradient of the reconstruction loss with respect to imgs was requested, but the "
+                               "term through the loss target patchify(imgs) is not implemented; detach imgs (the pre-training step "
+                               "never needs this gradient)")
         pred_full, imgs, frame_idx = ctx.saved_tensors
         u_sz, p, norm_pix, has_fi = ctx.meta
         Bn, L1, PD = pred_full.shape
