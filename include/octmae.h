@@ -43,8 +43,10 @@ extern "C" {
  * 21: octmae_rank_counts_masked (rank counts over a per-column population: the multi-task evaluation, csrc/metrics.hip).
  * 22: octmae_image_stats, octmae_image_augment, octmae_aug_desc (RandAugment's image operations on the device, csrc/augment2d.hip).
  * 23: octmae_patch_scatter, octmae_cam_weights (+ octmae_cam_ws_floats), octmae_cam_tokens, octmae_heatmap (input gradients, Grad-CAM
- *     and heat volumes, csrc/saliency.hip). */
-#define OCTMAE_ABI_VERSION 23
+ *     and heat volumes, csrc/saliency.hip).
+ * 24: octmae_clip_loss_fwd, octmae_clip_loss_bwd (+ octmae_clip_loss_ws_floats): the contrastive loss of the COEM training step and its
+ *     gradients off f32 MFMA tiles, csrc/cliploss.hip. */
+#define OCTMAE_ABI_VERSION 24
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -493,6 +495,40 @@ int octmae_rank_counts_masked(const float* scores, long long score_stride, const
 int octmae_retrieval_ranks(const float* a, long long a_stride, const float* b, long long b_stride, const int* target,
                            const uint8_t* keep, const int* row_group, const int* col_group, int* out, long long n, long long m,
                            int d, void* stream);
+
+/* ---- contrastive loss of the COEM training step (csrc/cliploss.hip) ---------------------------------
+ * retinal-COEM/src/open_clip/loss.py:148-230 (ClipLoss) and :230-385 (ThreeModalityClipLoss) form logit_scale * a @ b.T, its transpose,
+ * cross entropies of both and leave the backward to autograd: the [n][m] logits, their softmax and their gradient are stored each time.
+ * These entry points walk the same product on f32 MFMA tiles (the walk of octmae_retrieval_ranks) and store none of them.
+ *   a       f32 [n][d], rows a_stride ELEMENTS apart (>= d);  b  f32 [m][d], rows b_stride elements apart (>= d)
+ *   s(i, j) the f32 chain acc = 0; for k = 0 .. d-1: acc = fmaf(a[i][k], b[j][k], acc), as octmae_retrieval_ranks
+ *   z(i, j) = scale[0] * s(i, j), one f32 rounding; scale is a DEVICE pointer (no host synchronisation)
+ *   the partner of row i is column t_i = i + offset (offset: a host integer, 0 except for local_loss on a rank > 0)
+ *   wr      f32 [n] row weights;  wc  f32 [n] pair weights of the column direction, NULL = that direction is off
+ *     L = sum_i wr[i] (lse_j z(i, j) - z(i, t_i))  +  sum_i wc[i] (lse_i' z(i', t_i) - z(i, t_i))
+ *   n == m, offset 0, wr = wc = 1 / (2 n): the reference's ClipLoss; wc == NULL: one cross entropy of a rectangular logit block.
+ * octmae_clip_loss_fwd writes lse_row f32 [n], lse_col f32 [m] (over ALL n rows, for every column; only with wc), tscore f32 [n] =
+ * s(i, t_i) (the tile's own bits) and loss f32 [1].  Online maximum and sum over 64-column tiles: any finite z works, whatever its range.
+ * octmae_clip_loss_bwd, with G(i, j) = wr[i] (p - [j == t_i]) + wc[j - offset] (q - [j == t_i]), p = exp(z - lse_row[i]),
+ * q = exp(z - lse_col[j]) (0 for a column that is nobody's partner), writes
+ *   da f32 [n][d] = gout[0] scale G b,  db f32 [m][d] = gout[0] scale G^T a  (rows da_stride / db_stride elements apart),
+ *   dscale f32 [1] = gout[0] sum G o s;  gout: the upstream scalar, a DEVICE pointer.  Each of da, db, dscale may be NULL (not computed).
+ * s is recomputed per tile from the saved log-sum-exps.  DETERMINISTIC: no float atomics, every output element is summed in a fixed
+ * order (the loss and dscale in float64 by one workgroup), two runs are bit-equal.  A NaN or Inf feature gives a NaN loss and NaN in
+ * the gradients it reaches; nothing raises or waits on the values.  exp / log: the device library's expf / logf.  No 16-bit operand,
+ * no fast-math flag, no contraction: the same code in the two builds of the library.
+ *   ws      f32 workspace of at least octmae_clip_loss_ws_floats(n, m) elements (the forward's per-workgroup (max, sum) partials; the
+ *           backward keeps its n dscale partials there); the query returns -2 where n or m is <= 0 or the count passes 2^31 - 1.
+ * -2, before any launch: a NULL a / b / scale / wr / output (lse_col only with wc) / ws, n, m or d <= 0, a stride below d,
+ * offset < 0 or n + offset > m (host integers: no device read), n or m above 2^31 - 1, a workspace below the query. */
+int octmae_clip_loss_ws_floats(long long n, long long m);
+int octmae_clip_loss_fwd(const float* a, long long a_stride, const float* b, long long b_stride, const float* scale, const float* wr,
+                         const float* wc, long long offset, float* lse_row, float* lse_col, float* tscore, float* loss, float* ws,
+                         long long ws_floats, long long n, long long m, int d, void* stream);
+int octmae_clip_loss_bwd(const float* a, long long a_stride, const float* b, long long b_stride, const float* scale, const float* wr,
+                         const float* wc, long long offset, const float* lse_row, const float* lse_col, const float* gout, float* da,
+                         long long da_stride, float* db, long long db_stride, float* dscale, float* ws, long long ws_floats, long long n,
+                         long long m, int d, void* stream);
 
 /* ---- mixup / cutmix of a fine-tune batch (csrc/mixup.hip) ---------------------------------------------
  * timm.data.Mixup's three modes on the device, in place, in one launch; the decisions are the host's (octcubem_amd/mixup.py).

@@ -5,7 +5,9 @@
 
 The towers are the 3-D ST ViT (``models_vit_st``, OCT volume) and the 2-D ViT (``models_vit``, IR image) of this package; their
 ``head`` is the projection to the shared embedding.  The loss acts on ``[B, embed]`` features: a ``[B_global, B_global]``
-logits matmul and two cross-entropies -- a few MFLOP next to the towers' TFLOPs, left to ATen on the device.  With
+logits matmul and two cross-entropies -- a few MFLOP next to the towers' TFLOPs, left to ATen on the device by default
+(``fused=True``: ops.clip_pair_loss, csrc/cliploss.hip, which stores no ``[n, m]`` array).  The epoch loop with the reference's
+cached-feature accumulation is ``train_one_epoch`` / ``train_one_epoch_3modalities`` below.  With
 ``world_size > 1`` the features of all ranks are exchanged by ONE all-gather per tower (RCCL over xGMI; gloo in the CPU tests),
 differentiable when ``gather_with_grad`` (its backward is a reduce-scatter of the feature gradients)."""
 from __future__ import annotations
@@ -87,10 +89,20 @@ def gather_features(image_features, enface_features, local_loss=False, gather_wi
     return torch.cat(gi, dim=0), torch.cat(ge, dim=0)
 
 
+def _rows(x):
+    """a feature matrix as ops.clip_pair_loss takes it: unit column stride (a row-strided slice is passed as it is)"""
+    return x if x.dim() != 2 or x.shape[1] == 1 or x.stride(1) == 1 else x.contiguous()
+
+
 @autocast_invariant
 class ClipLoss(nn.Module):
+    """``fused=True``: the same gather and the same partners, with the logits / cross-entropy part and its autograd replaced by
+    ops.clip_pair_loss (csrc/cliploss.hip: no [n, m] array, deterministic) -- one call for the single-process and the gathered
+    non-local case, two rectangular calls under ``local_loss``.  ``correct_label`` (soft labels from duplicate reports) keeps the ATen
+    path whatever ``fused`` says.  ``fused=False`` (default) is the ATen composition, unchanged."""
+
     def __init__(self, local_loss=False, gather_with_grad=False, cache_labels=False, rank=0, world_size=1, use_horovod=False,
-                 correct_label=0):
+                 correct_label=0, fused=False):
         super().__init__()
         self.local_loss = local_loss
         self.gather_with_grad = gather_with_grad
@@ -99,8 +111,34 @@ class ClipLoss(nn.Module):
         self.world_size = world_size
         self.use_horovod = use_horovod
         self.correct_label = correct_label
+        self.fused = fused
         self.prev_num_logits = 0
         self.labels = {}
+        self._fused_w = {}
+
+    def _forward_fused(self, image_features, enface_features, logit_scale):
+        from . import ops
+        if self.world_size > 1:
+            all_image, all_enface = gather_features(image_features, enface_features, self.local_loss, self.gather_with_grad,
+                                                    self.rank, self.world_size, self.use_horovod)
+            if self.local_loss:
+                n = image_features.shape[0]
+                w = self._uniform(n, image_features.device)
+                off = n * self.rank              # labels = arange(num_logits) + num_logits * rank
+                return (ops.clip_pair_loss(_rows(image_features), _rows(all_enface), logit_scale, w, None, off)
+                        + ops.clip_pair_loss(_rows(enface_features), _rows(all_image), logit_scale, w, None, off))
+            image_features, enface_features = all_image, all_enface
+        w = self._uniform(image_features.shape[0], image_features.device)
+        return ops.clip_pair_loss(_rows(image_features), _rows(enface_features), logit_scale, w, w, 0)
+
+    def _uniform(self, n, device):
+        """1 / (2 n) per row: the mean of each cross entropy and the halving of their sum"""
+        w = self._fused_w.get((n, device)) if self.cache_labels else None
+        if w is None:
+            w = torch.full((n,), 0.5 / n, dtype=torch.float32, device=device)
+            if self.cache_labels:
+                self._fused_w = {(n, device): w}
+        return w
 
     def get_corrected_label(self, enface_features_i, enface_features_j, t=10 ** (-100)):
         """Soft labels that share the target mass among samples with IDENTICAL en-face features (same report)."""
@@ -109,6 +147,8 @@ class ClipLoss(nn.Module):
         return L / torch.sum(L, dim=1, keepdim=True)
 
     def forward(self, image_features, enface_features, logit_scale):
+        if self.fused and not self.correct_label:
+            return self._forward_fused(image_features, enface_features, logit_scale)
         device = image_features.device
         if self.world_size > 1:
             all_image, all_enface = gather_features(image_features, enface_features, self.local_loss, self.gather_with_grad,
@@ -163,10 +203,15 @@ class ThreeModalityClipLoss(nn.Module):
     """open_clip/loss.py:230-385: symmetric InfoNCE over the three pairs (OCT, en-face 1), (OCT, en-face 2), (en-face 1,
     en-face 2) with one temperature per pair; a sample whose modality is missing carries weight 0 in that modality's terms
     (t_weight1 / t_weight2, per sample), each term is a weighted mean over the samples present, 0 when none is; the total is
-    the mean of the six directed terms."""
+    the mean of the six directed terms.
+
+    ``fused=True``: three ops.clip_pair_loss calls (six rectangular ones under ``local_loss``) with the weights w / (6 sum w) built on the
+    device -- a modality absent from the whole batch contributes 0 without the host read of the ATen path.  The ``local_loss`` partners
+    are taken as the ATen path forms them (the reference's GLOBAL-count offset); where that puts a partner out of range the fused path
+    raises ValueError (``cross_entropy`` raises its own error there).  ``correct_label`` keeps the ATen path whatever ``fused`` says."""
 
     def __init__(self, local_loss=False, gather_with_grad=False, cache_labels=False, rank=0, world_size=1, use_horovod=False,
-                 correct_label=0):
+                 correct_label=0, fused=False):
         super().__init__()
         self.local_loss = local_loss
         self.gather_with_grad = gather_with_grad
@@ -175,8 +220,36 @@ class ThreeModalityClipLoss(nn.Module):
         self.world_size = world_size
         self.use_horovod = use_horovod
         self.correct_label = correct_label
+        self.fused = fused
         self.prev_num_logits = 0
         self.labels = {}
+
+    def _forward_fused(self, image_features, enface1_features, enface2_features, logit_scale, logit_scale1, logit_scale2, t_weight1,
+                       t_weight2):
+        from . import ops
+        if self.world_size > 1:
+            all_i, all_e1, all_e2, all_w1, all_w2 = gather_features_3mod(
+                image_features, enface1_features, enface2_features, t_weight1, t_weight2, self.local_loss, self.gather_with_grad,
+                self.rank, self.world_size, self.use_horovod)
+        else:
+            all_i, all_e1, all_e2, all_w1, all_w2 = image_features, enface1_features, enface2_features, t_weight1, t_weight2
+
+        def share(w):                  # w / (6 sum w), 0 where the modality is absent from the whole batch: no host read
+            w = w.detach().to(torch.float32)
+            tot = w.sum()
+            return torch.where(tot > 0, w / (6.0 * tot), torch.zeros_like(w))
+        f = _rows
+        if self.local_loss:
+            off = all_i.shape[0] * self.rank if self.world_size > 1 else 0      # the GLOBAL count, as the ATen path (and the reference)
+            w1, w2 = share(t_weight1), share(t_weight2)
+            w12 = share(t_weight1 * t_weight2)
+            pairs = ((image_features, all_e1, logit_scale, w1), (enface1_features, all_i, logit_scale, w1),
+                     (image_features, all_e2, logit_scale1, w2), (enface2_features, all_i, logit_scale1, w2),
+                     (enface1_features, all_e2, logit_scale2, w12), (enface2_features, all_e1, logit_scale2, w12))
+            return sum(ops.clip_pair_loss(f(a), f(b), sc, w, None, off) for a, b, sc, w in pairs)
+        w1, w2, w12 = share(all_w1), share(all_w2), share(all_w1 * all_w2)
+        return (ops.clip_pair_loss(f(all_i), f(all_e1), logit_scale, w1, w1, 0) + ops.clip_pair_loss(f(all_i), f(all_e2), logit_scale1, w2, w2, 0)
+                + ops.clip_pair_loss(f(all_e1), f(all_e2), logit_scale2, w12, w12, 0))
 
     @staticmethod
     def get_corrected_label(features_i, features_j, t=1e-10):
@@ -191,6 +264,9 @@ class ThreeModalityClipLoss(nn.Module):
 
     def forward(self, image_features, enface1_features, enface2_features, logit_scale, logit_scale1, logit_scale2, t_weight1,
                 t_weight2):
+        if self.fused and not self.correct_label:
+            return self._forward_fused(image_features, enface1_features, enface2_features, logit_scale, logit_scale1, logit_scale2,
+                                       t_weight1, t_weight2)
         device = image_features.device
         if self.world_size > 1:
             all_i, all_e1, all_e2, all_w1, all_w2 = gather_features_3mod(
@@ -361,6 +437,290 @@ def train_step(model, loss_fn, images, texts, optimizers, loss_scalers=None, cli
         o.step()
     clamp_logit_scale(model)
     return loss.detach()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the epoch loop (training/train_retclip.py:64-240, train_retclip_3modalities.py:74-276) and its schedule (training/scheduler.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _optimizer_list(optimizers):
+    return list(optimizers) if isinstance(optimizers, (list, tuple)) else [optimizers]
+
+
+def assign_learning_rate(optimizer, new_lr):
+    """scheduler.assign_learning_rate; ``optimizer`` may be a list (one optimizer per tower arena and one for the temperature)."""
+    for o in _optimizer_list(optimizer):
+        for param_group in o.param_groups:
+            param_group["lr"] = new_lr
+
+
+def _warmup_lr(base_lr, warmup_length, step):
+    return base_lr * (step + 1) / warmup_length
+
+
+def cosine_lr(optimizer, base_lr, warmup_length, steps):
+    """scheduler.cosine_lr: linear warm-up over ``warmup_length`` steps, then half a cosine down to 0 at ``steps``."""
+    def _lr_adjuster(step):
+        if step < warmup_length:
+            lr = _warmup_lr(base_lr, warmup_length, step)
+        else:
+            e = step - warmup_length
+            es = steps - warmup_length
+            lr = 0.5 * (1 + np.cos(np.pi * e / es)) * base_lr
+        assign_learning_rate(optimizer, lr)
+        return lr
+    return _lr_adjuster
+
+
+# The loop's default for ``fused``: the path profiles/cliploss_bench.txt shows faster at the shipped local-loss shape (32 local rows
+# against 256 gathered columns, two calls, forward + backward, d = 512): the ATen composition at 387 us per call against 819 us for the
+# fused path on an MI355X -- so False.  (The fused path is the faster one only at n = m = 64, and holds 33 x less memory at n = 8192.)
+FUSED_DEFAULT = False
+
+
+class AverageMeter:
+    """train_retclip.AverageMeter"""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.val = 0
+        self.avg = 0
+        self.sum = 0
+        self.count = 0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum += val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+def stack_weight_modalities(weight_modalities):
+    """train_retclip_3modalities.stack_weight_modalities: [accum step][modality] -> [modality], concatenated over the steps."""
+    return [torch.cat([step[i] for step in weight_modalities], dim=0) for i in range(len(weight_modalities[0]))]
+
+
+def convert_modalities_idx_to_flag(modalities):
+    """The per-sample presence weights of one modality as a float32 tensor.  (The reference imports this helper from open_clip/misc.py,
+    a module it does not ship; its loss uses the result as a 0 / 1 weight per sample, which is what the loader's flags are.)"""
+    return torch.as_tensor(modalities).to(torch.float32)
+
+
+def _refuse_unsupported(name, scaler, args):
+    if scaler is not None:
+        raise NotImplementedError(f"{name}: a GradScaler is not run by this package (the kernels keep fp32 gradients on bfloat16 operands; "
+                                  "pass scaler=None)")
+    if getattr(args, "horovod", False):
+        raise NotImplementedError(f"{name}: horovod is not supported (one process per GPU under torch.distributed)")
+    if getattr(args, "wandb", False):
+        raise NotImplementedError(f"{name}: wandb logging is not part of this package (pass a tb_writer)")
+    precision = getattr(args, "precision", None)
+    if precision not in (None, "fp32", "amp", "amp_bf16", "amp_bfloat16"):
+        raise NotImplementedError(f"{name}: precision {precision!r} casts the inputs to a 16-bit type, which this package does not run "
+                                  "(the kernels choose their own operand precision; use 'amp', 'amp_bf16' or 'fp32')")
+
+
+def _average_temperature_grads(model, reducers):
+    """the scalar temperature gradients are averaged over ranks once per optimizer step (DistributedDataParallel's job in the reference)"""
+    if not reducers or reducers[0].world <= 1:
+        return
+    m = getattr(model, "module", model)
+    for name in ("logit_scale", "logit_scale1", "logit_scale2"):
+        g = getattr(getattr(m, name, None), "grad", None)
+        if g is None:
+            continue
+        nc = _native_comm(g)
+        if nc is not None:
+            from . import comm as _comm
+            nc.all_reduce_async(g, _comm.AVG)
+            nc.wait()
+        else:
+            dist.all_reduce(g)
+            g.div_(reducers[0].world)
+
+
+def _run_epoch(name, three, model, data, epoch, optimizers, scaler, scheduler, args, tb_writer, reducers, loss, fused):
+    import logging
+    import time
+    _refuse_unsupported(name, scaler, args)
+    mm = getattr(args, "multimodal_type", "default") or "default"
+    allowed = ("oct_faf_ir",) if three else ("default", "oct_ir", "oct_faf_only")
+    if mm not in allowed:
+        raise NotImplementedError(f"{name}: multimodal_type {mm!r} is not supported (only {', '.join(repr(a) for a in allowed)})")
+    optimizers = _optimizer_list(optimizers)
+    device = torch.device(args.device)
+    accum_freq = int(getattr(args, "accum_freq", 1))
+    rank, world_size = getattr(args, "rank", 0), getattr(args, "world_size", 1)
+    is_master = rank == 0
+    clip = getattr(args, "grad_clip_norm", None)
+    model.train()
+    if loss is None:
+        cls = ThreeModalityClipLoss if three else ClipLoss
+        loss = cls(local_loss=getattr(args, "local_loss", False), gather_with_grad=getattr(args, "gather_with_grad", False),
+                   cache_labels=True, rank=rank, world_size=world_size, use_horovod=False,
+                   correct_label=getattr(args, "correct_label", 0), fused=FUSED_DEFAULT if fused is None else bool(fused))
+
+    data["train"].set_epoch(epoch)
+    dataloader = data["train"].dataloader
+    num_batches_per_epoch = dataloader.num_batches // accum_freq
+    sample_digits = math.ceil(math.log(dataloader.num_samples + 1, 10))
+    total_train_batch_size = accum_freq * args.batch_size * world_size
+    log_every = getattr(args, "log_every_n_steps", 100)
+    unwrapped = getattr(model, "module", model)
+    accum_inputs, accum_features, accum_weights = [], [], []
+    record = {"losses": [], "micro_losses": [], "steps": 0}
+
+    def unpack(batch):
+        """-> (model inputs on the device, per-sample weights [oct, ir, faf] or None)"""
+        if mm == "default":
+            images, texts = batch
+            inputs, weights = (images, texts), None
+        else:
+            images, texts_ir, texts_f2_faf = batch[0]["oct"], batch[0]["ir"], batch[0]["f2_faf"]
+            modalities = batch[1][2]
+            if mm == "oct_ir":
+                inputs, weights = (images, texts_ir), None
+            elif mm == "oct_faf_only":
+                assert sum(modalities[2]) == len(modalities[2]), "Only f2_faf is allowed in this setting"
+                inputs, weights = (images, texts_f2_faf), None
+            else:
+                inputs = (images, texts_ir, texts_f2_faf)
+                weights = [convert_modalities_idx_to_flag(mod) for mod in modalities[:3]]
+        return tuple(x.to(device=device, non_blocking=True) for x in inputs), weights
+
+    def micro_loss(inputs, j, weights):
+        """forward with a graph; the fresh features spliced at position j among the cached ones (all of them fresh when nothing is cached)"""
+        out = model(*inputs)
+        nf = len(inputs)
+        feats, scales = out[:nf], out[nf:]
+        if accum_features:
+            feats = [torch.cat(accum_features[k][:j] + [feats[k]] + accum_features[k][j + 1:]) for k in range(nf)]
+        if three:
+            return loss(*feats, *scales, t_weight1=weights[1], t_weight2=weights[2]), scales[0]
+        return loss(*feats, *scales), scales[0]
+
+    loss_m, batch_time_m, data_time_m = AverageMeter(), AverageMeter(), AverageMeter()
+    end = time.time()
+    for i, batch in enumerate(dataloader):
+        i_accum = i // accum_freq
+        step = num_batches_per_epoch * epoch + i_accum
+        inputs, weights = unpack(batch)
+        if not getattr(args, "skip_scheduler", False):
+            scheduler(step)
+        data_time_m.update(time.time() - end)
+
+        if accum_freq == 1 and not three:
+            logit_scale = unwrapped.logit_scale.detach().exp()
+            total_loss = train_step(model, loss, inputs[0], inputs[1], optimizers, clip_grad=clip, reducers=reducers)
+            micro = [total_loss]
+        else:
+            if accum_freq > 1:
+                # first, the features of this batch without a graph
+                with torch.no_grad():
+                    out = model(*inputs)
+                if not accum_features:
+                    accum_features = [[] for _ in inputs]
+                for k in range(len(inputs)):
+                    accum_features[k].append(out[k])
+                accum_inputs.append(inputs)
+                accum_weights.append(weights)
+                if ((i + 1) % accum_freq) > 0:
+                    continue
+            else:
+                accum_inputs, accum_weights = [inputs], [weights]
+            for o in optimizers:
+                o.zero_grad()
+            stacked = None
+            if three:
+                stacked = [w.to(device=device, non_blocking=True) for w in stack_weight_modalities(accum_weights)]
+            micro = []
+            for j in range(accum_freq):
+                total_loss, logit_scale = micro_loss(accum_inputs[j], j, stacked)
+                if reducers:
+                    for r in reducers:
+                        r.begin_backward(sync=(j == accum_freq - 1))
+                total_loss.backward()
+                micro.append(total_loss.detach())
+            if reducers:
+                for r in reducers:
+                    r.finish()
+                _average_temperature_grads(model, reducers)
+            if clip is not None:
+                torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], clip, norm_type=2.0)
+            for o in optimizers:
+                o.step()
+            accum_inputs, accum_features, accum_weights = [], [], []
+            clamp_logit_scale(model)
+            total_loss, logit_scale = micro[-1], logit_scale.detach()
+        record["losses"].append(total_loss)
+        record["micro_losses"].append(micro)
+        record["steps"] += 1
+
+        batch_time_m.update(time.time() - end)
+        end = time.time()
+        batch_count = i_accum + 1
+        if is_master and (i_accum % log_every or batch_count == num_batches_per_epoch):
+            batch_size = len(inputs[0])
+            num_samples = batch_count * batch_size * world_size * accum_freq
+            samples_per_epoch = dataloader.num_samples
+            percent_complete = 100.0 * batch_count / num_batches_per_epoch
+            # NOTE loss is coarsely sampled, just master node and per log update
+            loss_m.update(total_loss.item(), batch_size)
+            logit_scale_scalar = logit_scale.item()
+            lr = optimizers[0].param_groups[0]["lr"]
+            logging.info(
+                f"Train Epoch: {epoch} [{num_samples:>{sample_digits}}/{samples_per_epoch} ({percent_complete:.0f}%)] "
+                f"Loss: {loss_m.val:#.5g} ({loss_m.avg:#.4g}) "
+                f"Data (t): {data_time_m.avg:.3f} "
+                f"Batch (t): {batch_time_m.avg:.3f}, {total_train_batch_size / batch_time_m.val:#g}/s "
+                f"LR: {lr:5f} "
+                f"Logit Scale: {logit_scale_scalar:.3f}")
+            log_data = {"loss": loss_m.val, "data_time": data_time_m.val, "batch_time": batch_time_m.val,
+                        "samples_per_second": total_train_batch_size / batch_time_m.val, "scale": logit_scale_scalar, "lr": lr}
+            for key, val in log_data.items():
+                if tb_writer is not None:
+                    tb_writer.add_scalar("train/" + key, val, step)
+            batch_time_m.reset()
+            data_time_m.reset()
+    return record
+
+
+def train_one_epoch(model, data, epoch, optimizers, scaler, scheduler, args, tb_writer=None, reducers=None, loss=None, fused=None):
+    """training/train_retclip.py:64-240 in its order of operations: ``data['train'].set_epoch(epoch)``, ``dataloader.num_batches //
+    args.accum_freq`` optimizer steps, ``scheduler(step)`` unless ``args.skip_scheduler``, ``args.grad_clip_norm``, the ``logit_scale``
+    clamp, the reference's log line and ``tb_writer`` scalars (``train/loss``, ``data_time``, ``batch_time``, ``samples_per_second``,
+    ``scale``, ``lr``).  ``args.multimodal_type``: 'default' (batch = (images, texts)), 'oct_ir', 'oct_faf_only' (batch =
+    ({'oct', 'ir', 'f2_faf'}, (names, dataset index, modalities, h))); anything else raises NotImplementedError.
+
+    ``accum_freq == 1`` is ``train_step``.  ``accum_freq > 1`` is open_clip's cached-feature accumulation, what every training script
+    of the reference runs (``--accum-freq 4`` / ``8``): the features of ``accum_freq`` batches are cached under ``torch.no_grad()``;
+    then every batch is run again with a graph, its fresh features spliced at its own position among the cached ones, so the loss sees
+    the whole contrastive batch; one backward each, ONE optimizer step, the caches cleared.  A trailing incomplete group is dropped.
+    Every micro-step's loss is the full-batch loss, so the tower gradients add up to the full-batch gradient while ``logit_scale.grad``
+    ends up ``accum_freq`` times the full-batch derivative -- as in the reference, kept.
+
+    ``optimizers``: one optimizer or a list (one per tower arena and one for the temperature); ``scheduler`` as ``cosine_lr`` builds it.
+    ``reducers`` (``make_reducers``): ``begin_backward(sync=False)`` on every micro-step but the last, ``sync=True`` on the last and
+    ``finish()`` once -- the result of the reference's exchange on every micro-step at 1 / accum_freq of the traffic (parallel.py); the
+    temperature's gradient is averaged once, after the last micro-step.  Refused by name: a ``scaler`` (no GradScaler is run here),
+    ``args.horovod``, ``args.wandb``, and the pure 16-bit ``args.precision`` values ('fp16', 'bf16'); under 'amp*' nothing is cast, the
+    package is autocast-invariant.  The loss is built once per epoch as the reference builds it (``cache_labels=True``, rank / world size
+    from ``args``); ``loss=`` replaces it by any callable of the same signature (tests), ``fused=`` chooses ``ClipLoss(fused=...)``,
+    default ``FUSED_DEFAULT`` = False: at the shipped local-loss shape (32 x 256, two calls) the ATen composition measured 387 us per
+    forward + backward on an MI355X and the fused path 819 us (profiles/cliploss_bench.txt).  Returns ``{"losses": [the last micro-step's loss of every optimizer step], "micro_losses": [[...]],
+    "steps": n}`` (detached device tensors; the reference returns nothing)."""
+    return _run_epoch("train_one_epoch", False, model, data, epoch, optimizers, scaler, scheduler, args, tb_writer, reducers, loss, fused)
+
+
+def train_one_epoch_3modalities(model, data, epoch, optimizers, scaler, scheduler, args, tb_writer=None, reducers=None, loss=None,
+                                fused=None):
+    """training/train_retclip_3modalities.py:74-276: the same loop for ``args.multimodal_type == 'oct_faf_ir'`` -- ``model(oct, ir, faf)``
+    returns three feature matrices and three temperatures, the loss is ``ThreeModalityClipLoss`` with the per-sample presence weights
+    of the IR and FAF modalities (``batch[1][2]``: one flag vector per modality), which the accumulation caches per batch and
+    concatenates over the group (``stack_weight_modalities``) beside the features.  Everything else as ``train_one_epoch``."""
+    return _run_epoch("train_one_epoch_3modalities", True, model, data, epoch, optimizers, scaler, scheduler, args, tb_writer, reducers,
+                      loss, fused)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -848,6 +848,106 @@ def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Ten
     return out
 
 
+from ._autocast import no_autocast as _no_autocast  # noqa: E402
+
+
+class ClipPairLossFn(torch.autograd.Function):
+    """The checked operands of ``clip_pair_loss`` through octmae_clip_loss_fwd / _bwd (csrc/cliploss.hip).  Saved for the backward:
+    the operands and the two log-sum-exp vectors -- nothing of size [n, m]."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, wr, wc, offset):
+        n, d = a.shape
+        m = b.shape[0]
+        sa = a.stride(0) if n > 1 else d
+        sb = b.stride(0) if m > 1 else d
+        dev = a.device
+        lse_row = torch.empty(n, dtype=F32, device=dev)
+        lse_col = torch.empty(m, dtype=F32, device=dev) if wc is not None else None
+        tscore = torch.empty(n, dtype=F32, device=dev)
+        loss = torch.empty((), dtype=F32, device=dev)
+        nws = load().octmae_clip_loss_ws_floats(n, m)
+        if nws < 0:
+            raise ValueError(f"clip_pair_loss: n = {n}, m = {m} is beyond the kernel's workspace")
+        ws = torch.empty(nws, dtype=F32, device=dev)
+        # algorithmic HBM bytes: a and b read once per side that walks them (the re-reads per tile hit the caches)
+        _launch("clip_pair_loss", (4.0 if wc is not None else 2.0) * n * m * d, float(4 * (n + m) * d * (2 if wc is not None else 1)),
+                lambda: call("octmae_clip_loss_fwd", a.data_ptr(), sa, b.data_ptr(), sb, scale.data_ptr(), wr.data_ptr(), _p(wc), offset,
+                             lse_row.data_ptr(), _p(lse_col), tscore.data_ptr(), loss.data_ptr(), ws.data_ptr(), nws, n, m, d, _stream()))
+        ctx.save_for_backward(a, b, scale, wr, wc, lse_row, lse_col)
+        ctx.offset = offset
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, scale, wr, wc, lse_row, lse_col = ctx.saved_tensors
+        n, d = a.shape
+        m = b.shape[0]
+        sa = a.stride(0) if n > 1 else d
+        sb = b.stride(0) if m > 1 else d
+        dev = a.device
+        g = g.detach().to(F32).contiguous()
+        need_a, need_b, need_s = ctx.needs_input_grad[:3]
+        da = torch.empty((n, d), dtype=F32, device=dev) if need_a else None
+        db = torch.empty((m, d), dtype=F32, device=dev) if need_b else None
+        ds = torch.empty((), dtype=F32, device=dev) if need_s else None
+        ws = torch.empty(n, dtype=F32, device=dev) if need_s else None
+        if need_a or need_b or need_s:
+            sides = (2.0 if need_a or need_s else 0.0) + (2.0 if need_b else 0.0)
+            _launch("clip_pair_loss_bwd", sides * 2.0 * n * m * d, float(4 * (n + m) * d * 3),
+                    lambda: call("octmae_clip_loss_bwd", a.data_ptr(), sa, b.data_ptr(), sb, scale.data_ptr(), wr.data_ptr(), _p(wc), ctx.offset,
+                                 lse_row.data_ptr(), _p(lse_col), g.data_ptr(), _p(da), d, _p(db), d, _p(ds), _p(ws), n if need_s else 0, n, m,
+                                 d, _stream()))
+        return da, db, (ds.reshape(scale.shape) if need_s else None), None, None, None
+
+
+@_no_autocast
+def clip_pair_loss(a: torch.Tensor, b: torch.Tensor, logit_scale, wr: torch.Tensor, wc: Optional[torch.Tensor] = None,
+                   offset: int = 0) -> torch.Tensor:
+    """The scalar  L = sum_i wr[i] (lse_j z(i, j) - z(i, t_i)) + sum_i wc[i] (lse_i' z(i', t_i) - z(i, t_i))  with z = logit_scale * a @ b.T
+    in the kernel's f32 arithmetic (s(i, j) the fmaf chain over k of csrc/retrieval.hip) and t_i = i + offset the partner column of row i;
+    the second sum only when ``wc`` is given.  ``a`` float32 [n, d], ``b`` float32 [m, d] (slices of wider buffers are fine: unit column
+    stride, any row stride >= d), ``logit_scale`` a float32 GPU scalar (0-dim or one element; read on the device), ``wr`` / ``wc`` float32
+    [n].  n == m, offset 0, wr = wc = 1 / (2 n) is the reference's ClipLoss (open_clip/loss.py:148-230); without ``wc`` it is one
+    ``cross_entropy(reduction='sum')`` with per-row weights of the rectangular block (``local_loss``: offset = local batch * rank).
+    Gradients for ``a``, ``b`` and ``logit_scale``, none for the weights; the [n, m] logits are never stored, forward or backward, and two
+    runs are bit-equal (csrc/cliploss.hip).  A non-finite feature gives a NaN loss and NaN gradients, as the ATen composition does: the
+    caller's skip-step logic reads it.  ``offset`` outside 0 <= offset <= m - n raises ValueError before any launch.  No 16-bit operand,
+    and an enclosing autocast changes nothing."""
+    name = "clip_pair_loss"
+    for t, nm in ((a, "a"), (b, "b"), (logit_scale, "logit_scale"), (wr, "wr"), (wc, "wc")):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name}: {nm} must be a GPU tensor (the HIP path has no CPU fallback)")
+    for t, nm in ((a, "a"), (b, "b"), (logit_scale, "logit_scale"), (wr, "wr"), (wc, "wc")):
+        if t is not None and t.dtype != F32:
+            raise TypeError(f"{name}: {nm} must be float32, got {t.dtype}")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.device != b.device:
+        raise ValueError(f"{name}: expected a [n, d] and b [m, d] on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, d = a.shape
+    m = b.shape[0]
+    if n < 1 or m < 1 or d < 1:
+        raise ValueError(f"{name}: empty input {tuple(a.shape)} / {tuple(b.shape)}")
+    if max(n, m) > 2 ** 31 - 1:
+        raise ValueError(f"{name}: {max(n, m)} rows, the kernel indexes tiles with int32")
+    for t, nm, rows in ((a, "a", n), (b, "b", m)):
+        if (d > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < d):
+            raise ValueError(f"{name}: {nm} needs unit column stride and a row stride >= {d}, got strides {tuple(t.stride())}")
+    if logit_scale.numel() != 1 or logit_scale.device != a.device:
+        raise ValueError(f"{name}: logit_scale must be one element on {a.device}, got {tuple(logit_scale.shape)} on {logit_scale.device}")
+    for t, nm in ((wr, "wr"), (wc, "wc")):
+        if t is not None and (tuple(t.shape) != (n,) or t.device != a.device):
+            raise ValueError(f"{name}: {nm} must be [{n}] on {a.device}, got {tuple(t.shape)} on {t.device}")
+    if not isinstance(offset, (int, np.integer)) or isinstance(offset, bool):
+        raise TypeError(f"{name}: offset must be an int, got {type(offset).__name__}")
+    offset = int(offset)
+    if offset < 0 or n + offset > m:
+        raise ValueError(f"{name}: the partner of row i is column i + offset, which needs 0 <= offset <= m - n; got offset={offset}, "
+                         f"n={n}, m={m}")
+    wr = wr.detach().contiguous()
+    wc = None if wc is None else wc.detach().contiguous()
+    return ClipPairLossFn.apply(a, b, logit_scale, wr, wc, offset)
+
+
 def mix_tables(kind, lam, oml, box, Bn: int, H: int, W: int):
     """The host tables of ``mix_batch`` checked and brought to their device types: (kind int32 [B], lam f32 [B], oml f32 [B],
     box int32 [B, 4]).  ValueError for a wrong length, a kind outside {0, 1, 2}, or a cutmix box (yl, yh, xl, xh) that does not
