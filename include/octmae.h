@@ -45,8 +45,10 @@ extern "C" {
  * 23: octmae_patch_scatter, octmae_cam_weights (+ octmae_cam_ws_floats), octmae_cam_tokens, octmae_heatmap (input gradients, Grad-CAM
  *     and heat volumes, csrc/saliency.hip).
  * 24: octmae_clip_loss_fwd, octmae_clip_loss_bwd (+ octmae_clip_loss_ws_floats): the contrastive loss of the COEM training step and its
- *     gradients off f32 MFMA tiles, csrc/cliploss.hip. */
-#define OCTMAE_ABI_VERSION 24
+ *     gradients off f32 MFMA tiles, csrc/cliploss.hip.
+ * 25: octmae_join_fwd, octmae_join_bwd (+ octmae_join_ws_floats): normalise, concatenate and LayerNorm the tower outputs in front of
+ *     the COEM classification head, csrc/join.hip. */
+#define OCTMAE_ABI_VERSION 25
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -529,6 +531,32 @@ int octmae_clip_loss_bwd(const float* a, long long a_stride, const float* b, lon
                          const float* wc, long long offset, const float* lse_row, const float* lse_col, const float* gout, float* da,
                          long long da_stride, float* db, long long db_stride, float* dscale, float* ws, long long ws_floats, long long n,
                          long long m, int d, void* stream);
+
+/* ---- the join in front of the COEM classification head (csrc/join.hip) --------------------------------
+ * retinal-COEM/src/open_clip/model.py:741-809 (CustomTextCLIPClassification / CustomTextCLIP3ModClassification): F.normalize of each
+ * tower output, zeros for an absent modality, cat, ClassificationHead.input_norm = LayerNorm(M * D).  One kernel each way.
+ *   f_k     f32 [B][D], the RAW output of tower k (k < M; f2 = NULL when M == 2; an absent modality's pointer may be NULL)
+ *   present_mask   bit k set: modality k takes part; a clear bit puts zeros into slot k (single_modality)
+ *   n_out   f32 [M][B][D]: n_k = f_k / max(||f_k||_2, 1e-12), zeros in absent slots (the norm is taken of the slice scaled by a power
+ *           of two, so rows of size 1e-20 or 1e18 neither under- nor overflow);  inv_norm f32 [B][M] = 1 / max(||f_k||, 1e-12), 0 if absent
+ *   y_lp    [B][M * D] in the library's 16-bit operand type (octmae_lp_dtype) = LayerNorm(concat_k n_k; gamma, beta, eps), the
+ *           statistics over all M * D columns;  mean / rstd f32 [B]
+ * octmae_join_bwd: dy f32 [B][M * D] (the gradient at y), dn_extra f32 [M][B][D] or NULL (a gradient arriving at n_out from elsewhere;
+ * absent slots are not read), df_out f32 [M][B][D]: the gradient at f_k through LayerNorm and normalisation in one pass -- slices of
+ * absent modalities are NOT written.  A present row whose norm is below 1e-12 gets d / 1e-12 without the projection term (autograd's
+ * result for F.normalize).  dgamma / dbeta f32 [M * D] are ACCUMULATED (+=) when non-NULL, through per-workgroup partials in `ws`
+ * (at least octmae_join_ws_floats(B, D, M) floats; may be NULL when both are) folded in a fixed order: no float atomics, two runs are
+ * bit-equal, and df_out is bit-identical with and without them.
+ * Alignment: rows are moved in 16-byte pieces, so f_k, gamma, beta, n_out, dy, dn_extra, df_out and ws must be 16-byte aligned and
+ * y_lp 8-byte aligned (with D % 4 == 0 every row then is); inv_norm, mean, rstd, dgamma and dbeta are accessed word by word.
+ * -1, before any launch: D % 4 != 0, M not 2 or 3, M * D > 4096, B <= 0, present_mask == 0 or with a bit at or above M, a NULL
+ * pointer where one is needed, a pointer that is not aligned as above (octmae_join_ws_floats returns -1 for such a shape). */
+int octmae_join_ws_floats(int B, int D, int M);
+int octmae_join_fwd(const float* f0, const float* f1, const float* f2, int present_mask, const float* gamma, const float* beta,
+                    float* n_out, float* inv_norm, void* y_lp, float* mean, float* rstd, int B, int D, int M, float eps, void* stream);
+int octmae_join_bwd(const float* dy, const float* dn_extra, const float* f0, const float* f1, const float* f2, const float* inv_norm,
+                    const float* mean, const float* rstd, const float* gamma, int present_mask, float* df_out, float* dgamma,
+                    float* dbeta, float* ws, int B, int D, int M, void* stream);
 
 /* ---- mixup / cutmix of a fine-tune batch (csrc/mixup.hip) ---------------------------------------------
  * timm.data.Mixup's three modes on the device, in place, in one launch; the decisions are the host's (octcubem_amd/mixup.py).

@@ -42,6 +42,9 @@ SIGNATURES = {
     "octmae_clip_loss_ws_floats": [_ll, _ll],
     "octmae_clip_loss_fwd": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],
     "octmae_clip_loss_bwd": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _ll, _ll, _i, _vp],
+    "octmae_join_ws_floats": [_i, _i, _i],
+    "octmae_join_fwd": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "octmae_join_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "octmae_mix_batch": [_vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp],
     "octmae_attn_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "octmae_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],

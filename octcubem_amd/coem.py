@@ -333,6 +333,158 @@ class CustomTextCLIP(nn.Module):
         return self.encode_image(image, normalize=True), self.encode_text(text, normalize=True), self.logit_scale.exp()
 
 
+@autocast_invariant
+class CustomTextCLIP3Mod(CustomTextCLIP):
+    """open_clip/model.py:685-720: one OCT tower, ONE en-face tower with a head per modality (models_vit_2mod: IR = modality 0, FAF =
+    modality 1) and a temperature per pair -- ``logit_scale`` (OCT, IR), ``logit_scale1`` (OCT, FAF), ``logit_scale2`` (IR, FAF).
+    ``forward`` returns the reference's 6-tuple (L2-normalised features, None for a modality ``single_modality`` leaves out, and the
+    three exponentiated temperatures).  With both en-face images present the tower runs them in one trunk pass (``forward_pair``;
+    ``pair=False``: two passes, as the reference).  Deliberate departure: the 'text2' branch returns ``logit_scale2.exp()`` -- the
+    reference returns the unbound method there (model.py:715, a missing call)."""
+
+    def __init__(self, visual: nn.Module, text: nn.Module, pair: bool = True):
+        super().__init__(visual, text)
+        self.logit_scale1 = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
+        self.logit_scale2 = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
+        self.pair = bool(pair)
+
+    def encode_text(self, text, normalize: bool = False, modality=0):
+        features = self.text(text, modality=modality).float()
+        return F.normalize(features, dim=-1) if normalize else features
+
+    def _scales(self):
+        return self.logit_scale.exp(), self.logit_scale1.exp(), self.logit_scale2.exp()
+
+    def _raw_features(self, image, text1, text2, single_modality=None):
+        """the RAW tower outputs (image, text1, text2), None for what ``single_modality`` leaves out"""
+        if single_modality not in ("image", "text1", "text2", None):
+            raise ValueError(f"single_modality should be either 'image', 'text1', 'text2' or None, got {single_modality}")
+        if single_modality == "image":
+            return self.encode_image(image), None, None
+        if single_modality == "text1":
+            return None, self.encode_text(text1, modality=0), None
+        if single_modality == "text2":
+            return None, None, self.encode_text(text2, modality=1)
+        fi = self.encode_image(image)
+        if self.pair and hasattr(self.text, "forward_pair"):
+            f1, f2 = self.text.forward_pair(text1, text2)
+            return fi, f1.float(), f2.float()
+        return fi, self.encode_text(text1, modality=0), self.encode_text(text2, modality=1)
+
+    def forward(self, image, text1, text2, single_modality=None):
+        feats = self._raw_features(image, text1, text2, single_modality)
+        return tuple(None if f is None else F.normalize(f, dim=-1) for f in feats) + self._scales()
+
+
+@autocast_invariant
+class ClassificationHead(nn.Module):
+    """open_clip/model.py:723-739: ``input_norm`` (LayerNorm, eps 1e-5) -> ``fc1`` -> GELU -> ``fc2`` with the reference's keys and
+    initialisation (``fc1.weight`` ~ N(0, 0.02), everything else nn.Linear's / nn.LayerNorm's own).  A module with a parameter arena of
+    its own, as each tower is (``prepare()`` / ``invalidate_lp()``; one FusedAdamW / FlatGradReducer per arena).
+
+    ``forward(x)`` on an already-joined fp32 ``x`` is the plain form: the LayerNorm kernel, then fc1 + GELU -> fc2 on the MLP path
+    (ops.MlpFn).  ``forward_joined(features, present_mask)`` takes the RAW tower outputs and runs ops.JoinFn (csrc/join.hip: normalise,
+    zero-fill, concatenate, LayerNorm in one kernel each way) in front of the same MLP; it returns ``(logits, normalised features)``.
+    ``num_classes % 8 != 0`` (the reference's 2 and 5): fc2 takes the ``torch.nn.functional.linear`` route models_vit takes for odd class
+    counts, behind fc1 as ops.LinearFn and ATen's GELU."""
+
+    def __init__(self, input_dim, hidden_dim, num_classes, initialization=True):
+        super().__init__()
+        self.fc1 = nn.Linear(input_dim, hidden_dim)
+        self.gelu = nn.GELU()
+        self.fc2 = nn.Linear(hidden_dim, num_classes)
+        self.input_norm = nn.LayerNorm(input_dim)
+        if initialization:
+            torch.nn.init.normal_(self.fc1.weight, std=0.02)
+
+    def prepare(self):
+        from .arena import get_arena
+        arena = get_arena(self, full_check=True)
+        if torch.is_grad_enabled():
+            arena.rebind_grads()
+        arena.refresh_lp()
+        return arena
+
+    @property
+    def arena(self):
+        from .arena import get_arena
+        return get_arena(self, full_check=True)
+
+    def invalidate_lp(self):
+        self.arena.invalidate_lp()
+
+    def _mlp(self, arena, y):
+        from . import ops
+        f1, f2 = self.fc1, self.fc2
+        if f2.out_features % 8 == 0:
+            ps = (f1.weight, f1.bias, f2.weight, f2.bias)
+            return ops.MlpFn.apply(y, None, arena.lp_view(f1.weight), arena.f32_view(f1.bias), arena.lp_view(f2.weight),
+                                   arena.f32_view(f2.bias), lambda: tuple(arena.grad_view(p) for p in ps), *ps).float()
+        h = ops.LinearFn.apply(y, arena.lp_view(f1.weight), arena.f32_view(f1.bias), lambda: arena.grad_view(f1.weight),
+                               lambda: arena.grad_view(f1.bias), True, f1.weight, f1.bias)
+        return F.linear(F.gelu(h), f2.weight, f2.bias)
+
+    def forward(self, x):
+        from .video_vit import layer_norm
+        arena = self.prepare()
+        return self._mlp(arena, layer_norm(self.input_norm, x.float().contiguous()))
+
+    def forward_joined(self, features, present_mask):
+        from . import ops
+        arena = self.prepare()
+        feats = tuple(None if f is None else f.float() for f in features)
+        y, *n = ops.JoinFn.apply(self.input_norm.weight, self.input_norm.bias, self.input_norm.eps, int(present_mask), *feats)
+        return self._mlp(arena, y), tuple(n)
+
+
+def _tower_out_dim(tower):
+    d = getattr(tower, "out_dim", None)
+    return int(d) if d else int(tower.head.out_features)
+
+
+@autocast_invariant
+class CustomTextCLIPClassification(CustomTextCLIP):
+    """open_clip/model.py:741-769: the two towers and a ClassificationHead over ``2 * embed_dim``; ``forward`` returns
+    ``(logits, logit_scale.exp())``.  ``single_modality`` ('image' | 'text') puts zeros into the absent slot, as the reference does.
+    The normalisation, the zero-filling, the concatenation and the head's LayerNorm are one kernel (ClassificationHead.forward_joined)."""
+
+    def __init__(self, visual: nn.Module, text: nn.Module, num_classes: int, embed_dim: int = None):
+        super().__init__(visual, text)
+        embed_dim = _tower_out_dim(visual) if embed_dim is None else int(embed_dim)
+        self.classification_head = ClassificationHead(2 * embed_dim, hidden_dim=embed_dim, num_classes=num_classes)
+
+    def forward(self, image, text, single_modality=None):
+        if single_modality not in ("image", "text", None):
+            raise ValueError(f"single_modality should be either 'image' or 'text', got {single_modality}")
+        fi = None if single_modality == "text" else self.encode_image(image)
+        ft = None if single_modality == "image" else self.encode_text(text)
+        mask = (1 if fi is not None else 0) | (2 if ft is not None else 0)
+        logits, _ = self.classification_head.forward_joined((fi, ft), mask)
+        return logits, self.logit_scale.exp()
+
+
+@autocast_invariant
+class CustomTextCLIP3ModClassification(CustomTextCLIP3Mod):
+    """open_clip/model.py:772-809: CustomTextCLIP3Mod and a ClassificationHead over ``3 * embed_dim``; ``forward`` returns ``(logits,
+    logit_scale.exp(), logit_scale1.exp(), logit_scale2.exp())``; ``single_modality`` ('image' | 'text1' | 'text2') puts zeros into
+    the two absent slots."""
+
+    def __init__(self, visual: nn.Module, text: nn.Module, num_classes: int, embed_dim: int = None, pair: bool = True):
+        super().__init__(visual, text, pair=pair)
+        embed_dim = _tower_out_dim(visual) if embed_dim is None else int(embed_dim)
+        self.classification_head = ClassificationHead(3 * embed_dim, hidden_dim=embed_dim, num_classes=num_classes)
+
+    def forward_with_features(self, image, text1, text2, single_modality=None):
+        """-> (logits, (n_image, n_text1, n_text2)): the normalised features the join kernel wrote, zeros in absent slots"""
+        feats = self._raw_features(image, text1, text2, single_modality)
+        mask = sum(1 << k for k, f in enumerate(feats) if f is not None)
+        return self.classification_head.forward_joined(feats, mask)
+
+    def forward(self, image, text1, text2, single_modality=None):
+        logits, _ = self.forward_with_features(image, text1, text2, single_modality)
+        return (logits,) + self._scales()
+
+
 def build_towers_from_config(cfg: dict, flash_semantics: bool = True):
     """Config-driven construction of the two towers, for the model configs the reference ships for this path
     (retinal-COEM/src/open_clip/model_configs/vit_large_patch16_retFound-vit_large_patch16_OCTCube.json through
@@ -341,6 +493,8 @@ def build_towers_from_config(cfg: dict, flash_semantics: bool = True):
       vision_cfg.model_name  "ViT_ST" | "ViT_ST_nodrop"   -> the 3-D spatio-temporal ViT (models_vit_st), ``out_dim = embed_dim`` head,
                              sep_pos_embed / cls_embed on, dropout before the head only for "ViT_ST"
       text_cfg.vit_model_name "ViT_flash_attn"             -> the 2-D ViT (models_vit) on the en-face image
+                              "ViT_flash_attn_2mod"        -> the two-modality en-face tower (models_vit_2mod: one trunk, a head per
+                                                              modality), ``flash_compat`` from its own ``use_flash_attn`` and ``flash_semantics``
 
     ``use_flash_attn: true`` in the config selects, in the reference, flash-attn blocks whose final residual is dropped
     (SURVEY section 0 fact 3); ``flash_semantics`` reproduces that through ``flash_compat`` (native key layout).  The rest of
@@ -365,13 +519,22 @@ def build_towers_from_config(cfg: dict, flash_semantics: bool = True):
         global_pool=bool(v.get("global_pool", True)) if name == "ViT_ST_nodrop" else True,
         flash_compat=bool(v.get("use_flash_attn", False)) and flash_semantics)
     tname = t.get("vit_model_name") or ""
-    if "ViT_flash_attn" not in tname or "mod" in tname:
-        raise NotImplementedError(f"en-face tower {tname!r}: only ViT_flash_attn is built")
-    text = models_vit.VisionTransformer(
-        img_size=int(t["image_size"]), patch_size=int(t["patch_size"]), in_chans=int(t.get("in_chans", 3)), num_classes=embed_dim,
-        embed_dim=int(t["width"]), depth=int(t["layers"]), num_heads=int(t["num_heads"]), mlp_ratio=float(t.get("mlp_ratio", 4)),
-        qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=float(t.get("norm_layer_eps", 1e-6))),
-        drop_path_rate=float(t.get("drop_path_rate", 0.0)), global_pool=bool(t.get("global_pool", True)))
+    if "ViT_flash_attn_2mod" in tname:          # open_clip/model.py:510-534: one trunk, a head per en-face modality
+        from . import models_vit_2mod
+        text = models_vit_2mod.VisionTransformer(
+            image_size=int(t["image_size"]), out_dim=embed_dim, embed_dim=int(t["width"]), depth=int(t["layers"]),
+            patch_size=int(t["patch_size"]), in_chans=int(t.get("in_chans", 3)), global_pool=bool(t.get("global_pool", True)),
+            num_heads=int(t["num_heads"]), mlp_ratio=float(t.get("mlp_ratio", 4)), drop_path_rate=float(t.get("drop_path_rate", 0.0)),
+            norm_layer=partial(nn.LayerNorm, eps=float(t.get("norm_layer_eps", 1e-6))), dropout=float(t.get("dropout", 0.5)),
+            cls_embed=True, num_mod_head=2, flash_compat=bool(t.get("use_flash_attn", False)) and flash_semantics)
+    elif "ViT_flash_attn" not in tname or "mod" in tname:
+        raise NotImplementedError(f"en-face tower {tname!r}: only ViT_flash_attn and ViT_flash_attn_2mod are built")
+    else:
+        text = models_vit.VisionTransformer(
+            img_size=int(t["image_size"]), patch_size=int(t["patch_size"]), in_chans=int(t.get("in_chans", 3)), num_classes=embed_dim,
+            embed_dim=int(t["width"]), depth=int(t["layers"]), num_heads=int(t["num_heads"]), mlp_ratio=float(t.get("mlp_ratio", 4)),
+            qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=float(t.get("norm_layer_eps", 1e-6))),
+            drop_path_rate=float(t.get("drop_path_rate", 0.0)), global_pool=bool(t.get("global_pool", True)))
     for tower, c in ((visual, v), (text, t)):
         path = c.get("model_ckpt")
         if path and os.path.exists(path):
@@ -382,17 +545,27 @@ def build_towers_from_config(cfg: dict, flash_semantics: bool = True):
     return visual, text
 
 
-def create_model_from_config(cfg: dict, **kw) -> "CustomTextCLIP":
-    """CustomTextCLIP(embed_dim, vision_cfg, text_cfg) of open_clip/model.py:635-646 for the configs above."""
+def create_model_from_config(cfg: dict, three: bool = False, num_classes: int = None, **kw) -> "CustomTextCLIP":
+    """The model open_clip/factory.py:299-309 picks for the configs above: ``three`` is its ``args.enable_3mod_training``, a
+    ``num_classes`` its ``args.cls_dataset`` (with ``args.num_classes``) --
+        neither: CustomTextCLIP          three: CustomTextCLIP3Mod
+        num_classes: CustomTextCLIPClassification          both: CustomTextCLIP3ModClassification"""
     visual, text = build_towers_from_config(cfg, **kw)
-    return CustomTextCLIP(visual, text)
+    if num_classes is not None:
+        cls = CustomTextCLIP3ModClassification if three else CustomTextCLIPClassification
+        return cls(visual, text, int(num_classes), embed_dim=int(cfg["embed_dim"]))
+    return CustomTextCLIP3Mod(visual, text) if three else CustomTextCLIP(visual, text)
 
 
 def make_reducers(model, comm=None, **kw):
-    """One FlatGradReducer per tower (each tower is a model with its own flat gradient arena)."""
+    """One FlatGradReducer per tower (each tower is a model with its own flat gradient arena), and one for the classification head of a
+    model that has one."""
     from .parallel import FlatGradReducer
     m = getattr(model, "module", model)
-    return [FlatGradReducer(m.visual, comm=comm, **kw), FlatGradReducer(m.text, comm=comm, **kw)]
+    reds = [FlatGradReducer(m.visual, comm=comm, **kw), FlatGradReducer(m.text, comm=comm, **kw)]
+    if getattr(m, "classification_head", None) is not None:
+        reds.append(FlatGradReducer(m.classification_head, comm=comm, **kw))
+    return reds
 
 
 def clamp_logit_scale(model):

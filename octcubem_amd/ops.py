@@ -506,6 +506,88 @@ def slice_pool_bwd(dout, pooled, mean, rstd, gamma, T: int, S: int, cls: bool, d
     return dx, dxb
 
 
+def _join_check(name, feats, present_mask):
+    """The refusals of csrc/join.hip restated on the host, so that a bad call raises ValueError before any tensor is made or launched."""
+    M = len(feats)
+    if M not in (2, 3):
+        raise ValueError(f"{name}: {M} modalities, the kernel is built for 2 or 3")
+    if isinstance(present_mask, bool) or not isinstance(present_mask, (int, np.integer)) or not 0 < int(present_mask) < (1 << M):
+        raise ValueError(f"{name}: present_mask must have at least one of its low {M} bits set and none above them, got {present_mask!r}")
+    present_mask = int(present_mask)
+    ref = None
+    for k, f in enumerate(feats):
+        if not (present_mask >> k) & 1:
+            continue
+        if f is None:
+            raise ValueError(f"{name}: modality {k} is marked present and has no features")
+        _chk(f, F32, f"{name}: features of modality {k}")
+        if f.data_ptr() % 16:
+            raise ValueError(f"{name}: features of modality {k} start at an address that is not 16-byte aligned (a view at an odd "
+                             "storage offset): the kernel moves rows in 16-byte pieces -- pass a copy (.clone())")
+        if f.dim() != 2 or (ref is not None and (f.shape != ref.shape or f.device != ref.device)):
+            raise ValueError(f"{name}: expected [B, D] features of one shape on one device, got {tuple(f.shape)}")
+        ref = f
+    B, D = ref.shape
+    if B < 1 or D % 4 != 0 or M * D > 4096:
+        raise ValueError(f"{name}: B = {B}, D = {D}, M = {M}: the kernel needs B >= 1, D % 4 == 0 and M * D <= 4096")
+    return M, B, D, present_mask, ref.device
+
+
+def _join_aligned(name, **tensors):
+    for nm, t in tensors.items():
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"{name}: {nm} starts at an address that is not 16-byte aligned: the kernel moves rows in 16-byte pieces")
+
+
+def join_fwd(feats, present_mask: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float):
+    """feats: M = 2 or 3 raw tower outputs f32 [B, D] (None where absent) -> y (16-bit operand type) [B, M * D] = LayerNorm(concat of
+    the L2-normalised features, zeros in absent slots), n_out f32 [M, B, D] (the normalised features), inv_norm f32 [B, M], mean, rstd [B]
+    (csrc/join.hip)."""
+    M, B, D, present_mask, dev = _join_check("join_fwd", feats, present_mask)
+    if gamma.numel() != M * D or beta.numel() != M * D:
+        raise ValueError(f"join_fwd: gamma / beta need {M * D} elements, got {gamma.numel()} and {beta.numel()}")
+    _chk(gamma, F32, "join_fwd: gamma"); _chk(beta, F32, "join_fwd: beta")
+    _join_aligned("join_fwd", gamma=gamma, beta=beta)
+    y = torch.empty((B, M * D), dtype=BF16, device=dev)
+    n_out = torch.empty((M, B, D), dtype=F32, device=dev)
+    inv_norm = torch.empty((B, M), dtype=F32, device=dev)
+    mean = torch.empty((B,), dtype=F32, device=dev)
+    rstd = torch.empty((B,), dtype=F32, device=dev)
+    f = [(_p(x) if (present_mask >> k) & 1 else None) for k, x in enumerate(feats)] + [None] * (3 - M)
+    P = bin(present_mask).count("1")
+    # algorithmic HBM bytes: the present features read, the normalised features (fp32) and the 16-bit row written
+    _launch(f"join_fwd_d{M * D}", 0.0, (4.0 * P + 6.0 * M) * B * D + (8.0 + 4.0 * M) * B,
+            lambda: call("octmae_join_fwd", f[0], f[1], f[2], present_mask, gamma.data_ptr(), beta.data_ptr(), n_out.data_ptr(),
+                         inv_norm.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), B, D, M, float(eps), _stream()))
+    return y, n_out, inv_norm, mean, rstd
+
+
+def join_bwd(dy: torch.Tensor, dn_extra: Optional[torch.Tensor], feats, inv_norm, mean, rstd, gamma, present_mask: int,
+             dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> df f32 [M, B, D]: the gradient at the raw tower outputs (slices of absent modalities are NOT written); ``dy`` f32 [B, M * D],
+    ``dn_extra`` f32 [M, B, D] or None; ``dgamma`` / ``dbeta`` (f32 [M * D]) are accumulated into when given, deterministically."""
+    M, B, D, present_mask, dev = _join_check("join_bwd", feats, present_mask)
+    _chk(dy, F32, "join_bwd: dy")
+    if tuple(dy.shape) != (B, M * D) or (dn_extra is not None and tuple(dn_extra.shape) != (M, B, D)):
+        raise ValueError(f"join_bwd: dy must be [{B}, {M * D}] and dn_extra [{M}, {B}, {D}]")
+    if dn_extra is not None:
+        _chk(dn_extra, F32, "join_bwd: dn_extra")
+    for t, nm in ((dgamma, "dgamma"), (dbeta, "dbeta")):
+        if t is not None and (_chk(t, F32, f"join_bwd: {nm}").numel() != M * D):
+            raise ValueError(f"join_bwd: {nm} needs {M * D} elements")
+    _join_aligned("join_bwd", dy=dy, dn_extra=dn_extra, gamma=gamma)
+    df = torch.empty((M, B, D), dtype=F32, device=dev)
+    ws = None
+    if dgamma is not None or dbeta is not None:
+        ws = torch.empty((load().octmae_join_ws_floats(B, D, M),), dtype=F32, device=dev)
+    f = [(_p(x) if (present_mask >> k) & 1 else None) for k, x in enumerate(feats)] + [None] * (3 - M)
+    P = bin(present_mask).count("1")
+    _launch(f"join_bwd_d{M * D}", 0.0, (4.0 * M + (8.0 + (4.0 if dn_extra is not None else 0.0)) * P) * B * D + (8.0 + 4.0 * M) * B,
+            lambda: call("octmae_join_bwd", dy.data_ptr(), _p(dn_extra), f[0], f[1], f[2], inv_norm.data_ptr(), mean.data_ptr(),
+                         rstd.data_ptr(), gamma.data_ptr(), present_mask, df.data_ptr(), _p(dgamma), _p(dbeta), _p(ws), B, D, M, _stream()))
+    return df
+
+
 _VOL_DTYPES = {torch.uint8: 0, torch.float32: 1}
 
 
@@ -1290,6 +1372,49 @@ class SlicePoolFn(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
+class JoinFn(torch.autograd.Function):
+    """(y, n_0, ..., n_{M-1}) = join of M raw tower outputs in front of the COEM classification head (csrc/join.hip): n_k the L2-normalised
+    features (zeros where ``present_mask`` has bit k clear; pass None for that input), y = LayerNorm(concat n_k) in the 16-bit operand
+    type, ready to be fc1's operand.  The backward routes the gradients arriving at the n_k (a model that also returns them) into the
+    same kernel as ``dn_extra``; gamma / beta gradients are accumulated into their buffers as LayerNormFn does."""
+
+    @staticmethod
+    def forward(ctx, gamma, beta, eps, present_mask, *feats):
+        feats = tuple(None if f is None else (f if f.is_contiguous() else f.contiguous()) for f in feats)
+        y, n_out, inv_norm, mean, rstd = join_fwd(feats, present_mask, gamma, beta, eps)
+        ctx.save_for_backward(gamma, beta, inv_norm, mean, rstd, *[f for f in feats if f is not None])
+        ctx.slots = [f is not None for f in feats]
+        ctx.mask = int(present_mask)
+        ctx.set_materialize_grads(False)
+        return (y,) + n_out.unbind(0)
+
+    @staticmethod
+    def backward(ctx, dy, *dn):
+        gamma, beta, inv_norm, mean, rstd, *given = ctx.saved_tensors
+        it = iter(given)
+        feats = tuple(next(it) if s else None for s in ctx.slots)
+        M = len(feats)
+        ref = given[0]
+        B, D = ref.shape
+        dy = torch.zeros((B, M * D), dtype=F32, device=ref.device) if dy is None else dy.reshape(B, M * D).to(F32).contiguous()
+        extra = None
+        if any(d is not None for d in dn):
+            zero = None
+            parts = []
+            for d in dn:
+                if d is None:
+                    zero = torch.zeros((B, D), dtype=F32, device=ref.device) if zero is None else zero
+                    d = zero
+                parts.append(d.to(F32))
+            extra = torch.stack(parts).contiguous()
+        wg = _weight_grads
+        df = join_bwd(dy, extra, feats, inv_norm, mean, rstd, gamma, ctx.mask,
+                      grad_buf(gamma) if wg and ctx.needs_input_grad[0] else None, grad_buf(beta) if wg and ctx.needs_input_grad[1] else None)
+        if wg:
+            notify_grad_ready((gamma, beta))
+        return (None, None, None, None) + tuple(df[k] if (ctx.mask >> k) & 1 and ctx.needs_input_grad[4 + k] else None for k in range(M))
+
+
 class LinearFn(torch.autograd.Function):
     """y = x W^T + b on bf16 operands.  ``w_lp`` / ``b32`` are the (possibly fused q|k|v) bf16 weight and fp32 bias
     views; ``params`` = (weight params..., bias params...) whose .grad buffers are adjacent views of the arena."""
@@ -1411,15 +1536,14 @@ class MlpFn(torch.autograd.Function):
             out = linear_fwd(act, w2_lp, b2_32, "bf16")
         ctx.save_for_backward(y2, pre, act, w1_lp, w2_lp)
         ctx.grads, ctx.params, ctx.shp, ctx.has_res = grads, params, shp, res is not None
-        return out.view(shp)
+        return out.view(*shp[:-1], w2_lp.shape[0])      # a head whose fc2 is not as wide as its input (models_vit_2mod); a Block's is
 
     @staticmethod
     def backward(ctx, dout):
         y2, pre, act, w1_lp, w2_lp = ctx.saved_tensors
-        Cc = ctx.shp[-1]
         wg = _weight_grads
         gw1, gb1, gw2, gb2 = ctx.grads() if wg else (None,) * 4
-        d2 = dout.reshape(-1, Cc)
+        d2 = dout.reshape(-1, w2_lp.shape[0])
         if not d2.is_contiguous():
             d2 = d2.contiguous()
         dob = cast_bf16(d2)
@@ -1433,6 +1557,54 @@ class MlpFn(torch.autograd.Function):
             notify_grad_ready(ctx.params)
         dy = linear_dgrad(dpre, w1_lp).view(ctx.shp)
         return (dy, dout if ctx.has_res else None, None, None, None, None, None) + (None,) * len(ctx.params)
+
+
+class MlpPairFn(torch.autograd.Function):
+    """fc1 -> exact GELU ONCE over 2 B rows, then one fc2 per half: rows [0, B) through (w2a, b2a), rows [B, 2 B) through (w2b, b2b) --
+    the two modality heads of models_vit_2mod behind one shared trunk pass.  The same launches as MlpFn without a residual, the fc2
+    side once per half; the fc1 bias gradient is accumulated by both halves' dgrad epilogues."""
+
+    @staticmethod
+    def forward(ctx, y, w1_lp, b1_32, w2a_lp, b2a_32, w2b_lp, b2b_32, grads, *params):
+        y2 = cast_bf16(y.reshape(-1, y.shape[-1]))
+        if y2.shape[0] % 2:
+            raise ValueError(f"MlpPairFn: {y2.shape[0]} rows are not two halves")
+        B = y2.shape[0] // 2
+        ctx.pre_is_dgelu = GELU_PRIME_FWD
+        pre, act = linear_fwd(y2, w1_lp, b1_32, "gelu", store_dgelu=ctx.pre_is_dgelu)
+        out_a = linear_fwd(act[:B], w2a_lp, b2a_32, "bf16")
+        out_b = linear_fwd(act[B:], w2b_lp, b2b_32, "bf16")
+        ctx.save_for_backward(y2, pre, act, w1_lp, w2a_lp, w2b_lp)
+        ctx.grads, ctx.params, ctx.shp = grads, params, y.shape
+        ctx.set_materialize_grads(False)
+        return out_a, out_b
+
+    @staticmethod
+    def backward(ctx, da, db):
+        y2, pre, act, w1_lp, w2a_lp, w2b_lp = ctx.saved_tensors
+        B = y2.shape[0] // 2
+        wg = _weight_grads
+        gw1, gb1, gw2a, gb2a, gw2b, gb2b = ctx.grads() if wg else (None,) * 6
+        halves = []
+        for d, w2, gw2, gb2, rows in ((da, w2a_lp, gw2a, gb2a, slice(0, B)), (db, w2b_lp, gw2b, gb2b, slice(B, 2 * B))):
+            if d is None:      # this head's output took no part in the loss
+                halves.append(torch.zeros((B, w1_lp.shape[0]), dtype=BF16, device=y2.device))
+                continue
+            d2 = d.reshape(B, w2.shape[0])
+            if not d2.is_contiguous():
+                d2 = d2.contiguous()
+            dob = cast_bf16(d2)
+            if gb2 is not None:
+                colsum_accum(d2, gb2)
+            if wg:
+                linear_wgrad_accum(dob, act[rows], gw2)
+            halves.append(linear_dgrad(dob, w2, pre=pre[rows], colsum=gb1, pre_is_dgelu=ctx.pre_is_dgelu, fold_entry=not wg))
+        dpre = torch.cat(halves)
+        if wg:
+            linear_wgrad_accum(dpre, y2, gw1)
+            notify_grad_ready(ctx.params)
+        dy = linear_dgrad(dpre, w1_lp).view(ctx.shp)
+        return (dy,) + (None,) * 7 + (None,) * len(ctx.params)
 
 
 # Gradients handed from one fused op to the one upstream of it, keyed by the fp32 gradient tensor they describe:
