@@ -47,8 +47,11 @@ extern "C" {
  * 24: octmae_clip_loss_fwd, octmae_clip_loss_bwd (+ octmae_clip_loss_ws_floats): the contrastive loss of the COEM training step and its
  *     gradients off f32 MFMA tiles, csrc/cliploss.hip.
  * 25: octmae_join_fwd, octmae_join_bwd (+ octmae_join_ws_floats): normalise, concatenate and LayerNorm the tower outputs in front of
- *     the COEM classification head, csrc/join.hip. */
-#define OCTMAE_ABI_VERSION 25
+ *     the COEM classification head, csrc/join.hip.
+ * 26: octmae_ln_apply (csrc/layernorm.hip), octmae_gelu_apply (csrc/recompute.hip): the LayerNorm and GELU outputs rebuilt in the
+ *     backward of a Block that did not keep them (activation recomputation, ops.BlockFn); octmae_colsum_accum_ws (+ octmae_colsum_ws_rows):
+ *     the bias-gradient column sums with a fixed order of additions. */
+#define OCTMAE_ABI_VERSION 26
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -205,6 +208,10 @@ int octmae_linear_resid_rowscale(const void* W, const void* X, float* out, const
  *      caller-provided workspace partial_ws).  D % 4 == 0, D <= 2048. */
 int octmae_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y_bf16, float* mean, float* rstd,
                          int M, int D, float eps, void* stream);
+/* y bf16 = fmaf((x - mean[r]) * rstd[r], gamma, beta) from SAVED statistics: bit-equal to the y octmae_layernorm_fwd wrote for the same
+ * x, gamma, beta when mean / rstd are the ones it saved.  Same domain (D % 4 == 0, D <= 2048), -1 otherwise. */
+int octmae_ln_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y_bf16,
+                    int M, int D, void* stream);
 int octmae_layernorm_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma,
                          const float* dres, float* dx, void* dx_bf16, float* dgamma, float* dbeta, float* dxsum,
                          float* partial_ws, int M, int D, void* stream);
@@ -355,6 +362,11 @@ int octmae_attn_bwd_fused_delta(const void* qkv, const void* dout, const float* 
 int octmae_random_masking_ids(const float* noise, long long* ids_restore, long long* ids_keep, long long* ids_shuffle,
                               float* mask, int B, int L, int len_keep, void* stream);
 
+/* ---- activation recomputation --------------------------------------------------------------------
+ * act[i] = lp(gelu(float(pre[i]))) over n 16-bit values: bit-equal to the second output of the GELU epilogue (octmae_gemm_bf16
+ * epilogue 2) whose first output is `pre`.  n % 8 == 0, 16-byte aligned pointers; -1 otherwise. */
+int octmae_gelu_apply(const void* pre_bf16, void* act_bf16, long long n, void* stream);
+
 /* ---- token plumbing ------------------------------------------------------------------------------ */
 int octmae_cast_f32_bf16(const float* src, void* dst_bf16, long long n, void* stream);
 /* dst bf16 [R][D] = rowscale[r / rows_per_scale] * src f32 [R][D]: the gradient entering a stochastic-depth branch */
@@ -362,6 +374,13 @@ int octmae_cast_rowscale_f32_bf16(const float* src, const float* rowscale, void*
                                   int rows_per_scale, void* stream);
 /* out[c] += sum_r in[r][c]  (nn.Linear bias gradient) */
 int octmae_colsum_accum(const void* in, int in_is_bf16, float* out, int M, int N, int ld, void* stream);
+/* Both forms add in a fixed order (until ABI 26 the row splits of more than 256 rows added to `out` atomically, in the order they
+ * finished: an ACCUMULATED gradient depended on that order in its last bit).  Without a workspace one workgroup owns 8 columns and all
+ * the rows; with one the rows are split over workgroups, every split leaves one row of `ws` (fp32 [octmae_colsum_ws_rows(M)][N],
+ * caller-owned, need not be initialised; 0 rows: ws may be NULL) and a second launch adds the rows to `out` in their order: the
+ * form for many rows. */
+int octmae_colsum_ws_rows(int M);
+int octmae_colsum_accum_ws(const void* in, int in_is_bf16, float* out, float* ws, int M, int N, int ld, void* stream);
 /* im2col of the kept tokens for PatchEmbed's Conv3d(k = s = (tp,p,p)), video_vit.py:70-83 + the gather at
  * models_mae_joint_res_flash_attn.py:363: out bf16 [B*nkeep][C*tp*p*p] in conv-weight order (c,u,py,px).
  * ids: [B][nkeep] int64 (ids_is_i64=1) or int32, NULL = tokens 0..nkeep-1. */

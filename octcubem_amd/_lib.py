@@ -27,6 +27,8 @@ SIGNATURES = {
     "octmae_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "octmae_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "octmae_layernorm_bwd_ws_floats": [_i, _i],
+    "octmae_ln_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "octmae_gelu_apply": [_vp, _vp, _ll, _vp],
     "octmae_slice_pool_ws_floats": [_i, _i, _i],
     "octmae_slice_pool_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "octmae_slice_pool_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -60,6 +62,8 @@ SIGNATURES = {
     "octmae_cast_rowscale_f32_bf16": [_vp, _vp, _vp, _ll, _i, _i, _vp],
     "octmae_linear_resid_rowscale": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp],
     "octmae_colsum_accum": [_vp, _i, _vp, _i, _i, _i, _vp],
+    "octmae_colsum_ws_rows": [_i],
+    "octmae_colsum_accum_ws": [_vp, _i, _vp, _vp, _i, _i, _i, _vp],
     "octmae_dgelu_colsum_ws_rows": [_i],
     "octmae_linear_dgrad_dgelu": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp],
     "octmae_linear_dgrad_delta": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp],

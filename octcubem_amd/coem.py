@@ -316,6 +316,21 @@ class CustomTextCLIP(nn.Module):
         self.text = text
         self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
 
+    def lock_image_tower(self, unlocked_groups=0, freeze_bn_stats=False):
+        """model.py:649-651 (``--lock-image --lock-image-unlocked-groups N``): lock the OCT tower as per LiT."""
+        self.visual.lock(unlocked_groups=unlocked_groups, freeze_bn_stats=freeze_bn_stats)
+
+    def lock_text_tower(self, unlocked_layers: int = 0, freeze_layer_norm: bool = True):
+        """model.py:653-654: the en-face tower's ``lock``, the two arguments passed by position as the reference passes them (a ViT
+        tower reads them as ``unlocked_groups, freeze_bn_stats``)."""
+        self.text.lock(unlocked_layers, freeze_layer_norm)
+
+    @torch.jit.ignore
+    def set_grad_checkpointing(self, enable=True, mode="full"):
+        """model.py:656-659 (``--grad-checkpointing``) on both towers; ``mode`` as in video_vit.set_recompute."""
+        self.visual.set_grad_checkpointing(enable, mode)
+        self.text.set_grad_checkpointing(enable, mode)
+
     def encode_image(self, image, normalize: bool = False):
         features = self.visual(image).float()
         return F.normalize(features, dim=-1) if normalize else features

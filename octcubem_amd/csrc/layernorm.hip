@@ -99,6 +99,60 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   }
 }
 
+// y = the LayerNorm output rebuilt from the SAVED row statistics (activation recomputation: ops.BlockFn at level "light" drops y1 / y2
+// and calls this in its backward).  The expression and the packing are ln_fwd_kernel's, so the result is that kernel's y bit for bit;
+// without the two reductions a row costs one pass: 4 (x) read + 2 (y) write bytes per element, the row pipelined the same way.
+template <int NC>
+__global__ __launch_bounds__(256) void ln_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                       const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, bf16_t* __restrict__ y, int M, int D) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * 4;
+  const int nchunk = D >> 2;
+  f32x4 g[NC], b[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int ci = lane + 64 * c;
+    if (ci < nchunk) {
+      g[c] = *reinterpret_cast<const f32x4*>(gamma + 4 * ci);
+      b[c] = *reinterpret_cast<const f32x4*>(beta + 4 * ci);
+    }
+  }
+  f32x4 vn[NC];
+  float mu_n = 0.f, rs_n = 0.f;
+  auto issue = [&](int row) {
+    mu_n = mean[row];
+    rs_n = rstd[row];
+    const float* xr = x + (size_t)row * D;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int ci = lane + 64 * c;
+      if (ci < nchunk) vn[c] = LN_LD(f32x4, xr + 4 * ci);
+    }
+  };
+  if (wave < M) issue(wave);
+  for (int row = wave; row < M; row += nwaves) {
+    const float mu = mu_n, rs = rs_n;
+    f32x4 v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = vn[c];
+    if (row + nwaves < M) issue(row + nwaves);
+    bf16_t* yr = y + (size_t)row * D;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int ci = lane + 64 * c;
+      if (ci < nchunk) {
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = fmaf((v[c][e] - mu) * rs, g[c][e], b[c][e]);
+        u32x2 w = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
+        __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(yr + 4 * ci));
+      }
+    }
+  }
+}
+
 // dx = [dres +] rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy * gamma
 template <int NC>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x,
@@ -281,6 +335,24 @@ extern "C" int octmae_layernorm_fwd(const float* x, const float* gamma, const fl
     case 2: hipLaunchKernelGGL(ln_fwd_kernel<2>, grid, blk, 0, st, x, gamma, beta, y, mean, rstd, M, D, eps); break;
     case 3: case 4: hipLaunchKernelGGL(ln_fwd_kernel<4>, grid, blk, 0, st, x, gamma, beta, y, mean, rstd, M, D, eps); break;
     default: hipLaunchKernelGGL(ln_fwd_kernel<8>, grid, blk, 0, st, x, gamma, beta, y, mean, rstd, M, D, eps); break;
+  }
+  OCTMAE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int octmae_ln_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                               void* y_bf16, int M, int D, void* stream) {
+  OCTMAE_CHECK_ARG(x && mean && rstd && gamma && beta && y_bf16);
+  OCTMAE_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 256 * LN_MAXC);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int nc = (D / 4 + 63) / 64;
+  bf16_t* y = reinterpret_cast<bf16_t*>(y_bf16);
+  dim3 grid(ln_grid(M)), blk(256);
+  switch (nc) {
+    case 1: hipLaunchKernelGGL(ln_apply_kernel<1>, grid, blk, 0, st, x, mean, rstd, gamma, beta, y, M, D); break;
+    case 2: hipLaunchKernelGGL(ln_apply_kernel<2>, grid, blk, 0, st, x, mean, rstd, gamma, beta, y, M, D); break;
+    case 3: case 4: hipLaunchKernelGGL(ln_apply_kernel<4>, grid, blk, 0, st, x, mean, rstd, gamma, beta, y, M, D); break;
+    default: hipLaunchKernelGGL(ln_apply_kernel<8>, grid, blk, 0, st, x, mean, rstd, gamma, beta, y, M, D); break;
   }
   OCTMAE_LAUNCH_CHECK();
   return 0;

@@ -55,9 +55,11 @@ __global__ __launch_bounds__(256) void cast_rowscale_kernel(const float* __restr
 
 // ---------------------------------------------------------------------------------------------
 // out[c] += sum_rows in[r][c]   (bias gradients).  Block = 32 row-lanes x 8 column-lanes of 8 columns.
+// ws == nullptr (one row split only: colsum_launch): the split adds its sums to out atomically.  ws (fp32 [gridDim.y][N]): every row split leaves its sums as one row
+// of ws with plain stores and colsum_fold_kernel adds the rows in their order -- the same bits whatever the order the splits finish in.
 template <bool IN_BF16>
-__global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ in, float* __restrict__ out, int M, int N,
-                                                     int ld, int rows_per_block) {
+__global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ in, float* __restrict__ out, float* __restrict__ ws, int M,
+                                                     int N, int ld, int rows_per_block) {
   __shared__ float red[32][65];
   const int cl = threadIdx.x & 7, rl = threadIdx.x >> 3;
   const int c0 = blockIdx.x * 64 + cl * 8;
@@ -90,7 +92,62 @@ __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ in
 #pragma unroll 8
     for (int r = 0; r < 32; ++r) s += red[r][threadIdx.x];
     const int c = blockIdx.x * 64 + threadIdx.x;
-    if (c < N) unsafeAtomicAdd(out + c, s);
+    if (c < N) {
+      if (ws != nullptr) ws[(size_t)blockIdx.y * N + c] = s;
+      else unsafeAtomicAdd(out + c, s);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void colsum_fold_kernel(const float* __restrict__ ws, float* __restrict__ out, int rows, int N) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= N) return;
+  float t = 0.f;
+  for (int r = 0; r < rows; ++r) t += ws[(size_t)r * N + c];
+  out[c] += t;
+}
+
+// The same sums WITHOUT a workspace and without atomics, for more than 256 rows: one workgroup owns 8 columns (one 16-byte chunk of a
+// 16-bit row) and all the rows -- thread t takes rows t, t + 256, ... -- and folds its 256 partial sums through LDS in a fixed order.
+// N / 8 workgroups; rows are read in 16- or 32-byte pieces, neighbouring workgroups share the cache lines.  What the library's own
+// callers (the bias gradients beside a weight-gradient GEMM, the fold of the GELU' column sums) take, so that a gradient accumulated
+// over several backwards does not depend on which workgroup finished first.
+template <bool IN_BF16>
+__global__ __launch_bounds__(256) void colsum_cols_kernel(const void* __restrict__ in, float* __restrict__ out, int M, int N, int ld) {
+  __shared__ float red[256][9];
+  __shared__ float red2[8][8];
+  const int c0 = blockIdx.x * 8;      // N % 8 == 0 and gridDim.x == N / 8: always a whole chunk inside the row
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+  for (int r = threadIdx.x; r < M; r += 256) {
+    if (IN_BF16) {
+      const u32x4 w = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(in) + (size_t)r * ld + c0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { acc[2 * e] += bflo(w[e]); acc[2 * e + 1] += bfhi(w[e]); }
+    } else {
+      const float* p = reinterpret_cast<const float*>(in) + (size_t)r * ld + c0;
+      const f32x4 a = *reinterpret_cast<const f32x4*>(p);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { acc[e] += a[e]; acc[4 + e] += b[e]; }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = acc[e];
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int e = threadIdx.x & 7, grp = threadIdx.x >> 3;
+    float s = 0.f;
+    for (int r = 0; r < 32; ++r) s += red[grp * 32 + r][e];
+    red2[grp][e] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 8) {
+    float s = 0.f;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) s += red2[g][threadIdx.x];
+    out[c0 + threadIdx.x] += s;
   }
 }
 
@@ -445,19 +502,53 @@ extern "C" int octmae_cast_rowscale_f32_bf16(const float* src, const float* rows
   return 0;
 }
 
+// the row splits of a column sum over M rows: (splits, rows per split); one split up to 256 rows, 128 at the most
+static inline void colsum_splits(int M, int* splits, int* rpb) {
+  int s = (M + 255) / 256;
+  if (s > 128) s = 128;
+  int r = (M + s - 1) / s;
+  r = (r + 31) / 32 * 32;
+  *splits = (M + r - 1) / r;
+  *rpb = r;
+}
+
+static int colsum_launch(const void* in, int in_is_bf16, float* out, float* ws, int M, int N, int ld, hipStream_t st) {
+  int splits, rpb;
+  colsum_splits(M, &splits, &rpb);
+  if (splits == 1) ws = nullptr;      // one addend per column: nothing to order
+  if (splits > 1 && ws == nullptr) {  // no workspace to order the row splits in: the column-owning form
+    if (in_is_bf16) hipLaunchKernelGGL(colsum_cols_kernel<true>, dim3(N / 8), dim3(256), 0, st, in, out, M, N, ld);
+    else hipLaunchKernelGGL(colsum_cols_kernel<false>, dim3(N / 8), dim3(256), 0, st, in, out, M, N, ld);
+    OCTMAE_LAUNCH_CHECK();
+    return 0;
+  }
+  dim3 grid((N + 63) / 64, splits);
+  if (in_is_bf16) hipLaunchKernelGGL(colsum_kernel<true>, grid, dim3(256), 0, st, in, out, ws, M, N, ld, rpb);
+  else hipLaunchKernelGGL(colsum_kernel<false>, grid, dim3(256), 0, st, in, out, ws, M, N, ld, rpb);
+  OCTMAE_LAUNCH_CHECK();
+  if (ws != nullptr) {
+    hipLaunchKernelGGL(colsum_fold_kernel, dim3((N + 255) / 256), dim3(256), 0, st, ws, out, splits, N);
+    OCTMAE_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 extern "C" int octmae_colsum_accum(const void* in, int in_is_bf16, float* out, int M, int N, int ld, void* stream) {
   OCTMAE_CHECK_ARG(in && out && M > 0 && N > 0 && N % 8 == 0 && ld % 8 == 0);
-  int splits = (M + 255) / 256;
-  if (splits > 128) splits = 128;
-  int rpb = (M + splits - 1) / splits;
-  rpb = (rpb + 31) / 32 * 32;
-  splits = (M + rpb - 1) / rpb;
-  dim3 grid((N + 63) / 64, splits);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (in_is_bf16) hipLaunchKernelGGL(colsum_kernel<true>, grid, dim3(256), 0, st, in, out, M, N, ld, rpb);
-  else hipLaunchKernelGGL(colsum_kernel<false>, grid, dim3(256), 0, st, in, out, M, N, ld, rpb);
-  OCTMAE_LAUNCH_CHECK();
-  return 0;
+  return colsum_launch(in, in_is_bf16, out, nullptr, M, N, ld, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int octmae_colsum_ws_rows(int M) {
+  if (M <= 0) return 0;
+  int splits, rpb;
+  colsum_splits(M, &splits, &rpb);
+  return splits > 1 ? splits : 0;
+}
+
+extern "C" int octmae_colsum_accum_ws(const void* in, int in_is_bf16, float* out, float* ws, int M, int N, int ld, void* stream) {
+  OCTMAE_CHECK_ARG(in && out && M > 0 && N > 0 && N % 8 == 0 && ld % 8 == 0);
+  OCTMAE_CHECK_ARG(ws != nullptr || octmae_colsum_ws_rows(M) == 0);
+  return colsum_launch(in, in_is_bf16, out, ws, M, N, ld, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int octmae_patch_gather(const float* imgs, const void* ids, int ids_is_i64, void* out_bf16, int B, int C, int T,

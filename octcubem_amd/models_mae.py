@@ -147,6 +147,14 @@ class MaskedAutoencoderViT(nn.Module):
             object.__setattr__(self, "_lin_views", (arena, v))
         return self._lin_views
 
+    @torch.jit.ignore
+    def set_grad_checkpointing(self, enable=True, mode="full"):
+        """The reference's switch (``model.set_grad_checkpointing()``, main_retclip.py:170), honoured: every Block of the encoder and the decoder keeps only its
+        input and runs its forward again in the backward, as ``torch.utils.checkpoint`` around each block would.  ``mode="light"``
+        (this package's own) rebuilds only the LayerNorm and GELU outputs; ``enable=False`` restores "none".  Results are
+        bit-identical in every mode (video_vit.set_recompute)."""
+        video_vit.set_recompute(self, mode if enable else "none")
+
     def prepare(self):
         """Validate/bind the parameter arena, re-attach .grad views and refresh the bf16 operand copy.
         Called at the top of every forward; cheap (one cast kernel over the arena)."""

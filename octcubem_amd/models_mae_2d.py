@@ -102,6 +102,14 @@ class MaskedAutoencoderViT(nn.Module):
             nn.init.constant_(m.bias, 0)
             nn.init.constant_(m.weight, 1.0)
 
+    @torch.jit.ignore
+    def set_grad_checkpointing(self, enable=True, mode="full"):
+        """The reference's switch (``model.set_grad_checkpointing()``, main_retclip.py:170), honoured: every Block of the encoder and the decoder keeps only its
+        input and runs its forward again in the backward, as ``torch.utils.checkpoint`` around each block would.  ``mode="light"``
+        (this package's own) rebuilds only the LayerNorm and GELU outputs; ``enable=False`` restores "none".  Results are
+        bit-identical in every mode (video_vit.set_recompute)."""
+        video_vit.set_recompute(self, mode if enable else "none")
+
     def prepare(self):
         arena = get_arena(self, full_check=True)
         if torch.is_grad_enabled():

@@ -10,7 +10,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, video_vit
 from .arena import get_arena
 from .video_vit import TimmBlock as Block, TimmPatchEmbed as PatchEmbed, layer_norm
 from ._autocast import autocast_invariant
@@ -62,6 +62,14 @@ class VisionTransformer(nn.Module):
     @torch.jit.ignore
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
+
+    @torch.jit.ignore
+    def set_grad_checkpointing(self, enable=True, mode="full"):
+        """The reference's switch (``model.set_grad_checkpointing()``, main_retclip.py:170), honoured: every Block keeps only its
+        input and runs its forward again in the backward, as ``torch.utils.checkpoint`` around each block would.  ``mode="light"``
+        (this package's own) rebuilds only the LayerNorm and GELU outputs; ``enable=False`` restores "none".  Results are
+        bit-identical in every mode (video_vit.set_recompute)."""
+        video_vit.set_recompute(self, mode if enable else "none")
 
     def prepare(self):
         arena = get_arena(self, full_check=True)

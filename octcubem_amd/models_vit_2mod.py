@@ -16,12 +16,11 @@ from __future__ import annotations
 
 import operator
 from functools import partial
-from typing import Sequence
 
 import torch
 import torch.nn as nn
 
-from . import models_vit_flash_attn, ops
+from . import models_vit_flash_attn, ops, video_vit
 from .arena import get_arena
 from ._autocast import autocast_invariant
 
@@ -92,23 +91,9 @@ class VisionTransformer(models_vit_flash_attn.VisionTransformer):
     def lock(self, unlocked_groups=0, freeze_bn_stats=False):
         """models_vit_flash_attn_2mod.py:221-251: freeze everything, then unfreeze the last ``unlocked_groups`` of [embedding, block 0,
         ..., block n-2, (block n-1, final norm), head]; the modality heads stay frozen, as in the reference."""
-        for param in self.parameters():
-            param.requires_grad = False
-        if unlocked_groups != 0:
-            groups = [[self.patch_embed, self.cls_token, self.pos_embed], *self.blocks[:-1],
-                      [self.blocks[-1], self.fc_norm if hasattr(self, "fc_norm") else self.norm], self.head]
-
-            def _unlock(x):
-                if isinstance(x, Sequence):
-                    for g in x:
-                        _unlock(g)
-                elif isinstance(x, torch.nn.Parameter):
-                    x.requires_grad = True
-                else:
-                    for p in x.parameters():
-                        p.requires_grad = True
-
-            _unlock(groups[-unlocked_groups:])
+        groups = [[self.patch_embed, self.cls_token, self.pos_embed], *self.blocks[:-1],
+                  [self.blocks[-1], self.fc_norm if hasattr(self, "fc_norm") else self.norm], self.head]
+        video_vit.lock_groups(self, groups, unlocked_groups)
 
 
 def flash_attn_vit_large_patch16(**kwargs):

@@ -11,12 +11,11 @@ model (timm layout); flash checkpoints load through ``load_state_dict_to_backbon
 from __future__ import annotations
 
 from functools import partial
-from typing import Sequence
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, video_vit
 from .arena import get_arena
 from .models_vit_flash_attn import VisionTransformer as VisionTransformer2DCenterHead
 from .video_vit import layer_norm
@@ -53,27 +52,13 @@ class VisionTransformerWith3DPoolingHead(VisionTransformer2DCenterHead):
     def lock(self, unlocked_groups=0, freeze_bn_stats=False):
         """Freeze everything, then unfreeze the last ``unlocked_groups`` of: embeddings, blocks[0 .. -2], (last block + fc_norm /
         norm), (fc_aggregate_cls + aggregate_cls_norm + head) -- models_vit_3dhead_flash_attn.py:67-101."""
-        for param in self.parameters():
-            param.requires_grad = False
-        if unlocked_groups != 0:
-            groups = [
-                [self.patch_embed, self.cls_token, self.pos_embed],
-                *self.blocks[:-1],
-                [self.blocks[-1], self.fc_norm if hasattr(self, "fc_norm") else self.norm],
-                [self.fc_aggregate_cls, self.aggregate_cls_norm, self.head],
-            ]
-
-            def _unlock(x):
-                if isinstance(x, Sequence):
-                    for g in x:
-                        _unlock(g)
-                elif isinstance(x, torch.nn.Parameter):
-                    x.requires_grad = True
-                else:
-                    for p in x.parameters():
-                        p.requires_grad = True
-
-            _unlock(groups[-unlocked_groups:])
+        groups = [
+            [self.patch_embed, self.cls_token, self.pos_embed],
+            *self.blocks[:-1],
+            [self.blocks[-1], self.fc_norm if hasattr(self, "fc_norm") else self.norm],
+            [self.fc_aggregate_cls, self.aggregate_cls_norm, self.head],
+        ]
+        video_vit.lock_groups(self, groups, unlocked_groups)
 
 
 def flash_attn_vit_large_patch16_3DSliceHead(**kwargs):

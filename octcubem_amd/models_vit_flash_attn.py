@@ -23,7 +23,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from . import models_vit, ops
+from . import models_vit, ops, video_vit
 from .arena import get_arena
 from .video_vit import layer_norm
 from ._autocast import autocast_invariant
@@ -125,6 +125,14 @@ class VisionTransformer(models_vit.VisionTransformer):
         if hidden_states:
             return x
         return self._head(x)
+
+    def lock(self, unlocked_groups=0, freeze_bn_stats=False):
+        """retinal-COEM/src/open_clip/models_vit_flash_attn.py:202-232: freeze everything, then unfreeze the last ``unlocked_groups``
+        of [embeddings (patch_embed, cls_token, pos_embed), block 0, ..., block n-2, (block n-1, fc_norm / norm), head].  There are no
+        batch-norm statistics to freeze."""
+        groups = [[self.patch_embed, self.cls_token, self.pos_embed], *self.blocks[:-1],
+                  [self.blocks[-1], self.fc_norm if hasattr(self, "fc_norm") else self.norm], self.head]
+        video_vit.lock_groups(self, groups, unlocked_groups)
 
     def load_state_dict_to_backbone(self, state_dict, strict=False, filter_keys=()):
         """Load a timm-layout (RETFound: ``attn.qkv``, ``norm.*``) or flash-layout checkpoint; missing / unexpected block keys are

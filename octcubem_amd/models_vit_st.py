@@ -64,6 +64,14 @@ class VisionTransformer(nn.Module):
     def no_weight_decay(self):
         return {"cls_token", "pos_embed", "pos_embed_spatial", "pos_embed_temporal", "pos_embed_class"}
 
+    @torch.jit.ignore
+    def set_grad_checkpointing(self, enable=True, mode="full"):
+        """The reference's switch (``model.set_grad_checkpointing()``, main_retclip.py:170), honoured: every Block keeps only its
+        input and runs its forward again in the backward, as ``torch.utils.checkpoint`` around each block would.  ``mode="light"``
+        (this package's own) rebuilds only the LayerNorm and GELU outputs; ``enable=False`` restores "none".  Results are
+        bit-identical in every mode (video_vit.set_recompute)."""
+        video_vit.set_recompute(self, mode if enable else "none")
+
     def prepare(self):
         arena = get_arena(self, full_check=True)
         if torch.is_grad_enabled():
@@ -122,6 +130,15 @@ class VisionTransformer(nn.Module):
         if return_embeddings:
             return x, embedding
         return x
+
+    def lock(self, unlocked_groups=0, freeze_bn_stats=False):
+        """retinal-COEM/src/open_clip/models_vit_st_flash_attn_nodrop.py:302-345: freeze everything, then unfreeze the last
+        ``unlocked_groups`` of [embeddings (patch_embed, the positional tables, cls_token), block 0, ..., block n-2, (block n-1, norm),
+        head group].  The head group is whichever of ``fc_aggregate_cls`` / ``aggregate_cls_norm`` / ``head`` this class has (the
+        reference's tower has all three; this one ends in ``head``).  There are no batch-norm statistics to freeze."""
+        first_group = [self.patch_embed, self.pos_embed_spatial, self.pos_embed_temporal, self.pos_embed_class, self.cls_token]
+        head_group = [getattr(self, n, None) for n in ("fc_aggregate_cls", "aggregate_cls_norm", "head")]
+        video_vit.lock_groups(self, [first_group, *self.blocks[:-1], [self.blocks[-1], self.norm], head_group], unlocked_groups)
 
     def load_state_dict_to_backbone(self, state_dict, strict=False, filter_keys=()):
         """Accepts flash-layout keys (mixer.Wqkv / mixer.out_proj) as well as the native attn.q/k/v/proj layout."""

@@ -224,9 +224,13 @@ def cast_bf16_into(src: torch.Tensor, dst: torch.Tensor):
 
 
 def colsum_accum(x2d: torch.Tensor, out: torch.Tensor):
-    """out[c] += sum_r x2d[r][c] (fp32 accumulate)."""
+    """out[c] += sum_r x2d[r][c] (fp32 accumulate).  The additions have a fixed order (octmae_colsum_accum_ws: beyond 256 rows the row
+    splits leave their sums in a workspace and a second launch folds them), so a gradient accumulated over several backwards does not
+    depend on the order the workgroups finish in."""
     M, N = x2d.shape
-    call("octmae_colsum_accum", x2d.data_ptr(), 1 if x2d.dtype == BF16 else 0, out.data_ptr(), M, N, x2d.stride(0), _stream())
+    rows = load().octmae_colsum_ws_rows(M)
+    ws = torch.empty((rows, N), dtype=F32, device=x2d.device) if rows else None
+    call("octmae_colsum_accum_ws", x2d.data_ptr(), 1 if x2d.dtype == BF16 else 0, out.data_ptr(), _p(ws), M, N, x2d.stride(0), _stream())
 
 
 _GEMM_KIND = {(0, 0): "gemm_fwd", (1, 0): "gemm_dgrad", (1, 1): "gemm_wgrad"}
@@ -457,6 +461,31 @@ def layernorm_fwd(x: torch.Tensor, gamma, beta, eps: float):
             lambda: call("octmae_layernorm_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
                          rstd.data_ptr(), M, D, float(eps), _stream()))
     return y, mean, rstd
+
+
+def ln_apply(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta) -> torch.Tensor:
+    """The ``y`` of ``layernorm_fwd(x, gamma, beta, eps)`` rebuilt from the row statistics that call returned: bit-equal, one pass
+    without reductions (octmae_ln_apply).  What a Block that runs at recompute level "light" does instead of keeping y1 / y2."""
+    M, D = _chk(x, F32, "ln_apply input").shape
+    if _chk(mean, F32, "ln_apply mean").numel() != M or _chk(rstd, F32, "ln_apply rstd").numel() != M:
+        raise ValueError(f"ln_apply: {mean.numel()} / {rstd.numel()} row statistics for {M} rows")
+    if gamma.numel() != D or beta.numel() != D:
+        raise ValueError(f"ln_apply: gamma / beta of {gamma.numel()} / {beta.numel()} elements for rows of {D}")
+    y = torch.empty((M, D), dtype=BF16, device=x.device)
+    _launch(f"ln_apply_d{D}", 0.0, 6.0 * M * D + 8.0 * M,
+            lambda: call("octmae_ln_apply", x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                         y.data_ptr(), M, D, _stream()))
+    return y
+
+
+def gelu_apply(pre: torch.Tensor) -> torch.Tensor:
+    """The ``act`` of ``pre, act = linear_fwd(..., "gelu")`` rebuilt from ``pre`` (the stored, 16-bit-rounded pre-activation): bit-equal
+    to the GEMM epilogue's (octmae_gelu_apply).  The element count must be a multiple of 8."""
+    _chk(pre, BF16, "gelu_apply input")
+    act = torch.empty_like(pre)
+    n = pre.numel()
+    _launch("gelu_apply", 0.0, 4.0 * n, lambda: call("octmae_gelu_apply", pre.data_ptr(), act.data_ptr(), n, _stream()))
+    return act
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres=None, want_bf16=False, dxsum=None):
@@ -1642,19 +1671,51 @@ def _sidecar_take(d: torch.Tensor):
     return dxb, colsum
 
 
+RECOMPUTE_NONE, RECOMPUTE_LIGHT, RECOMPUTE_FULL = 0, 1, 2
+
+
+def _block_chain(x2d, Bn, N, H, HD, scale, eps1, eps2, lp, ln, s1, store_dgelu):
+    """A Block's forward up to and including fc1 + GELU: every intermediate BlockFn's backward reads.  The forward runs it, and the
+    backward of a Block at recompute level "full" runs it again on the saved input -- the same launches on the same operands, so
+    (every launch being deterministic) the same bits."""
+    wqkv, bqkv, wproj, bproj, w1, b1 = lp[:6]
+    g1, be1, g2, be2 = ln
+    y1, mean1, rstd1 = layernorm_fwd(x2d, g1, be1, eps1)
+    qkv = linear_fwd(y1, wqkv, bqkv, "bf16")
+    o, lse = attn_fwd(qkv, Bn, N, H, HD, scale)
+    x2 = linear_fwd(o, wproj, bproj, "resid", res=x2d, rowscale=s1, rows_per_scale=N)
+    y2, mean2, rstd2 = layernorm_fwd(x2, g2, be2, eps2)
+    pre, act = linear_fwd(y2, w1, b1, "gelu", store_dgelu=store_dgelu)
+    return mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act
+
+
 class BlockFn(torch.autograd.Function):
     """One pre-norm transformer Block (video_vit.py:181-184) as a single autograd node.
 
     forward : x -> LN1 -> Wqkv -> attention -> proj (+x) -> LN2 -> fc1 + GELU -> fc2 (+x2)          (7 launches)
     backward: the same chain in reverse with everything that only existed to please per-op autograd fused away:
               both residual gradient adds and the bf16 gradient copy happen inside the LayerNorm backward kernels, which also
-              produce the proj / fc2 bias gradients (column sums of what they write); GELU' is the fc2-dgrad epilogue."""
+              produce the proj / fc2 bias gradients (column sums of what they write); GELU' is the fc2-dgrad epilogue.
+
+    ``recompute`` -- what the node keeps for its backward, per token and block at width C, hidden 4 C and 16-bit operands:
+      0 none   36 C bytes: x, y1, qkv, o, x2, y2, pre, act (+ the row statistics and lse); nothing is rebuilt.
+      1 light  24 C bytes: y1, y2 and act are dropped.  The backward rebuilds the LayerNorm outputs from the saved row statistics
+               (ln_apply) and the GELU output from the stored pre-activation (gelu_apply): three memory-bound passes, launched only
+               when weight gradients are wanted (nothing else reads the three).  With OCTMAE_GELU_PRIME_FWD=1 ``pre`` holds GELU'
+               and the GELU output cannot be rebuilt from it: ``act`` then stays saved (28 C bytes).
+      2 full    4 C bytes: x only (with the weights and the stochastic-depth factors).  The backward runs the forward chain again up
+               to fc1 + GELU -- not the fc2 GEMM, whose output nothing reads -- and then proceeds as at level 0.
+    The rebuilt tensors are bit-equal to the dropped ones, so the backward of every level runs the same launches on the same operands:
+    outputs and input gradients are bit-identical, and so are the parameter gradients wherever level 0 repeats itself (everywhere but
+    in split-K weight gradients that add fp32 atomically, at large sizes).  The stochastic-depth factors are the saved ones, never redrawn."""
 
     @staticmethod
-    def forward(ctx, x, H, eps1, eps2, lp, grads, s1, s2, final_residual, *params):
+    def forward(ctx, x, H, eps1, eps2, lp, grads, s1, s2, final_residual, recompute, *params):
         """s1 / s2: None, or fp32 [B] per-sample stochastic-depth factors (0 or 1/keep_prob) of the attention / MLP branch.
         final_residual=False returns the MLP branch alone (flash_compat: what flash-attn's prenorm Block hands back as
         ``hidden_states`` and the reference's flash models feed to the final norm, models_mae_joint_res_flash_attn.py:480-489)."""
+        if recompute not in (RECOMPUTE_NONE, RECOMPUTE_LIGHT, RECOMPUTE_FULL):
+            raise ValueError(f"BlockFn: recompute level {recompute!r} (0 none, 1 light, 2 full)")
         shp = x.shape
         C = shp[-1]
         Bn, N = shp[0], shp[1]
@@ -1665,19 +1726,23 @@ class BlockFn(torch.autograd.Function):
         wqkv, bqkv, wproj, bproj, w1, b1, w2, b2 = lp
         g1, be1, g2, be2 = params[0], params[1], params[2], params[3]
         x2d = _chk(x.reshape(-1, C), F32, "block input")
-        y1, mean1, rstd1 = layernorm_fwd(x2d, g1, be1, eps1)
-        qkv = linear_fwd(y1, wqkv, bqkv, "bf16")
-        o, lse = attn_fwd(qkv, Bn, N, H, HD, scale)
-        x2 = linear_fwd(o, wproj, bproj, "resid", res=x2d, rowscale=s1, rows_per_scale=N)
-        y2, mean2, rstd2 = layernorm_fwd(x2, g2, be2, eps2)
         ctx.pre_is_dgelu, ctx.fc1_bias = GELU_PRIME_FWD, b1 is not None
-        pre, act = linear_fwd(y2, w1, b1, "gelu", store_dgelu=ctx.pre_is_dgelu)
+        mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act = _block_chain(
+            x2d, Bn, N, H, HD, scale, eps1, eps2, lp, (g1, be1, g2, be2), s1, ctx.pre_is_dgelu)
         if final_residual:
             x3 = linear_fwd(act, w2, b2, "resid", res=x2, rowscale=s2, rows_per_scale=N)
         else:
             x3, s2 = linear_fwd(act, w2, b2, "f32"), None
         ctx.final_residual = final_residual
-        ctx.save_for_backward(x2d, mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act, wqkv, wproj, w1, w2, g1, g2)
+        ctx.recompute = recompute
+        if recompute == RECOMPUTE_NONE:
+            ctx.save_for_backward(x2d, mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act, wqkv, wproj, w1, w2, g1, g2)
+        elif recompute == RECOMPUTE_LIGHT:
+            ctx.save_for_backward(x2d, mean1, rstd1, None, qkv, o, lse, x2, mean2, rstd2, None, pre, act if ctx.pre_is_dgelu else None,
+                                  wqkv, wproj, w1, w2, g1, g2, be1, be2)
+        else:
+            ctx.save_for_backward(x2d, wqkv, wproj, w1, w2, g1, g2, be1, be2, bqkv, bproj, b1)
+            ctx.eps = (eps1, eps2)
         ctx.scales = (s1, s2)
         ctx.meta = (Bn, N, H, HD, scale, shp)
         ctx.grads, ctx.params = grads, params
@@ -1687,9 +1752,16 @@ class BlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx3, dx2_in=None):
-        x2d, mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act, wqkv, wproj, w1, w2, g1, g2 = ctx.saved_tensors
         Bn, N, H, HD, scale, shp = ctx.meta
         C = H * HD
+        s1, s2 = ctx.scales
+        if ctx.recompute == RECOMPUTE_FULL:
+            x2d, wqkv, wproj, w1, w2, g1, g2, be1, be2, bqkv, bproj, b1 = ctx.saved_tensors
+            with torch.no_grad():
+                mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act = _block_chain(
+                    x2d, Bn, N, H, HD, scale, *ctx.eps, (wqkv, bqkv, wproj, bproj, w1, b1), (g1, be1, g2, be2), s1, ctx.pre_is_dgelu)
+        else:
+            x2d, mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act, wqkv, wproj, w1, w2, g1, g2, *betas = ctx.saved_tensors
         wg = _weight_grads      # off: every parameter-gradient side output below is a null pointer, the launches are the same
         (gg1, gb1n, gg2, gb2n, gwqkv, gbqkv, gwproj, gbproj, gw1, gb1, gw2, gb2) = ctx.grads() if wg else (None,) * 12
         if dx3.dtype != F32 or not dx3.is_contiguous():
@@ -1713,7 +1785,11 @@ class BlockFn(torch.autograd.Function):
         # ---- MLP
         dpre = linear_dgrad(d3b, w2, pre=pre, colsum=gb1, pre_is_dgelu=ctx.pre_is_dgelu, fold_entry=ctx.fc1_bias and not wg)   # GELU' and fc1's bias gradient in the epilogue
         if wg:
+            if ctx.recompute == RECOMPUTE_LIGHT:      # only the weight gradients read the two
+                act = gelu_apply(pre) if act is None else act
+                y2 = ln_apply(x2, mean2, rstd2, g2, betas[1])
             linear_wgrad_accum_pair((d3b, act, gw2, None), (dpre, y2, gw1, None))
+            act = y2 = None
         dy2 = linear_dgrad(dpre, w1)
         # ---- LN2 backward + residual add + bf16 copy + proj bias gradient
         if ctx.final_residual:
@@ -1734,6 +1810,8 @@ class BlockFn(torch.autograd.Function):
         # the qkv bias gradient rides in the weight-gradient GEMM (column sums of its dY operand); fusing it into the attention
         # backward kernels had been measured and dropped (+10..25 % on their main loops for a 2 % pass)
         if wg:
+            if ctx.recompute == RECOMPUTE_LIGHT:
+                y1 = ln_apply(x2d, mean1, rstd1, g1, betas[0])
             linear_wgrad_accum_pair((dx2b, o, gwproj, None), (dqkv, y1, gwqkv, gbqkv))
         dy1 = linear_dgrad(dqkv, wqkv)
         # ---- LN1 backward + residual add; its bf16 copy / column sums are what the previous Block's backward needs
@@ -1743,7 +1821,7 @@ class BlockFn(torch.autograd.Function):
             notify_grad_ready(ctx.params)
         dx = dx.view(shp)
         _sidecar_put(dx, dxb.view(shp), colsum)
-        return (dx, None, None, None, None, None, None, None, None) + (None,) * len(ctx.params)
+        return (dx, None, None, None, None, None, None, None, None, None) + (None,) * len(ctx.params)
 
 
 class EncAssembleFn(torch.autograd.Function):

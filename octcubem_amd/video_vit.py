@@ -256,10 +256,69 @@ def layer_norm(norm: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
     return ops.LayerNormFn.apply(x, norm.weight, norm.bias, norm.eps)
 
 
+RECOMPUTE_LEVELS = {"none": ops.RECOMPUTE_NONE, "light": ops.RECOMPUTE_LIGHT, "full": ops.RECOMPUTE_FULL}
+
+
+def _recompute_level(mode) -> int:
+    try:
+        return RECOMPUTE_LEVELS[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"recompute mode {mode!r}: one of {', '.join(map(repr, RECOMPUTE_LEVELS))}") from None
+
+
+def set_recompute(module: nn.Module, mode: str) -> int:
+    """Set the activation-recomputation mode of every Block (FlashBlock, TimmBlock) at or below ``module``; returns how many there are.
+      "none"   every Block keeps all its intermediates for the backward (36 C bytes per token at width C): the default;
+      "light"  the two LayerNorm outputs and the GELU output are rebuilt in the backward (24 C bytes);
+      "full"   only the Block's input is kept and its forward is run again in the backward (4 C bytes) -- what
+               ``torch.utils.checkpoint`` around every block would give.
+    Losses and gradients are bit-identical in the three modes (ops.BlockFn)."""
+    _recompute_level(mode)
+    n = 0
+    for m in module.modules():
+        if isinstance(m, Block):
+            m.recompute = mode
+            n += 1
+    return n
+
+
+def lock_groups(module: nn.Module, groups, unlocked_groups: int = 0):
+    """The ``lock(unlocked_groups)`` of the reference's towers: freeze every parameter of ``module``, then unfreeze the last
+    ``unlocked_groups`` entries of ``groups`` (modules, parameters, None, or nested lists of them).  A frozen parameter also gives up
+    its ``grad``: after a first forward that is a zero-filled view of the gradient arena, and an optimizer that steps every parameter
+    with a gradient would let weight decay move the locked weights.  ``arena.rebind_grads()`` (every training forward) re-attaches
+    what is unlocked here or later."""
+    for p in module.parameters():
+        p.requires_grad = False
+
+    def _unlock(x):
+        if x is None:
+            return
+        if isinstance(x, torch.nn.Parameter):
+            x.requires_grad = True
+        elif isinstance(x, nn.Module):
+            for p in x.parameters():
+                p.requires_grad = True
+        else:
+            for g in x:
+                _unlock(g)
+
+    if unlocked_groups != 0:
+        _unlock(list(groups)[-unlocked_groups:])
+    for p in module.parameters():
+        if not p.requires_grad:
+            p.grad = None
+
+
 @autocast_invariant
 class Block(nn.Module):
     """Transformer Block with specified Attention function (pre-norm residual, video_vit.py:181-184).
-    The residual stream is fp32; both residual adds are fused into GEMM epilogues."""
+    The residual stream is fp32; both residual adds are fused into GEMM epilogues.
+
+    ``recompute`` ("none" | "light" | "full", see ``set_recompute``): what the fused Block keeps for its backward; read in forward,
+    without effect when grad is disabled and on the unfused path."""
+
+    recompute = "none"
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=False, qk_scale=None, drop=0.0, attn_drop=0.0, drop_path=0.0,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm, attn_func=Attention):
@@ -302,7 +361,7 @@ class Block(nn.Module):
             if not no_drop:     # stochastic depth: one keep/drop draw per sample and branch, folded into the residual epilogues
                 s1, s2 = self.drop_path.sample(x.shape[0], x.device), self.drop_path.sample(x.shape[0], x.device)
             out = ops.BlockFn.apply(x, self.attn.num_heads, self.norm1.eps, self.norm2.eps, lp, grads, s1, s2, final_residual,
-                                    *params)
+                                    _recompute_level(self.recompute), *params)
             if final_residual:
                 return out
             return out if return_stream else out[0]
@@ -402,7 +461,8 @@ class FlashBlock(Block):
         s1 = None
         if self.training and self.drop_path2.drop_prob > 0.0:
             s1 = self.drop_path2.sample(x.shape[0], x.device)
-        return ops.BlockFn.apply(x, self.mixer.num_heads, self.norm1.eps, self.norm2.eps, lp, grads, s1, None, False, *params)
+        return ops.BlockFn.apply(x, self.mixer.num_heads, self.norm1.eps, self.norm2.eps, lp, grads, s1, None, False,
+                                 _recompute_level(self.recompute), *params)
 
 
 def create_block(embed_dim, num_heads, mlp_ratio, qkv_bias, drop_rate, attn_drop_rate, drop_path1, drop_path2, norm_layer,
