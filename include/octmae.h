@@ -50,8 +50,10 @@ extern "C" {
  *     the COEM classification head, csrc/join.hip.
  * 26: octmae_ln_apply (csrc/layernorm.hip), octmae_gelu_apply (csrc/recompute.hip): the LayerNorm and GELU outputs rebuilt in the
  *     backward of a Block that did not keep them (activation recomputation, ops.BlockFn); octmae_colsum_accum_ws (+ octmae_colsum_ws_rows):
- *     the bias-gradient column sums with a fixed order of additions. */
-#define OCTMAE_ABI_VERSION 26
+ *     the bias-gradient column sums with a fixed order of additions.
+ * 27: octmae_dwconv7_fwd / _bwd_input / _bwd_weight (+ _ws_floats), octmae_layer_scale_fwd / _bwd (+ _ws_floats): the depthwise 7x7
+ *     convolution and the layer scale of a ConvNeXt layer (the SLIViT baseline's feature extractor, csrc/convnext.hip). */
+#define OCTMAE_ABI_VERSION 27
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -576,6 +578,33 @@ int octmae_join_fwd(const float* f0, const float* f1, const float* f2, int prese
 int octmae_join_bwd(const float* dy, const float* dn_extra, const float* f0, const float* f1, const float* f2, const float* inv_norm,
                     const float* mean, const float* rstd, const float* gamma, int present_mask, float* df_out, float* dgamma,
                     float* dbeta, float* ws, int B, int D, int M, void* stream);
+
+/* ---- ConvNeXt layer: depthwise 7x7 convolution and layer scale (csrc/convnext.hip) -------------------------
+ * What HF's ConvNextLayer (transformers/models/convnext/modeling_convnext.py, reached from OCTCube/model_slivit_baseline.py:72-85) gets
+ * from nn.Conv2d(C, C, 7, padding=3, groups=C), its autograd, and `residual + layer_scale_parameter * x`.
+ * All tensors are channels-last fp32: x, z, dz, dx, dres [B][H][W][C] = [M = B H W][C] rows; wt f32 [C][7][7], bias f32 [C]; C % 8 == 0,
+ * any H, W >= 1 (also maps smaller than the filter).  Nothing is rounded to 16 bits except dbranch_lp.
+ *   octmae_dwconv7_fwd        z[b,h,w,c]  = bias[c] + sum_{i,j in 0..6} wt[c,i,j] x[b, h+i-3, w+j-3, c], zero outside the map (cross-
+ *                             correlation, as nn.Conv2d computes)
+ *   octmae_dwconv7_bwd_input  dx[b,h,w,c] = dres[b,h,w,c] + sum_{i,j} wt[c,i,j] dz[b, h-i+3, w-j+3, c]; dres (may be NULL) is the gradient
+ *                             arriving on the residual path, added LAST: the result is (the result without dres) + dres exactly
+ *   octmae_dwconv7_bwd_weight gw[c,i,j] += sum_{b,h,w} dz[b,h,w,c] x[b, h+i-3, w+j-3, c],  gb[c] += sum dz[b,h,w,c]: per-workgroup partial
+ *                             sums in ws (at least octmae_dwconv7_bwd_weight_ws_floats(B, H, W, C) floats = G * 50 * C, G the number of
+ *                             partials) folded in ascending order by a second launch; no float atomics, two runs are bit-equal
+ *   octmae_layer_scale_fwd    out[m,c] = res[m,c] + gamma[c] * branch[m,c]: one fp32 multiply, one fp32 add (not fused)
+ *   octmae_layer_scale_bwd    dbranch_lp[m,c] = gamma[c] * dout[m,c] rounded once to the 16-bit operand type (octmae_lp_dtype);
+ *                             ggamma[c] += sum_m dout[m,c] * branch[m,c] when ggamma is not NULL (then branch and ws, at least
+ *                             octmae_layer_scale_bwd_ws_floats(M, C) floats = G * C, are needed), folded in a fixed order as above
+ * Every fp32 pointer must be 16-byte aligned (wt, gw, gb, ggamma: word accesses, 4 bytes), dbranch_lp 8-byte aligned.
+ * -1, before any launch: C % 8 != 0, an empty or out-of-range shape, a NULL or misaligned pointer (the _ws_floats queries return -1). */
+int octmae_dwconv7_fwd(const float* x, const float* wt, const float* bias, float* z, int B, int H, int W, int C, void* stream);
+int octmae_dwconv7_bwd_input(const float* dz, const float* wt, const float* dres, float* dx, int B, int H, int W, int C, void* stream);
+int octmae_dwconv7_bwd_weight_ws_floats(int B, int H, int W, int C);
+int octmae_dwconv7_bwd_weight(const float* dz, const float* x, float* gw, float* gb, float* ws, int B, int H, int W, int C, void* stream);
+int octmae_layer_scale_fwd(const float* res, const float* branch, const float* gamma, float* out, int M, int C, void* stream);
+int octmae_layer_scale_bwd_ws_floats(int M, int C);
+int octmae_layer_scale_bwd(const float* dout, const float* branch, const float* gamma, void* dbranch_lp, float* ggamma, float* ws, int M, int C,
+                           void* stream);
 
 /* ---- mixup / cutmix of a fine-tune batch (csrc/mixup.hip) ---------------------------------------------
  * timm.data.Mixup's three modes on the device, in place, in one launch; the decisions are the host's (octcubem_amd/mixup.py).

@@ -47,6 +47,13 @@ SIGNATURES = {
     "octmae_join_ws_floats": [_i, _i, _i],
     "octmae_join_fwd": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "octmae_join_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "octmae_dwconv7_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "octmae_dwconv7_bwd_input": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "octmae_dwconv7_bwd_weight_ws_floats": [_i, _i, _i, _i],
+    "octmae_dwconv7_bwd_weight": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "octmae_layer_scale_fwd": [_vp, _vp, _vp, _vp, _i, _i, _vp],
+    "octmae_layer_scale_bwd_ws_floats": [_i, _i],
+    "octmae_layer_scale_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "octmae_mix_batch": [_vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp],
     "octmae_attn_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "octmae_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],

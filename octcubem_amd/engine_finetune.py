@@ -4,7 +4,8 @@ mixup callable, forward, non-finite guard, ``loss_scaler(loss / accum_iter, clip
 zero_grad on step boundaries, min/max group LR logging, scalar loss all-reduce.
 
 Not reproduced: the per-iteration ``torch.cuda.synchronize()`` and logits printing (pipeline stalls with no numerical effect),
-and the 2-D/3-D ``variable_joint`` and SLIViT reshapes (models outside SURVEY §8).  ``evaluate`` returns loss, top-1 accuracy and
+and the 2-D/3-D ``variable_joint`` reshape (a model outside SURVEY §8).  The SLIViT reshape (:417-419, :572-574) is applied when
+``args.patient_dataset_type == "convnext_slivit"``: the slices of a volume laid side by side for model_slivit_baseline.SLIViT.  ``evaluate`` returns loss, top-1 accuracy and
 the gathered logits / targets for a caller with metric code of its own; ``evaluate_report`` is the reference's ``evaluate`` (:498-813)
 with its signature, its return value and its CSV files, the ranking metrics from the rank-count kernel (ops.rank_counts,
 octcubem_amd/metrics.py) in place of scikit-learn, and the confusion matrix as a CSV of integers in place of the pycm / matplotlib JPEG.
@@ -29,6 +30,15 @@ import torch
 from . import losses, lr_sched, metrics, misc
 
 
+def _slivit_reshape(samples: torch.Tensor, args) -> torch.Tensor:
+    """engine_finetune.py:417-419 / :572-574, for ``patient_dataset_type`` ``convnext_slivit`` only: ``permute(0, 2, 3, 4, 1)`` then
+    ``reshape(-1, s[1], s[2], s[3] * s[4])`` of the permuted shape ``s``, exactly as the reference writes it.  Anything else passes through."""
+    if getattr(args, "patient_dataset_type", None) != "convnext_slivit":
+        return samples
+    samples = samples.permute(0, 2, 3, 4, 1)
+    return samples.reshape(-1, samples.shape[1], samples.shape[2], samples.shape[3] * samples.shape[4])
+
+
 def train_one_epoch(model: torch.nn.Module, criterion: torch.nn.Module, data_loader: Iterable, optimizer: torch.optim.Optimizer,
                     device: torch.device, epoch: int, loss_scaler, max_norm: float = 0, mixup_fn=None, log_writer=None, args=None):
     model.train(True)
@@ -50,6 +60,7 @@ def train_one_epoch(model: torch.nn.Module, criterion: torch.nn.Module, data_loa
         targets = targets.to(device, non_blocking=True)
         if float_targets:
             targets = targets.float()
+        samples = _slivit_reshape(samples, args)
         if mixup_fn is not None:
             samples, targets = mixup_fn(samples, targets)
         outputs = model(samples)
@@ -80,15 +91,16 @@ def train_one_epoch(model: torch.nn.Module, criterion: torch.nn.Module, data_loa
 
 
 @torch.no_grad()
-def evaluate(data_loader: Iterable, model: torch.nn.Module, device: torch.device, criterion: Optional[torch.nn.Module] = None):
-    """Eval-mode pass: ``{"loss", "acc1", "logits" [n, C], "targets" [n]}`` (logits / targets on the host, fp32)."""
+def evaluate(data_loader: Iterable, model: torch.nn.Module, device: torch.device, criterion: Optional[torch.nn.Module] = None, args=None):
+    """Eval-mode pass: ``{"loss", "acc1", "logits" [n, C], "targets" [n]}`` (logits / targets on the host, fp32).  ``args`` is read for
+    ``patient_dataset_type`` only (the SLIViT reshape)."""
     criterion = criterion or torch.nn.CrossEntropyLoss()
     model.eval()
     logits_all, targets_all, loss_sum, n = [], [], 0.0, 0
     for samples, targets in misc.prefetched(data_loader, device, None, only=(0, 1)):
         samples = samples.to(device, non_blocking=True)
         targets = targets.to(device, non_blocking=True)
-        out = model(samples).float()
+        out = model(_slivit_reshape(samples, args)).float()
         t = targets.float() if isinstance(criterion, torch.nn.BCEWithLogitsLoss) else targets
         loss_sum += float(criterion(out, t)) * samples.shape[0]
         n += samples.shape[0]
@@ -167,7 +179,7 @@ def evaluate_report(data_loader, model, device, task, epoch, mode, num_class, cr
     for batch in misc.prefetched(data_loader, device, args, only=(0, 1)):
         samples = batch[0].to(device, non_blocking=True)
         targets = batch[-1].to(device, non_blocking=True)
-        out = model(samples)
+        out = model(_slivit_reshape(samples, args))
         with torch.autocast(device.type, enabled=False):
             out = out.float()
             loss = criterion(out, targets.float() if float_targets else targets)
@@ -278,7 +290,7 @@ def evaluate_task_report(data_loader, model, device, task, epoch, mode, num_clas
     for batch in misc.prefetched(data_loader, device, args, only=(0, 1)):
         samples = batch[0].to(device, non_blocking=True)
         targets = batch[-1].to(device, non_blocking=True)
-        out = model(samples)
+        out = model(_slivit_reshape(samples, args))
         with torch.autocast(device.type, enabled=False):
             out = out.float()
             if not whole_set_loss:

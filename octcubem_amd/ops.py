@@ -503,6 +503,109 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres=None, want_bf16=
 
 
 
+# ------------------------------------------------------------------------------------------------
+# ConvNeXt layer (csrc/convnext.hip): depthwise 7x7 convolution and layer scale, channels-last fp32
+# ------------------------------------------------------------------------------------------------
+def _chk_nhwc(t: torch.Tensor, name: str):
+    _chk(t, F32, name)
+    if t.dim() != 4:
+        raise RuntimeError(f"{name}: expected a channels-last [B, H, W, C] tensor, got {tuple(t.shape)}")
+    if t.shape[3] % 8:
+        raise RuntimeError(f"{name}: C = {t.shape[3]} is not a multiple of 8")
+    return tuple(int(v) for v in t.shape)
+
+
+def _chk_dw_weight(wt: torch.Tensor, C: int, name: str):
+    _chk(wt, F32, name)
+    if wt.numel() != C * 49 or wt.shape[0] != C or tuple(wt.shape[-2:]) != (7, 7):
+        raise RuntimeError(f"{name}: expected [{C}, 7, 7] (or [{C}, 1, 7, 7]), got {tuple(wt.shape)}")
+
+
+def _chk_vec(v: torch.Tensor, C: int, name: str):
+    _chk(v, F32, name)
+    if v.numel() != C:
+        raise RuntimeError(f"{name}: expected {C} elements, got {tuple(v.shape)}")
+
+
+def dwconv7_fwd(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """z[b,h,w,c] = bias[c] + sum_ij wt[c,i,j] x[b, h+i-3, w+j-3, c] (zero padding): nn.Conv2d(C, C, 7, padding=3, groups=C) on a
+    channels-last fp32 map [B, H, W, C], C % 8 == 0, any H, W >= 1."""
+    B, H, W, C = _chk_nhwc(x, "dwconv7_fwd x")
+    _chk_dw_weight(wt, C, "dwconv7_fwd weight"); _chk_vec(bias, C, "dwconv7_fwd bias")
+    z = torch.empty_like(x)
+    n = float(x.numel())
+    _launch(f"dwconv7_fwd_c{C}", 2.0 * 49 * n, 8.0 * n,
+            lambda: call("octmae_dwconv7_fwd", x.data_ptr(), wt.data_ptr(), bias.data_ptr(), z.data_ptr(), B, H, W, C, _stream()))
+    return z
+
+
+def dwconv7_bwd_input(dz: torch.Tensor, wt: torch.Tensor, dres: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx = dres + sum_ij wt[c,i,j] dz[b, h-i+3, w-j+3, c]; ``dres`` (fp32, the shape of dz) is added last, exactly."""
+    B, H, W, C = _chk_nhwc(dz, "dwconv7_bwd_input dz")
+    _chk_dw_weight(wt, C, "dwconv7_bwd_input weight")
+    if dres is not None and _chk(dres, F32, "dwconv7_bwd_input dres").shape != dz.shape:
+        raise RuntimeError(f"dwconv7_bwd_input: dres {tuple(dres.shape)} for dz {tuple(dz.shape)}")
+    dx = torch.empty_like(dz)
+    n = float(dz.numel())
+    _launch(f"dwconv7_bwd_input_c{C}", 2.0 * 49 * n, (8.0 if dres is None else 12.0) * n,
+            lambda: call("octmae_dwconv7_bwd_input", dz.data_ptr(), wt.data_ptr(), _p(dres), dx.data_ptr(), B, H, W, C, _stream()))
+    return dx
+
+
+def dwconv7_bwd_weight(dz: torch.Tensor, x: torch.Tensor, gw: torch.Tensor, gb: torch.Tensor):
+    """gw[c,i,j] += sum dz[b,h,w,c] x[b, h+i-3, w+j-3, c], gb[c] += sum dz: fp32 accumulation in a fixed order (two launches: partial sums
+    per workgroup, then their fold), so two runs are bit-equal."""
+    B, H, W, C = _chk_nhwc(dz, "dwconv7_bwd_weight dz")
+    if _chk_nhwc(x, "dwconv7_bwd_weight x") != (B, H, W, C):
+        raise RuntimeError(f"dwconv7_bwd_weight: x {tuple(x.shape)} for dz {tuple(dz.shape)}")
+    _chk_dw_weight(gw, C, "dwconv7_bwd_weight gw"); _chk_vec(gb, C, "dwconv7_bwd_weight gb")
+    nws = load().octmae_dwconv7_bwd_weight_ws_floats(B, H, W, C)
+    if nws <= 0:
+        raise RuntimeError(f"dwconv7_bwd_weight: unsupported shape {(B, H, W, C)}")
+    ws = torch.empty((nws,), dtype=F32, device=dz.device)
+    n = float(dz.numel())
+    _launch(f"dwconv7_bwd_weight_c{C}", 2.0 * 49 * n, 8.0 * n + 8.0 * nws,
+            lambda: call("octmae_dwconv7_bwd_weight", dz.data_ptr(), x.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(), B, H, W, C,
+                         _stream()))
+
+
+def _chk_rows(t: torch.Tensor, dtype, name: str):
+    _chk(t, dtype, name)
+    if t.dim() != 2 or t.shape[1] % 8:
+        raise RuntimeError(f"{name}: expected [M, C] rows with C % 8 == 0, got {tuple(t.shape)}")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def layer_scale_fwd(res: torch.Tensor, branch: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
+    """out = res + gamma[c] * branch on fp32 rows [M, C]: bit-equal to torch's fp32 mul followed by add."""
+    M, C = _chk_rows(res, F32, "layer_scale_fwd res")
+    if _chk_rows(branch, F32, "layer_scale_fwd branch") != (M, C):
+        raise RuntimeError(f"layer_scale_fwd: branch {tuple(branch.shape)} for res {tuple(res.shape)}")
+    _chk_vec(gamma, C, "layer_scale_fwd gamma")
+    out = torch.empty_like(res)
+    _launch(f"layer_scale_fwd_c{C}", 2.0 * M * C, 12.0 * M * C,
+            lambda: call("octmae_layer_scale_fwd", res.data_ptr(), branch.data_ptr(), gamma.data_ptr(), out.data_ptr(), M, C, _stream()))
+    return out
+
+
+def layer_scale_bwd(dout: torch.Tensor, branch: Optional[torch.Tensor], gamma: torch.Tensor, ggamma: Optional[torch.Tensor] = None):
+    """dbranch = gamma[c] * dout in the 16-bit operand type (one rounding); with ``ggamma`` (fp32 [C]) also
+    ggamma[c] += sum_m dout[m,c] * branch[m,c], in a fixed order."""
+    M, C = _chk_rows(dout, F32, "layer_scale_bwd dout")
+    _chk_vec(gamma, C, "layer_scale_bwd gamma")
+    ws = None
+    if ggamma is not None:
+        _chk_vec(ggamma, C, "layer_scale_bwd ggamma")
+        if branch is None or _chk_rows(branch, F32, "layer_scale_bwd branch") != (M, C):
+            raise RuntimeError("layer_scale_bwd: the gamma gradient needs branch, fp32 and of dout's shape")
+        ws = torch.empty((load().octmae_layer_scale_bwd_ws_floats(M, C),), dtype=F32, device=dout.device)
+    dbranch = torch.empty((M, C), dtype=BF16, device=dout.device)
+    _launch(f"layer_scale_bwd_c{C}", 2.0 * M * C, (6.0 if ggamma is None else 10.0) * M * C,
+            lambda: call("octmae_layer_scale_bwd", dout.data_ptr(), _p(branch) if ggamma is not None else None, gamma.data_ptr(),
+                         dbranch.data_ptr(), _p(ggamma), _p(ws), M, C, _stream()))
+    return dbranch
+
+
 def slice_pool_fwd(x: torch.Tensor, gamma, beta, eps: float, S: int, cls: bool):
     """x fp32 [B*S, T, D] -> out fp32 [B, D] = mean over the S slices of LayerNorm(mean of tokens 1..T-1, or token 0); with the
     pooled rows and their LayerNorm statistics (saved for the backward)."""
@@ -1586,6 +1689,49 @@ class MlpFn(torch.autograd.Function):
             notify_grad_ready(ctx.params)
         dy = linear_dgrad(dpre, w1_lp).view(ctx.shp)
         return (dy, dout if ctx.has_res else None, None, None, None, None, None) + (None,) * len(ctx.params)
+
+
+class ConvNextLayerFn(torch.autograd.Function):
+    """HF ConvNextLayer on a channels-last fp32 map [B, H, W, C]: depthwise 7x7 convolution (fp32) -> LayerNorm over C (eps 1e-6, 16-bit
+    output) -> pwconv1 with the GELU epilogue -> pwconv2 (fp32 output) -> x + layer_scale * branch.  ``views`` = (dw weight [C, 7, 7], dw
+    bias, LayerNorm weight, LayerNorm bias, layer scale) as fp32 arena views, (w1, w2) the 16-bit operand views and (b1, b2) the fp32
+    biases of the two Linears; ``grads()`` returns the gradient views (gdw, gdwb, gln_w, gln_b, gw1, gb1, gw2, gb2, ggamma)."""
+
+    @staticmethod
+    def forward(ctx, x, views, w1_lp, b1_32, w2_lp, b2_32, grads, eps, *params):
+        dw_w, dw_b, ln_w, ln_b, gamma = views
+        B, H, W, C = x.shape
+        x = _chk(x, F32, "ConvNextLayerFn input")
+        z = dwconv7_fwd(x, dw_w, dw_b)
+        z2 = z.view(-1, C)
+        y, mean, rstd = layernorm_fwd(z2, ln_w, ln_b, eps)
+        pre, act = linear_fwd(y, w1_lp, b1_32, "gelu")
+        branch = linear_fwd(act, w2_lp, b2_32, "f32")
+        out = layer_scale_fwd(x.view(-1, C), branch, gamma)
+        ctx.save_for_backward(x, z2, mean, rstd, y, pre, act, branch, dw_w, ln_w, gamma, w1_lp, w2_lp)
+        ctx.grads, ctx.params = grads, params
+        return out.view(B, H, W, C)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, z2, mean, rstd, y, pre, act, branch, dw_w, ln_w, gamma, w1_lp, w2_lp = ctx.saved_tensors
+        B, H, W, C = x.shape
+        wg = _weight_grads
+        gdw, gdwb, gln_w, gln_b, gw1, gb1, gw2, gb2, ggamma = ctx.grads() if wg else (None,) * 9
+        dout = dout if dout.is_contiguous() else dout.contiguous()
+        d2 = _chk(dout.view(-1, C), F32, "ConvNextLayerFn gradient")
+        dbr = layer_scale_bwd(d2, branch, gamma, ggamma)
+        dpre = linear_dgrad(dbr, w2_lp, pre=pre, colsum=gb1, fold_entry=not wg)
+        if wg:
+            linear_wgrad_accum_pair((dbr, act, gw2, gb2), (dpre, y, gw1, None))
+        dy = linear_dgrad(dpre, w1_lp)
+        dz, _ = layernorm_bwd(dy, z2, mean, rstd, ln_w, gln_w, gln_b)
+        dz = dz.view(B, H, W, C)
+        if wg:
+            dwconv7_bwd_weight(dz, x, gdw, gdwb)
+            notify_grad_ready(ctx.params)
+        dx = dwconv7_bwd_input(dz, dw_w, dres=dout) if ctx.needs_input_grad[0] else None
+        return (dx,) + (None,) * (7 + len(ctx.params))
 
 
 class MlpPairFn(torch.autograd.Function):
