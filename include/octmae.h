@@ -52,8 +52,10 @@ extern "C" {
  *     backward of a Block that did not keep them (activation recomputation, ops.BlockFn); octmae_colsum_accum_ws (+ octmae_colsum_ws_rows):
  *     the bias-gradient column sums with a fixed order of additions.
  * 27: octmae_dwconv7_fwd / _bwd_input / _bwd_weight (+ _ws_floats), octmae_layer_scale_fwd / _bwd (+ _ws_floats): the depthwise 7x7
- *     convolution and the layer scale of a ConvNeXt layer (the SLIViT baseline's feature extractor, csrc/convnext.hip). */
-#define OCTMAE_ABI_VERSION 27
+ *     convolution and the layer scale of a ConvNeXt layer (the SLIViT baseline's feature extractor, csrc/convnext.hip).
+ * 28: octmae_slab_norm_fwd, octmae_slab_norm_bwd (+ octmae_slabnorm_ws_floats): the LayerNorm over a transposed token slab in front of
+ *     the SLIViT head's patch projection (the OCTCube trunk with the SLIViT slice head, csrc/slabnorm.hip). */
+#define OCTMAE_ABI_VERSION 28
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -578,6 +580,35 @@ int octmae_join_fwd(const float* f0, const float* f1, const float* f2, int prese
 int octmae_join_bwd(const float* dy, const float* dn_extra, const float* f0, const float* f1, const float* f2, const float* inv_norm,
                     const float* mean, const float* rstd, const float* gamma, int present_mask, float* df_out, float* dgamma,
                     float* dbeta, float* ws, int B, int D, int M, void* stream);
+
+/* ---- slab LayerNorm: the SLIViT head's patch embedding on the spatio-temporal token stream (csrc/slabnorm.hip) ----
+ * OCTCube/models_vit_st_flash_attn_slivit.py:245-257 hands x[:, 1:] viewed [N, T, L, C] and transposed to [N, T, C, L] to
+ * models_slivit_head.py:37-38, whose Rearrange 'b c (h p1) (w p2) -> b (c h w) (p1 p2)' (p1 = C, p2 = L) flattens every [C, L] slice into
+ * one row for vit-pytorch's to_patch_embedding: LayerNorm(C L) -> Linear(C L, dim) -> LayerNorm(dim).  These two entry points are the
+ * first LayerNorm and its backward, off the token stream as it lies in memory.
+ *   x       f32 [N][n_prefix + T L][C], contiguous: n_prefix leading tokens per volume (the cls token) that take no part
+ *   row r = n T + t is the contiguous slab S_r = x[n][n_prefix + t L .. n_prefix + (t + 1) L)[0..C) read transposed: element
+ *           k = c L + l of the row is S_r[l][c];  K = C L
+ *   mean, rstd   f32 [N T]: over the K elements of the slab, biased variance, rstd = 1 / sqrt(var + eps); the variance is the sum of
+ *           squared deviations from the mean (chunks of 16384 elements combined pairwise in double), so it survives a common offset
+ *   a_lp    [N T][K] in the library's 16-bit operand type (octmae_lp_dtype), row-major: a_lp[r][c L + l] =
+ *           lp(fmaf((S_r[l][c] - mean_r) * rstd_r, gamma[c L + l], beta[c L + l])) -- the GEMM's operand as it is
+ *   gamma, beta  f32 [K] in the order of k
+ * octmae_slab_norm_bwd: da_lp [N T][K] in the 16-bit operand type (what the dgrad GEMM writes); with g_k = da[r][k] gamma[k] and
+ *   xh_k = (S_r[l][c] - mean_r) rstd_r:  dx's slab element [l][c] = rstd_r (g_k - mean_k(g) - xh_k mean_k(g xh)); dx f32 of x's shape,
+ *   written densely: the n_prefix leading token rows of every volume are zeros.  dgamma[k] += sum_r da[r][k] xh_k and
+ *   dbeta[k] += sum_r da[r][k] (f32 [K], ACCUMULATED) when the pointer is not NULL; nothing is computed for a NULL one.
+ * No float atomics: every sum runs in a fixed order (per-tile and per-row-group partials in ws, folded in ascending order), two runs
+ * are bit-equal, and dx is bit-identical with and without dgamma / dbeta.
+ *   ws      at least octmae_slabnorm_ws_floats(N, T, L, C) floats, for either call; caller-owned, needs no initialisation
+ * Alignment: x, gamma, beta, a_lp, da_lp, dx and ws 16-byte aligned; mean, rstd, dgamma, dbeta are accessed word by word.
+ * -1, before any launch: C % 8 != 0 or C < 8, L < 1, T < 1, N < 1, n_prefix < 0, eps < 0, K above 2^30, N T above 2^24, a NULL pointer
+ * where one is needed, a pointer that is not aligned as above (octmae_slabnorm_ws_floats returns -1 for such a shape). */
+int octmae_slabnorm_ws_floats(int N, int T, int L, int C);
+int octmae_slab_norm_fwd(const float* x, const float* gamma, const float* beta, void* a_lp, float* mean, float* rstd, float* ws, int N,
+                         int T, int L, int C, int n_prefix, float eps, void* stream);
+int octmae_slab_norm_bwd(const void* da_lp, const float* x, const float* mean, const float* rstd, const float* gamma, float* dx,
+                         float* dgamma, float* dbeta, float* ws, int N, int T, int L, int C, int n_prefix, void* stream);
 
 /* ---- ConvNeXt layer: depthwise 7x7 convolution and layer scale (csrc/convnext.hip) -------------------------
  * What HF's ConvNextLayer (transformers/models/convnext/modeling_convnext.py, reached from OCTCube/model_slivit_baseline.py:72-85) gets

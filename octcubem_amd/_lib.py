@@ -47,6 +47,9 @@ SIGNATURES = {
     "octmae_join_ws_floats": [_i, _i, _i],
     "octmae_join_fwd": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "octmae_join_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "octmae_slabnorm_ws_floats": [_i, _i, _i, _i],
+    "octmae_slab_norm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
+    "octmae_slab_norm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "octmae_dwconv7_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "octmae_dwconv7_bwd_input": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "octmae_dwconv7_bwd_weight_ws_floats": [_i, _i, _i, _i],

@@ -346,10 +346,18 @@ class SLIViT(_ArenaModel):
         a = get_arena(self)
         Bn, P = feat.shape[0], self.num_patches
         x = feat.reshape(Bn, P, self.patch_height * self.patch_width)
-        ln1, proj, ln2 = self.to_patch_embedding[1], self.to_patch_embedding[2], self.to_patch_embedding[3]
+        ln1, proj = self.to_patch_embedding[1], self.to_patch_embedding[2]
         x = F.layer_norm(x, ln1.normalized_shape, _gp(ln1.weight), _gp(ln1.bias), ln1.eps)
         x = ops.LinearFn.apply(x, a.lp_view(proj.weight), a.f32_view(proj.bias), lambda: a.grad_view(proj.weight),
                                lambda: a.grad_view(proj.bias), True, proj.weight, proj.bias)
+        return self.forward_embedded(x)
+
+    def forward_embedded(self, x: torch.Tensor) -> torch.Tensor:
+        """The head from the patch projection's output on, fp32 [B, P, vit_dim] -> logits [B, num_classes]: what forward_head ends in,
+        and what models_slivit_head.SLIViT runs behind its own patch embedding."""
+        a = get_arena(self)
+        Bn, P = x.shape[0], self.num_patches
+        ln2 = self.to_patch_embedding[3]
         x = F.layer_norm(x, ln2.normalized_shape, _gp(ln2.weight), _gp(ln2.bias), ln2.eps)
         x = torch.cat((_gp(self.cls_token).expand(Bn, -1, -1), x), dim=1) + _gp(self.pos_embedding)[:, :P + 1]
         x = x.contiguous()

@@ -720,6 +720,75 @@ def join_bwd(dy: torch.Tensor, dn_extra: Optional[torch.Tensor], feats, inv_norm
     return df
 
 
+# ------------------------------------------------------------------------------------------------
+# slab LayerNorm (csrc/slabnorm.hip): the SLIViT head's first LayerNorm off the spatio-temporal token stream
+# ------------------------------------------------------------------------------------------------
+def _slab_check(name, x: torch.Tensor, T: int, L: int, n_prefix: int, **vectors):
+    """The refusals of csrc/slabnorm.hip restated on the host, so that a bad call raises ValueError before anything is allocated."""
+    _chk(x, F32, f"{name}: token stream")
+    if x.dim() != 3:
+        raise ValueError(f"{name}: expected the token stream [N, n_prefix + T * L, C], got {tuple(x.shape)}")
+    N, tokens, C = x.shape
+    if T < 1 or L < 1 or n_prefix < 0 or N < 1 or tokens != n_prefix + T * L:
+        raise ValueError(f"{name}: {tokens} tokens are not n_prefix = {n_prefix} + T = {T} slices of L = {L}")
+    if C % 8 != 0 or C < 8:
+        raise ValueError(f"{name}: C = {C} is not a multiple of 8")
+    K = C * L
+    for nm, v in vectors.items():
+        if v is None:
+            continue
+        if _chk(v, F32, f"{name}: {nm}").numel() != K:
+            raise ValueError(f"{name}: {nm} needs C * L = {K} elements, got {v.numel()}")
+    for nm, v in dict(x=x, **vectors).items():
+        if v is not None and v.data_ptr() % 16:
+            raise ValueError(f"{name}: {nm} starts at an address that is not 16-byte aligned: the kernel moves it in 16-byte pieces")
+    return N, C, K
+
+
+def _slab_ws(N: int, T: int, L: int, C: int, dev) -> torch.Tensor:
+    n = load().octmae_slabnorm_ws_floats(N, T, L, C)
+    if n < 0:
+        raise ValueError(f"slab_norm: N = {N}, T = {T}, L = {L}, C = {C} is outside the kernel's domain (include/octmae.h)")
+    return torch.empty((max(n, 4),), dtype=F32, device=dev)
+
+
+def slab_norm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, T: int, L: int, n_prefix: int):
+    """x f32 [N, n_prefix + T * L, C] -> A (16-bit operand type) [N * T, C * L], mean, rstd f32 [N * T]: row n * T + t of A is
+    LayerNorm(C * L) of slice t's L tokens transposed to [C, L] and flattened (element c * L + l), gamma / beta f32 [C * L] in that
+    order -- models_slivit_head.py:37-38 in front of vit-pytorch's to_patch_embedding[1], without a transposed copy of the stream."""
+    N, C, K = _slab_check("slab_norm_fwd", x, T, L, n_prefix, gamma=gamma, beta=beta)
+    rows = N * T
+    A = torch.empty((rows, K), dtype=BF16, device=x.device)
+    mean = torch.empty((rows,), dtype=F32, device=x.device)
+    rstd = torch.empty((rows,), dtype=F32, device=x.device)
+    ws = _slab_ws(N, T, L, C, x.device)
+    # algorithmic HBM bytes: the slab read once (fp32), the row written (16 bits), gamma and beta once, the statistics
+    _launch(f"slab_norm_fwd_k{K}", 0.0, 6.0 * rows * K + 8.0 * K + 8.0 * rows,
+            lambda: call("octmae_slab_norm_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), A.data_ptr(), mean.data_ptr(),
+                         rstd.data_ptr(), ws.data_ptr(), N, T, L, C, n_prefix, float(eps), _stream()))
+    return A, mean, rstd
+
+
+def slab_norm_bwd(dA: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, T: int, L: int,
+                  n_prefix: int, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> dx f32 of x's shape (the n_prefix leading token rows of every volume are zeros) for dA (16-bit) [N * T, C * L]; ``dgamma`` /
+    ``dbeta`` (f32 [C * L]) are accumulated into when given, in a fixed order."""
+    N, C, K = _slab_check("slab_norm_bwd", x, T, L, n_prefix, gamma=gamma, dgamma=dgamma, dbeta=dbeta)
+    rows = N * T
+    _chk(dA, BF16, "slab_norm_bwd: dA")
+    if tuple(dA.shape) != (rows, K) or dA.data_ptr() % 16:
+        raise ValueError(f"slab_norm_bwd: dA must be a 16-byte aligned [{rows}, {K}] matrix, got {tuple(dA.shape)}")
+    if _chk(mean, F32, "slab_norm_bwd: mean").numel() != rows or _chk(rstd, F32, "slab_norm_bwd: rstd").numel() != rows:
+        raise ValueError(f"slab_norm_bwd: {mean.numel()} / {rstd.numel()} row statistics for {rows} rows")
+    dx = torch.empty_like(x)
+    ws = _slab_ws(N, T, L, C, x.device)
+    pgrads = (dgamma is not None) + (dbeta is not None)
+    _launch(f"slab_norm_bwd_k{K}", 0.0, 10.0 * rows * K + 4.0 * K * (1 + 2 * pgrads) + 4.0 * N * n_prefix * C + 8.0 * rows,
+            lambda: call("octmae_slab_norm_bwd", dA.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+                         dx.data_ptr(), _p(dgamma), _p(dbeta), ws.data_ptr(), N, T, L, C, n_prefix, _stream()))
+    return dx
+
+
 _VOL_DTYPES = {torch.uint8: 0, torch.float32: 1}
 
 
@@ -1545,6 +1614,46 @@ class JoinFn(torch.autograd.Function):
         if wg:
             notify_grad_ready((gamma, beta))
         return (None, None, None, None) + tuple(df[k] if (ctx.mask >> k) & 1 and ctx.needs_input_grad[4 + k] else None for k in range(M))
+
+
+class SliceEmbedFn(torch.autograd.Function):
+    """y fp32 [N, T, dim] = Linear(LayerNorm(C * L)(slice t of x transposed to [C, L] and flattened)) for the token stream
+    x fp32 [N, n_prefix + T * L, C]: the Rearrange, LayerNorm and Linear of the SLIViT head's to_patch_embedding (models_slivit_head.py:37-38
+    over vit-pytorch) fed by models_vit_st_flash_attn_slivit.py:245-257.  slab_norm_fwd writes the GEMM's 16-bit operand straight from the
+    stream; the backward hands the dgrad GEMM's output to slab_norm_bwd.  No fp32 transposed copy exists either way; saved: the
+    operand, the row statistics and a reference to x.  ``gamma`` / ``beta`` are the LayerNorm's parameters (their gradients are
+    accumulated into their buffers as LayerNormFn does), ``params`` = (weight, bias) of the Linear with ``gw`` / ``gb`` their buffers."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, T, L, n_prefix, w_lp, b32, gw, gb, *params):
+        x = x if x.is_contiguous() else x.contiguous()
+        A, mean, rstd = slab_norm_fwd(x, gamma, beta, eps, T, L, n_prefix)
+        y = linear_fwd(A, w_lp, b32, "f32")
+        ctx.save_for_backward(x, A, mean, rstd, gamma, beta, w_lp)
+        ctx.meta = (int(T), int(L), int(n_prefix))
+        ctx.gw, ctx.gb, ctx.params = gw, gb, params
+        return y.view(x.shape[0], T, w_lp.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, A, mean, rstd, gamma, beta, w_lp = ctx.saved_tensors
+        T, L, n_prefix = ctx.meta
+        wg = _weight_grads
+        want_w = wg and any(ctx.needs_input_grad[11:])
+        want_g, want_b = wg and ctx.needs_input_grad[1], wg and ctx.needs_input_grad[2]
+        nothing = (None,) * (11 + len(ctx.params))
+        if not (ctx.needs_input_grad[0] or want_w or want_g or want_b):
+            return nothing
+        dyb = _as2d_bf16(dy, w_lp.shape[0])
+        if want_w:
+            linear_wgrad_accum(dyb, A, ctx.gw(), ctx.gb())
+        dx = None
+        if ctx.needs_input_grad[0] or want_g or want_b:
+            dx = slab_norm_bwd(linear_dgrad(dyb, w_lp), x, mean, rstd, gamma, T, L, n_prefix,
+                               grad_buf(gamma) if want_g else None, grad_buf(beta) if want_b else None)
+        if wg:
+            notify_grad_ready(((gamma, beta) if want_g or want_b else ()) + (tuple(ctx.params) if want_w else ()))
+        return (dx if ctx.needs_input_grad[0] else None,) + nothing[1:]
 
 
 class LinearFn(torch.autograd.Function):
