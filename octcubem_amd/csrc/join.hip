@@ -15,7 +15,7 @@
 // of max |f| over the slice: a power of two, so f * s is exact and its largest element lies in [1, 2) -- the sum lies in [1, 4 D).
 // n = (f * s) * (1 / sqrt(sum)) never forms the norm itself; the norm sqrt(sum) / s is formed once, only to compare it with 1e-12
 // (below it: n = f * 1e12, what F.normalize's clamp gives).  inv_norm = s / sqrt(sum) (or 1e12) is what the backward multiplies with.
-#include "common.hpp"
+#include "rowwave.hpp"
 #include "../../include/octmae.h"
 
 namespace octmae {
@@ -52,10 +52,10 @@ __global__ __launch_bounds__(256) void join_fwd_kernel(JoinSrc src, unsigned mas
     for (int k = 0; k < M; ++k) {
       const bool present = (mask >> k) & 1u;
 #pragma unroll
-      for (int c = 0; c < NC; ++c) {
+      for (int c = 0; c < NC; ++c) {      // written out: a slot past the row, or of an absent modality, holds zeros
         const int ci = lane + 64 * c;
         v[k][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (present && ci < nchunk) v[k][c] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src.p[k] + (size_t)row * D + 4 * ci));
+        if (present && ci < nchunk) v[k][c] = ROW_LD(f32x4, src.p[k] + (size_t)row * D + 4 * ci);
       }
     }
     float s1 = 0.f;
@@ -91,27 +91,12 @@ __global__ __launch_bounds__(256) void join_fwd_kernel(JoinSrc src, unsigned mas
           }
       }
       if (lane == 0) inv_norm[(size_t)row * M + k] = inv;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int ci = lane + 64 * c;
-        if (ci < nchunk) __builtin_nontemporal_store(v[k][c], reinterpret_cast<f32x4*>(n_out + ((size_t)k * B + row) * D + 4 * ci));
-      }
+      ROW_CHUNKS(c, ci) __builtin_nontemporal_store(v[k][c], reinterpret_cast<f32x4*>(n_out + ((size_t)k * B + row) * D + 4 * ci));
     }
     const float mu = wave_sum(s1) * invMD;
     float q = 0.f;
 #pragma unroll
-    for (int k = 0; k < M; ++k)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int ci = lane + 64 * c;
-        if (ci < nchunk) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float d = v[k][c][e] - mu;
-            q = fmaf(d, d, q);
-          }
-        }
-      }
+    for (int k = 0; k < M; ++k) ROW_CHUNKS(c, ci) ROW_SQDEV4(q, v[k][c], mu);
     const float var = wave_sum(q) * invMD;
     const float rs = rsqrtf(var + eps);
     if (lane == 0) {
@@ -120,21 +105,12 @@ __global__ __launch_bounds__(256) void join_fwd_kernel(JoinSrc src, unsigned mas
     }
     bf16_t* yr = y + (size_t)row * M * D;
 #pragma unroll
-    for (int k = 0; k < M; ++k)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int ci = lane + 64 * c;
-        if (ci < nchunk) {
-          const int col = k * D + 4 * ci;
-          const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + col);
-          const f32x4 b = *reinterpret_cast<const f32x4*>(beta + col);
-          float o[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = fmaf((v[k][c][e] - mu) * rs, g[e], b[e]);
-          u32x2 w = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
-          __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(yr + col));
-        }
-      }
+    for (int k = 0; k < M; ++k) ROW_CHUNKS(c, ci) {
+      const int col = k * D + 4 * ci;
+      const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + col);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(beta + col);
+      LN_AFFINE_STORE(v[k][c], mu, rs, g, b, yr + col);
+    }
   }
 }
 
@@ -146,7 +122,7 @@ __global__ __launch_bounds__(256) void join_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ inv_norm, const float* __restrict__ mean,
                                                        const float* __restrict__ rstd, const float* __restrict__ gamma, unsigned mask,
                                                        float* __restrict__ df, float* __restrict__ partial, bool want_w, int B, int D) {
-  __shared__ float red[2][4][64 * 4 + 4];
+  __shared__ RowRed red[2];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int wave = blockIdx.x * 4 + w;
   const int nwaves = gridDim.x * 4;
@@ -169,70 +145,57 @@ __global__ __launch_bounds__(256) void join_bwd_kernel(const float* __restrict__
       const bool present = (mask >> k) & 1u;
       inv[k] = present ? inv_norm[(size_t)row * M + k] : 0.f;
 #pragma unroll
-      for (int c = 0; c < NC; ++c) {
+      for (int c = 0; c < NC; ++c) {      // written out: as in join_fwd_kernel
         const int ci = lane + 64 * c;
         n[k][c] = f32x4{0.f, 0.f, 0.f, 0.f};
         d[k][c] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (ci < nchunk) {
-          if (present) n[k][c] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src.p[k] + (size_t)row * D + 4 * ci));
-          d[k][c] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(dy + (size_t)row * M * D + k * D + 4 * ci));
+          if (present) n[k][c] = ROW_LD(f32x4, src.p[k] + (size_t)row * D + 4 * ci);
+          d[k][c] = ROW_LD(f32x4, dy + (size_t)row * M * D + k * D + 4 * ci);
         }
       }
     }
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int k = 0; k < M; ++k)
+    for (int k = 0; k < M; ++k) ROW_CHUNKS(c, ci) {
+      const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + k * D + 4 * ci);
 #pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int ci = lane + 64 * c;
-        if (ci < nchunk) {
-          const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + k * D + 4 * ci);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            n[k][c][e] *= inv[k];
-            const float xhat = (n[k][c][e] - mu) * rs;
-            if (want_w) {
-              ag[k][c][e] = fmaf(d[k][c][e], xhat, ag[k][c][e]);
-              ab[k][c][e] += d[k][c][e];
-            }
-            const float gy = d[k][c][e] * g[e];
-            d[k][c][e] = gy;
-            s1 += gy;
-            s2 = fmaf(gy, xhat, s2);
-          }
+      for (int e = 0; e < 4; ++e) {
+        n[k][c][e] *= inv[k];
+        const float xhat = (n[k][c][e] - mu) * rs;
+        if (want_w) {
+          ag[k][c][e] = fmaf(d[k][c][e], xhat, ag[k][c][e]);
+          ab[k][c][e] += d[k][c][e];
         }
+        const float gy = d[k][c][e] * g[e];
+        d[k][c][e] = gy;
+        s1 += gy;
+        s2 = fmaf(gy, xhat, s2);
       }
+    }
     const float m1 = wave_sum(s1) * invMD, m2 = wave_sum(s2) * invMD;
 #pragma unroll
     for (int k = 0; k < M; ++k) {
       if (!((mask >> k) & 1u)) continue;      // wave-uniform
       float dot = 0.f;
+      ROW_CHUNKS(c, ci) {
+        f32x4 x = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (dn_extra != nullptr) x = ROW_LD(f32x4, dn_extra + ((size_t)k * B + row) * D + 4 * ci);
 #pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int ci = lane + 64 * c;
-        if (ci < nchunk) {
-          f32x4 x = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (dn_extra != nullptr) x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(dn_extra + ((size_t)k * B + row) * D + 4 * ci));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float xhat = (n[k][c][e] - mu) * rs;
-            const float dn = rs * (d[k][c][e] - m1 - xhat * m2) + x[e];
-            d[k][c][e] = dn;
-            dot = fmaf(n[k][c][e], dn, dot);
-          }
+        for (int e = 0; e < 4; ++e) {
+          const float xhat = (n[k][c][e] - mu) * rs;
+          const float dn = LN_DX(rs, d[k][c][e], m1, xhat, m2) + x[e];
+          d[k][c][e] = dn;
+          dot = fmaf(n[k][c][e], dn, dot);
         }
       }
       dot = wave_sum(dot);
       if (inv[k] >= JOIN_INV_EPS) dot = 0.f;      // below the clamp: d / 1e-12, no projection term
+      ROW_CHUNKS(c, ci) {
+        f32x4 o;
 #pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int ci = lane + 64 * c;
-        if (ci < nchunk) {
-          f32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = inv[k] * (d[k][c][e] - n[k][c][e] * dot);
-          __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(df + ((size_t)k * B + row) * D + 4 * ci));
-        }
+        for (int e = 0; e < 4; ++e) o[e] = inv[k] * (d[k][c][e] - n[k][c][e] * dot);
+        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(df + ((size_t)k * B + row) * D + 4 * ci));
       }
     }
   }
@@ -241,22 +204,9 @@ __global__ __launch_bounds__(256) void join_bwd_kernel(const float* __restrict__
 #pragma unroll
   for (int k = 0; k < M; ++k)
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
+    for (int c = 0; c < NC; ++c) {      // written out: every slot takes part in the barriers of ROW_FOLD4
       const int ci = lane + 64 * c;
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red[0][w][lane * 4 + e] = ag[k][c][e];
-        red[1][w][lane * 4 + e] = ab[k][c][e];
-      }
-      __syncthreads();
-      if (w < 2 && ci < nchunk) {
-        f32x4 t;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          t[e] = (red[w][0][lane * 4 + e] + red[w][1][lane * 4 + e]) + (red[w][2][lane * 4 + e] + red[w][3][lane * 4 + e]);
-        *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + w) * M * D + k * D + 4 * ci) = t;
-      }
+      ROW_FOLD4(2, ci, partial + ((size_t)blockIdx.x * 2 + w) * M * D + k * D + 4 * ci, ag[k][c][e], ab[k][c][e]);
     }
 }
 
@@ -309,7 +259,7 @@ extern "C" int octmae_join_fwd(const float* f0, const float* f1, const float* f2
   for (int k = 0; k < M; ++k) OCTMAE_CHECK_ARG(!((present_mask >> k) & 1) || (src.p[k] != nullptr && join_aligned(src.p[k], 16)));
   OCTMAE_CHECK_ARG(join_aligned(gamma, 16) && join_aligned(beta, 16) && join_aligned(n_out, 16) && join_aligned(y_lp, 8));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nc = (D / 4 + 63) / 64;
+  const int nc = row_nc(D);
   bf16_t* y = reinterpret_cast<bf16_t*>(y_lp);
   const unsigned mask = (unsigned)present_mask;
   dim3 grid(join_grid(B)), blk(256);
@@ -339,7 +289,7 @@ extern "C" int octmae_join_bwd(const float* dy, const float* dn_extra, const flo
   OCTMAE_CHECK_ARG(join_aligned(dy, 16) && join_aligned(dn_extra, 16) && join_aligned(gamma, 16) && join_aligned(df_out, 16) &&
                    join_aligned(ws, 16));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nc = (D / 4 + 63) / 64;
+  const int nc = row_nc(D);
   const unsigned mask = (unsigned)present_mask;
   const int blocks = join_grid(B);
   dim3 grid(blocks), blk(256);

@@ -8,21 +8,13 @@
 //   accumulated per lane across the rows a wave walks, reduced over the block in LDS, written as per-block
 //   partials to a caller-provided workspace and folded by a second small kernel (deterministic, no atomics).
 #include <cstdlib>
-#include "common.hpp"
+#ifdef LN_PLAIN_LOADS      // A/B builds: ordinary loads of the row operands, in this file only
+#define ROW_PLAIN_LOADS
+#endif
+#include "rowwave.hpp"
 #include "../../include/octmae.h"
 
-// The row operands (x, dy, the residual gradient) are read exactly once: their loads are non-temporal, like the stores of the outputs.
-// Measured same box (profiles/r04_layernorm_nt_loads.txt): forward 5.85 -> 6.10 TB/s, backward 5.91 -> 6.12 at D = 1024 inside the
-// training step, +0.17 % on the step.  -DLN_PLAIN_LOADS: the ordinary loads (A/B builds).
-#ifndef LN_PLAIN_LOADS
-#define LN_LD(T, p) __builtin_nontemporal_load(reinterpret_cast<const T*>(p))
-#else
-#define LN_LD(T, p) (*reinterpret_cast<const T*>(p))
-#endif
-
 namespace octmae {
-
-constexpr int LN_MAXC = 8;  // float4 chunks per lane -> D <= 2048
 
 template <int NC>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -35,23 +27,15 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   const int nchunk = D >> 2;
   const float invD = 1.0f / (float)D;
   f32x4 g[NC], b[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int ci = lane + 64 * c;
-    if (ci < nchunk) {
-      g[c] = *reinterpret_cast<const f32x4*>(gamma + 4 * ci);
-      b[c] = *reinterpret_cast<const f32x4*>(beta + 4 * ci);
-    }
+  ROW_CHUNKS(c, ci) {
+    g[c] = *reinterpret_cast<const f32x4*>(gamma + 4 * ci);
+    b[c] = *reinterpret_cast<const f32x4*>(beta + 4 * ci);
   }
   // the next row of the wave is requested before the current one is reduced (as in the backward kernel)
   f32x4 vn[NC];
   auto issue = [&](int row) {
     const float* xr = x + (size_t)row * D;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) vn[c] = LN_LD(f32x4, xr + 4 * ci);
-    }
+    ROW_CHUNKS(c, ci) vn[c] = ROW_LD(f32x4, xr + 4 * ci);
   };
   if (wave < M) issue(wave);
   for (int row = wave; row < M; row += nwaves) {
@@ -60,24 +44,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 #pragma unroll
     for (int c = 0; c < NC; ++c) v[c] = vn[c];
     if (row + nwaves < M) issue(row + nwaves);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) s += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
-    }
+    ROW_CHUNKS(c, ci) s += ROW_SUM4(v[c]);
     const float mu = wave_sum(s) * invD;
     float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = v[c][e] - mu;
-          q = fmaf(d, d, q);
-        }
-      }
-    }
+    ROW_CHUNKS(c, ci) ROW_SQDEV4(q, v[c], mu);
     const float var = wave_sum(q) * invD;
     const float rs = rsqrtf(var + eps);
     if (lane == 0) {
@@ -85,23 +55,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
       rstd[row] = rs;
     }
     bf16_t* yr = y + (size_t)row * D;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-        float o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = fmaf((v[c][e] - mu) * rs, g[c][e], b[c][e]);
-        u32x2 w = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
-        __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(yr + 4 * ci));
-      }
-    }
+    ROW_CHUNKS(c, ci) LN_AFFINE_STORE(v[c], mu, rs, g[c], b[c], yr + 4 * ci);
   }
 }
 
 // y = the LayerNorm output rebuilt from the SAVED row statistics (activation recomputation: ops.BlockFn at level "light" drops y1 / y2
-// and calls this in its backward).  The expression and the packing are ln_fwd_kernel's, so the result is that kernel's y bit for bit;
-// without the two reductions a row costs one pass: 4 (x) read + 2 (y) write bytes per element, the row pipelined the same way.
+// and calls this in its backward) through the LN_AFFINE_STORE that ln_fwd_kernel uses: that kernel's y bit for bit.  Without the two reductions
+// a row costs one pass: 4 (x) read + 2 (y) write bytes per element, the row pipelined the same way.
 template <int NC>
 __global__ __launch_bounds__(256) void ln_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                        const float* __restrict__ rstd, const float* __restrict__ gamma,
@@ -111,13 +71,9 @@ __global__ __launch_bounds__(256) void ln_apply_kernel(const float* __restrict__
   const int nwaves = gridDim.x * 4;
   const int nchunk = D >> 2;
   f32x4 g[NC], b[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int ci = lane + 64 * c;
-    if (ci < nchunk) {
-      g[c] = *reinterpret_cast<const f32x4*>(gamma + 4 * ci);
-      b[c] = *reinterpret_cast<const f32x4*>(beta + 4 * ci);
-    }
+  ROW_CHUNKS(c, ci) {
+    g[c] = *reinterpret_cast<const f32x4*>(gamma + 4 * ci);
+    b[c] = *reinterpret_cast<const f32x4*>(beta + 4 * ci);
   }
   f32x4 vn[NC];
   float mu_n = 0.f, rs_n = 0.f;
@@ -125,11 +81,7 @@ __global__ __launch_bounds__(256) void ln_apply_kernel(const float* __restrict__
     mu_n = mean[row];
     rs_n = rstd[row];
     const float* xr = x + (size_t)row * D;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) vn[c] = LN_LD(f32x4, xr + 4 * ci);
-    }
+    ROW_CHUNKS(c, ci) vn[c] = ROW_LD(f32x4, xr + 4 * ci);
   };
   if (wave < M) issue(wave);
   for (int row = wave; row < M; row += nwaves) {
@@ -139,17 +91,7 @@ __global__ __launch_bounds__(256) void ln_apply_kernel(const float* __restrict__
     for (int c = 0; c < NC; ++c) v[c] = vn[c];
     if (row + nwaves < M) issue(row + nwaves);
     bf16_t* yr = y + (size_t)row * D;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-        float o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = fmaf((v[c][e] - mu) * rs, g[c][e], b[c][e]);
-        u32x2 w = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
-        __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(yr + 4 * ci));
-      }
-    }
+    ROW_CHUNKS(c, ci) LN_AFFINE_STORE(v[c], mu, rs, g[c], b[c], yr + 4 * ci);
   }
 }
 
@@ -160,7 +102,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
                                                      const float* __restrict__ gamma, const float* __restrict__ dres,
                                                      float* __restrict__ dx, bf16_t* __restrict__ dxb,
                                                      float* __restrict__ partial, bool want_dxsum, int M, int D) {
-  __shared__ float red[3][4][64 * 4 + 4];
+  __shared__ RowRed red[3];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int wave = blockIdx.x * 4 + w;
   const int nwaves = gridDim.x * 4;
@@ -168,7 +110,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
   const float invD = 1.0f / (float)D;
   f32x4 g[NC], ag[NC], ab[NC], as[NC];
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
+  for (int c = 0; c < NC; ++c) {      // written out: the accumulators of every slot are zeroed, inside the row or not
     const int ci = lane + 64 * c;
     if (ci < nchunk) g[c] = *reinterpret_cast<const f32x4*>(gamma + 4 * ci);
 #pragma unroll
@@ -184,14 +126,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
   auto issue = [&](int row) {
     mu_n = mean[row];
     rs_n = rstd[row];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-        xn[c] = LN_LD(f32x4, x + (size_t)row * D + 4 * ci);
-        dn[c] = LN_LD(u32x2, dy + (size_t)row * D + 4 * ci);
-        if (dres != nullptr) rn[c] = LN_LD(f32x4, dres + (size_t)row * D + 4 * ci);
-      }
+    ROW_CHUNKS(c, ci) {
+      xn[c] = ROW_LD(f32x4, x + (size_t)row * D + 4 * ci);
+      dn[c] = ROW_LD(u32x2, dy + (size_t)row * D + 4 * ci);
+      if (dres != nullptr) rn[c] = ROW_LD(f32x4, dres + (size_t)row * D + 4 * ci);
     }
   };
   if (wave < M) issue(wave);
@@ -203,45 +141,37 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     for (int c = 0; c < NC; ++c) { xh[c] = xn[c]; dw[c] = dn[c]; rv[c] = rn[c]; }
     if (row + nwaves < M) issue(row + nwaves);
     float s1 = 0.f, s2 = 0.f;
+    ROW_CHUNKS(c, ci) {
+      const float d[4] = {bflo(dw[c][0]), bfhi(dw[c][0]), bflo(dw[c][1]), bfhi(dw[c][1])};
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-        const float d[4] = {bflo(dw[c][0]), bfhi(dw[c][0]), bflo(dw[c][1]), bfhi(dw[c][1])};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xhat = (xh[c][e] - mu) * rs;
-          const float gy = d[e] * g[c][e];
-          xh[c][e] = xhat;
-          s1 += gy;
-          s2 = fmaf(gy, xhat, s2);
-          ag[c][e] = fmaf(d[e], xhat, ag[c][e]);
-          ab[c][e] += d[e];
-        }
+      for (int e = 0; e < 4; ++e) {
+        const float xhat = (xh[c][e] - mu) * rs;
+        const float gy = d[e] * g[c][e];
+        xh[c][e] = xhat;
+        s1 += gy;
+        s2 = fmaf(gy, xhat, s2);
+        ag[c][e] = fmaf(d[e], xhat, ag[c][e]);
+        ab[c][e] += d[e];
       }
     }
     const float m1 = wave_sum(s1) * invD, m2 = wave_sum(s2) * invD;
+    ROW_CHUNKS(c, ci) {
+      const float d[4] = {bflo(dw[c][0]), bfhi(dw[c][0]), bflo(dw[c][1]), bfhi(dw[c][1])};
+      f32x4 o;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-        const float d[4] = {bflo(dw[c][0]), bfhi(dw[c][0]), bflo(dw[c][1]), bfhi(dw[c][1])};
-        f32x4 o;
+      for (int e = 0; e < 4; ++e) o[e] = LN_DX(rs, d[e] * g[c][e], m1, xh[c][e], m2);
+      if (dres != nullptr) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = rs * (d[e] * g[c][e] - m1 - xh[c][e] * m2);
-        if (dres != nullptr) {
+        for (int e = 0; e < 4; ++e) o[e] += rv[c][e];
+      }
+      __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dx + (size_t)row * D + 4 * ci));
+      if (dxb != nullptr) {
+        u32x2 wv = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
+        __builtin_nontemporal_store(wv, reinterpret_cast<u32x2*>(dxb + (size_t)row * D + 4 * ci));
+      }
+      if (want_dxsum) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] += rv[c][e];
-        }
-        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dx + (size_t)row * D + 4 * ci));
-        if (dxb != nullptr) {
-          u32x2 wv = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
-          __builtin_nontemporal_store(wv, reinterpret_cast<u32x2*>(dxb + (size_t)row * D + 4 * ci));
-        }
-        if (want_dxsum) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) as[c][e] += o[e];
-        }
+        for (int e = 0; e < 4; ++e) as[c][e] += o[e];
       }
     }
   }
@@ -249,23 +179,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
   // sums to the workspace (a second tiny kernel folds them): 1024 workgroups adding atomically into the same 3 x D
   // words ran at the contended-atomic rate and took 3/4 of this kernel's time.
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
+  for (int c = 0; c < NC; ++c) {      // written out: every slot takes part in the barriers of ROW_FOLD4
     const int ci = lane + 64 * c;
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      red[0][w][lane * 4 + e] = ag[c][e];
-      red[1][w][lane * 4 + e] = ab[c][e];
-      red[2][w][lane * 4 + e] = as[c][e];
-    }
-    __syncthreads();
-    if (w < 3 && ci < nchunk) {
-      f32x4 t;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        t[e] = (red[w][0][lane * 4 + e] + red[w][1][lane * 4 + e]) + (red[w][2][lane * 4 + e] + red[w][3][lane * 4 + e]);
-      *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 3 + w) * D + 4 * ci) = t;
-    }
+    ROW_FOLD4(3, ci, partial + ((size_t)blockIdx.x * 3 + w) * D + 4 * ci, ag[c][e], ab[c][e], as[c][e]);
   }
 }
 
@@ -325,17 +241,12 @@ using namespace octmae;
 extern "C" int octmae_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y_bf16, float* mean,
                                     float* rstd, int M, int D, float eps, void* stream) {
   OCTMAE_CHECK_ARG(x && gamma && beta && y_bf16 && mean && rstd);
-  OCTMAE_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 256 * LN_MAXC);
+  OCTMAE_CHECK_ARG(row_shape_ok(M, D));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nc = (D / 4 + 63) / 64;
+  const int nc = row_nc(D);
   bf16_t* y = reinterpret_cast<bf16_t*>(y_bf16);
   dim3 grid(ln_grid(M)), blk(256);
-  switch (nc) {
-    case 1: hipLaunchKernelGGL(ln_fwd_kernel<1>, grid, blk, 0, st, x, gamma, beta, y, mean, rstd, M, D, eps); break;
-    case 2: hipLaunchKernelGGL(ln_fwd_kernel<2>, grid, blk, 0, st, x, gamma, beta, y, mean, rstd, M, D, eps); break;
-    case 3: case 4: hipLaunchKernelGGL(ln_fwd_kernel<4>, grid, blk, 0, st, x, gamma, beta, y, mean, rstd, M, D, eps); break;
-    default: hipLaunchKernelGGL(ln_fwd_kernel<8>, grid, blk, 0, st, x, gamma, beta, y, mean, rstd, M, D, eps); break;
-  }
+  ROW_DISPATCH(ln_fwd_kernel, grid, blk, x, gamma, beta, y, mean, rstd, M, D, eps);
   OCTMAE_LAUNCH_CHECK();
   return 0;
 }
@@ -343,17 +254,12 @@ extern "C" int octmae_layernorm_fwd(const float* x, const float* gamma, const fl
 extern "C" int octmae_ln_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                                void* y_bf16, int M, int D, void* stream) {
   OCTMAE_CHECK_ARG(x && mean && rstd && gamma && beta && y_bf16);
-  OCTMAE_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 256 * LN_MAXC);
+  OCTMAE_CHECK_ARG(row_shape_ok(M, D));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nc = (D / 4 + 63) / 64;
+  const int nc = row_nc(D);
   bf16_t* y = reinterpret_cast<bf16_t*>(y_bf16);
   dim3 grid(ln_grid(M)), blk(256);
-  switch (nc) {
-    case 1: hipLaunchKernelGGL(ln_apply_kernel<1>, grid, blk, 0, st, x, mean, rstd, gamma, beta, y, M, D); break;
-    case 2: hipLaunchKernelGGL(ln_apply_kernel<2>, grid, blk, 0, st, x, mean, rstd, gamma, beta, y, M, D); break;
-    case 3: case 4: hipLaunchKernelGGL(ln_apply_kernel<4>, grid, blk, 0, st, x, mean, rstd, gamma, beta, y, M, D); break;
-    default: hipLaunchKernelGGL(ln_apply_kernel<8>, grid, blk, 0, st, x, mean, rstd, gamma, beta, y, M, D); break;
-  }
+  ROW_DISPATCH(ln_apply_kernel, grid, blk, x, mean, rstd, gamma, beta, y, M, D);
   OCTMAE_LAUNCH_CHECK();
   return 0;
 }
@@ -368,21 +274,16 @@ extern "C" int octmae_layernorm_bwd(const void* dy_bf16, const float* x, const f
                                     const float* gamma, const float* dres, float* dx, void* dx_bf16, float* dgamma,
                                     float* dbeta, float* dxsum, float* partial_ws, int M, int D, void* stream) {
   OCTMAE_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && dx && partial_ws);
-  OCTMAE_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 256 * LN_MAXC);
+  OCTMAE_CHECK_ARG(row_shape_ok(M, D));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nc = (D / 4 + 63) / 64;
+  const int nc = row_nc(D);
   const bf16_t* dy = reinterpret_cast<const bf16_t*>(dy_bf16);
   bf16_t* dxb = reinterpret_cast<bf16_t*>(dx_bf16);
   int blocks = ln_grid(M, true);
   if (blocks > 512) blocks = 512;
   dim3 grid(blocks), blk(256);
   const bool ws = dxsum != nullptr;
-  switch (nc) {
-    case 1: hipLaunchKernelGGL(ln_bwd_kernel<1>, grid, blk, 0, st, dy, x, mean, rstd, gamma, dres, dx, dxb, partial_ws, ws, M, D); break;
-    case 2: hipLaunchKernelGGL(ln_bwd_kernel<2>, grid, blk, 0, st, dy, x, mean, rstd, gamma, dres, dx, dxb, partial_ws, ws, M, D); break;
-    case 3: case 4: hipLaunchKernelGGL(ln_bwd_kernel<4>, grid, blk, 0, st, dy, x, mean, rstd, gamma, dres, dx, dxb, partial_ws, ws, M, D); break;
-    default: hipLaunchKernelGGL(ln_bwd_kernel<8>, grid, blk, 0, st, dy, x, mean, rstd, gamma, dres, dx, dxb, partial_ws, ws, M, D); break;
-  }
+  ROW_DISPATCH(ln_bwd_kernel, grid, blk, dy, x, mean, rstd, gamma, dres, dx, dxb, partial_ws, ws, M, D);
   OCTMAE_LAUNCH_CHECK();
   if (dgamma != nullptr || dbeta != nullptr || dxsum != nullptr) {
     hipLaunchKernelGGL(ln_bwd_finish_kernel, dim3((D + 63) / 64, 3), dim3(1024), 0, st, partial_ws, blocks, D, dgamma, dbeta, dxsum);

@@ -8,14 +8,10 @@
 //   fwd bytes/element of x: 4 read (mean mode; cls mode reads one row per slice)
 //   bwd bytes/element of dx: 4 written [+2 (bf16 copy)]; everything else is O(B*S*D)
 #include <cstdlib>
-#include "common.hpp"
+#include "rowwave.hpp"
 #include "../../include/octmae.h"
 
-#define PL_LD(T, p) __builtin_nontemporal_load(reinterpret_cast<const T*>(p))
-
 namespace octmae {
-
-constexpr int PL_MAXC = 8;  // float4 chunks per lane -> D <= 2048
 
 // Split of a slice's L = T-1 patch tokens over workgroups: ~2 workgroups per CU over all slices, >= 16 rows (4 per wave) each.
 static inline int pool_nsplit(int BS, int T) {
@@ -32,7 +28,7 @@ static inline int pool_nsplit(int BS, int T) {
 template <int NC>
 __global__ __launch_bounds__(256) void pool_colsum_kernel(const float* __restrict__ x, float* __restrict__ partial, int T, int D,
                                                           int rows_per_split) {
-  __shared__ float red[4][64 * 4 + 4];
+  __shared__ RowRed red[1];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int k = blockIdx.x, s = blockIdx.y, nsplit = gridDim.x;
   const int nchunk = D >> 2;
@@ -49,39 +45,18 @@ __global__ __launch_bounds__(256) void pool_colsum_kernel(const float* __restric
   int t = t0 + w;
   for (; t + 4 < t1; t += 8) {
     f32x4 v0[NC], v1[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-        v0[c] = PL_LD(f32x4, xs + (size_t)t * D + 4 * ci);
-        v1[c] = PL_LD(f32x4, xs + (size_t)(t + 4) * D + 4 * ci);
-      }
+    ROW_CHUNKS(c, ci) {
+      v0[c] = ROW_LD(f32x4, xs + (size_t)t * D + 4 * ci);
+      v1[c] = ROW_LD(f32x4, xs + (size_t)(t + 4) * D + 4 * ci);
     }
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-      if (lane + 64 * c < nchunk) { a0[c] += v0[c]; a1[c] += v1[c]; }
+    ROW_CHUNKS(c, ci) { a0[c] += v0[c]; a1[c] += v1[c]; }
   }
-  if (t < t1) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) a0[c] += PL_LD(f32x4, xs + (size_t)t * D + 4 * ci);
-    }
-  }
+  if (t < t1) ROW_CHUNKS(c, ci) a0[c] += ROW_LD(f32x4, xs + (size_t)t * D + 4 * ci);
   float* dst = partial + ((size_t)s * nsplit + k) * D;
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
+  for (int c = 0; c < NC; ++c) {      // written out: every slot takes part in the barriers of ROW_FOLD4
     const int ci = lane + 64 * c;
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) red[w][lane * 4 + e] = a0[c][e] + a1[c][e];
-    __syncthreads();
-    if (w == 0 && ci < nchunk) {
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (red[0][lane * 4 + e] + red[1][lane * 4 + e]) + (red[2][lane * 4 + e] + red[3][lane * 4 + e]);
-      *reinterpret_cast<f32x4*>(dst + 4 * ci) = o;
-    }
+    ROW_FOLD4(1, ci, dst + 4 * ci, a0[c][e] + a1[c][e]);
   }
 }
 
@@ -99,40 +74,22 @@ __global__ __launch_bounds__(256) void pool_stats_kernel(const float* __restrict
   float sum = 0.f;
   if (cls) {
     const float* xr = x + (size_t)s * T * D;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) p[c] = *reinterpret_cast<const f32x4*>(xr + 4 * ci);
-    }
+    ROW_CHUNKS(c, ci) p[c] = *reinterpret_cast<const f32x4*>(xr + 4 * ci);
   } else {
     const float invL = 1.0f / (float)(T - 1);
     const float* src = partial + (size_t)s * nsplit * D;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-        f32x4 a = *reinterpret_cast<const f32x4*>(src + 4 * ci);
-        for (int k = 1; k < nsplit; ++k) a += *reinterpret_cast<const f32x4*>(src + (size_t)k * D + 4 * ci);
-        p[c] = a * invL;
-      }
+    ROW_CHUNKS(c, ci) {
+      f32x4 a = *reinterpret_cast<const f32x4*>(src + 4 * ci);
+      for (int k = 1; k < nsplit; ++k) a += *reinterpret_cast<const f32x4*>(src + (size_t)k * D + 4 * ci);
+      p[c] = a * invL;
     }
   }
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-    if (lane + 64 * c < nchunk) sum += (p[c][0] + p[c][1]) + (p[c][2] + p[c][3]);
+  ROW_CHUNKS(c, ci) sum += ROW_SUM4(p[c]);
   const float mu = wave_sum(sum) * invD;
   float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int ci = lane + 64 * c;
-    if (ci < nchunk) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = p[c][e] - mu;
-        q = fmaf(d, d, q);
-      }
-      *reinterpret_cast<f32x4*>(pooled + (size_t)s * D + 4 * ci) = p[c];
-    }
+  ROW_CHUNKS(c, ci) {
+    ROW_SQDEV4(q, p[c], mu);
+    *reinterpret_cast<f32x4*>(pooled + (size_t)s * D + 4 * ci) = p[c];
   }
   const float rs = rsqrtf(wave_sum(q) * invD + eps);
   if (lane == 0) {
@@ -152,7 +109,7 @@ __global__ __launch_bounds__(256) void pool_slice_mean_kernel(const float* __res
   float acc = 0.f;
   for (int j = 0; j < S; ++j) {
     const int s = b * S + j;
-    acc += fmaf((pooled[(size_t)s * D + c] - mean[s]) * rstd[s], g, bt);
+    acc += LN_AFFINE(pooled[(size_t)s * D + c], mean[s], rstd[s], g, bt);
   }
   out[(size_t)b * D + c] = acc / (float)S;
 }
@@ -174,41 +131,33 @@ __global__ __launch_bounds__(256) void pool_bwd_rows_kernel(const float* __restr
   const float mu = mean[s], rs = rstd[s];
   f32x4 dy[NC], xh[NC], g[NC];
   float s1 = 0.f, s2 = 0.f;
+  ROW_CHUNKS(c, ci) {
+    const f32x4 d = *reinterpret_cast<const f32x4*>(dout + (size_t)b * D + 4 * ci);
+    const f32x4 p = *reinterpret_cast<const f32x4*>(pooled + (size_t)s * D + 4 * ci);
+    const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * ci);
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int ci = lane + 64 * c;
-    if (ci < nchunk) {
-      const f32x4 d = *reinterpret_cast<const f32x4*>(dout + (size_t)b * D + 4 * ci);
-      const f32x4 p = *reinterpret_cast<const f32x4*>(pooled + (size_t)s * D + 4 * ci);
-      const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * ci);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        dy[c][e] = d[e] * invS;
-        xh[c][e] = (p[e] - mu) * rs;
-        g[c][e] = dy[c][e] * gm[e];
-        s1 += g[c][e];
-        s2 = fmaf(g[c][e], xh[c][e], s2);
-      }
+    for (int e = 0; e < 4; ++e) {
+      dy[c][e] = d[e] * invS;
+      xh[c][e] = (p[e] - mu) * rs;
+      g[c][e] = dy[c][e] * gm[e];
+      s1 += g[c][e];
+      s2 = fmaf(g[c][e], xh[c][e], s2);
     }
   }
   const float m1 = wave_sum(s1) * invD, m2 = wave_sum(s2) * invD;
   float* pr = part + (size_t)s * 3 * D;
+  ROW_CHUNKS(c, ci) {
+    f32x4 dp, dg, dsc;
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int ci = lane + 64 * c;
-    if (ci < nchunk) {
-      f32x4 dp, dg, dsc;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        dp[e] = rs * (g[c][e] - m1 - xh[c][e] * m2);
-        dg[e] = dy[c][e] * xh[c][e];
-        dsc[e] = dp[e] * scale;
-      }
-      *reinterpret_cast<f32x4*>(dps + (size_t)s * D + 4 * ci) = dsc;
-      *reinterpret_cast<f32x4*>(pr + 4 * ci) = dg;
-      *reinterpret_cast<f32x4*>(pr + D + 4 * ci) = dy[c];
-      *reinterpret_cast<f32x4*>(pr + 2 * D + 4 * ci) = dp;
+    for (int e = 0; e < 4; ++e) {
+      dp[e] = LN_DX(rs, g[c][e], m1, xh[c][e], m2);
+      dg[e] = dy[c][e] * xh[c][e];
+      dsc[e] = dp[e] * scale;
     }
+    *reinterpret_cast<f32x4*>(dps + (size_t)s * D + 4 * ci) = dsc;
+    *reinterpret_cast<f32x4*>(pr + 4 * ci) = dg;
+    *reinterpret_cast<f32x4*>(pr + D + 4 * ci) = dy[c];
+    *reinterpret_cast<f32x4*>(pr + 2 * D + 4 * ci) = dp;
   }
 }
 
@@ -247,29 +196,17 @@ __global__ __launch_bounds__(256) void pool_dx_kernel(const float* __restrict__ 
   for (int row = wave; row < M; row += nwaves) {
     const int s = row / T, t = row - s * T;
     const bool pooled_row = cls ? (t == 0) : (t != 0);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ci = lane + 64 * c;
-      if (ci < nchunk) {
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (pooled_row) v = *reinterpret_cast<const f32x4*>(dps + (size_t)s * D + 4 * ci);
-        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dx + (size_t)row * D + 4 * ci));
-        if (dxb != nullptr) {
-          u32x2 wv = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-          __builtin_nontemporal_store(wv, reinterpret_cast<u32x2*>(dxb + (size_t)row * D + 4 * ci));
-        }
+    ROW_CHUNKS(c, ci) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (pooled_row) v = *reinterpret_cast<const f32x4*>(dps + (size_t)s * D + 4 * ci);
+      __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dx + (size_t)row * D + 4 * ci));
+      if (dxb != nullptr) {
+        u32x2 wv = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+        __builtin_nontemporal_store(wv, reinterpret_cast<u32x2*>(dxb + (size_t)row * D + 4 * ci));
       }
     }
   }
 }
-
-#define POOL_DISPATCH(KERNEL, GRID, BLK, ...)                                                             \
-  switch (nc) {                                                                                           \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, GRID, BLK, 0, st, __VA_ARGS__); break;                          \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, GRID, BLK, 0, st, __VA_ARGS__); break;                          \
-    case 3: case 4: hipLaunchKernelGGL(KERNEL<4>, GRID, BLK, 0, st, __VA_ARGS__); break;                  \
-    default: hipLaunchKernelGGL(KERNEL<8>, GRID, BLK, 0, st, __VA_ARGS__); break;                         \
-  }
 
 }  // namespace octmae
 using namespace octmae;
@@ -285,19 +222,19 @@ extern "C" int octmae_slice_pool_ws_floats(int BS, int T, int D) {
 extern "C" int octmae_slice_pool_fwd(const float* x, const float* gamma, const float* beta, float* out, float* pooled, float* mean,
                                      float* rstd, float* ws, int B, int S, int T, int D, int cls, float eps, void* stream) {
   OCTMAE_CHECK_ARG(x && gamma && beta && out && pooled && mean && rstd && ws);
-  OCTMAE_CHECK_ARG(B > 0 && S > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 256 * PL_MAXC && (cls == 0 || cls == 1));
+  OCTMAE_CHECK_ARG(S > 0 && T > 0 && row_shape_ok(B, D) && (cls == 0 || cls == 1));
   OCTMAE_CHECK_ARG(cls == 1 || T >= 2);
   OCTMAE_CHECK_ARG((long long)B * S * T * D < (1LL << 40));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int BS = B * S;
-  const int nc = (D / 4 + 63) / 64;
+  const int nc = row_nc(D);
   const int nsplit = cls ? 1 : pool_nsplit(BS, T);
   if (!cls) {
     const int rps = (T - 1 + nsplit - 1) / nsplit;
-    POOL_DISPATCH(pool_colsum_kernel, dim3(nsplit, BS), dim3(256), x, ws, T, D, rps);
+    ROW_DISPATCH(pool_colsum_kernel, dim3(nsplit, BS), dim3(256), x, ws, T, D, rps);
     OCTMAE_LAUNCH_CHECK();
   }
-  POOL_DISPATCH(pool_stats_kernel, dim3((BS + 3) / 4), dim3(256), x, ws, nsplit, pooled, mean, rstd, BS, T, D, cls, eps);
+  ROW_DISPATCH(pool_stats_kernel, dim3((BS + 3) / 4), dim3(256), x, ws, nsplit, pooled, mean, rstd, BS, T, D, cls, eps);
   OCTMAE_LAUNCH_CHECK();
   hipLaunchKernelGGL(pool_slice_mean_kernel, dim3((D + 255) / 256, B), dim3(256), 0, st, pooled, mean, rstd, gamma, beta, out, S, D);
   OCTMAE_LAUNCH_CHECK();
@@ -308,17 +245,17 @@ extern "C" int octmae_slice_pool_bwd(const float* dout, const float* pooled, con
                                      float* dx, void* dx_bf16, float* dgamma, float* dbeta, float* dxsum, float* ws, int B, int S,
                                      int T, int D, int cls, void* stream) {
   OCTMAE_CHECK_ARG(dout && pooled && mean && rstd && gamma && dx && ws);
-  OCTMAE_CHECK_ARG(B > 0 && S > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 256 * PL_MAXC && (cls == 0 || cls == 1));
+  OCTMAE_CHECK_ARG(S > 0 && T > 0 && row_shape_ok(B, D) && (cls == 0 || cls == 1));
   OCTMAE_CHECK_ARG(cls == 1 || T >= 2);
   OCTMAE_CHECK_ARG((long long)B * S * T * D < (1LL << 40));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int BS = B * S;
   const int M = BS * T;
-  const int nc = (D / 4 + 63) / 64;
+  const int nc = row_nc(D);
   float* dps = ws;                         // [BS][D]
   float* part = ws + (size_t)BS * D;       // [BS][3][D]
   const float scale = cls ? 1.0f : 1.0f / (float)(T - 1);
-  POOL_DISPATCH(pool_bwd_rows_kernel, dim3((BS + 3) / 4), dim3(256), dout, pooled, mean, rstd, gamma, dps, part, BS, S, D, scale);
+  ROW_DISPATCH(pool_bwd_rows_kernel, dim3((BS + 3) / 4), dim3(256), dout, pooled, mean, rstd, gamma, dps, part, BS, S, D, scale);
   OCTMAE_LAUNCH_CHECK();
   if (dgamma != nullptr || dbeta != nullptr || dxsum != nullptr) {
     hipLaunchKernelGGL(pool_bwd_finish_kernel, dim3((D + 63) / 64, 3), dim3(1024), 0, st, part, BS, D, dgamma, dbeta, dxsum);
@@ -328,7 +265,7 @@ extern "C" int octmae_slice_pool_bwd(const float* dout, const float* pooled, con
   int blocks = (M + 3) / 4;
   if (blocks > 2048) blocks = 2048;
   bf16_t* dxb = reinterpret_cast<bf16_t*>(dx_bf16);
-  POOL_DISPATCH(pool_dx_kernel, dim3(blocks), dim3(256), dps, dx, dxb, M, T, D, cls);
+  ROW_DISPATCH(pool_dx_kernel, dim3(blocks), dim3(256), dps, dx, dxb, M, T, D, cls);
   OCTMAE_LAUNCH_CHECK();
   return 0;
 }

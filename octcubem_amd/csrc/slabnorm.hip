@@ -21,7 +21,7 @@
 //                every sum has a fixed order, two runs are bit-equal.
 //   bytes/element: forward 4 + 4 (x twice; the second read follows the first closely) + 2 (A) + 8 (gamma, beta, per row of the batch);
 //                  backward 2 x (2 + 4) read + 4 (gamma) x 2 + 4 (dx) written.
-#include "common.hpp"
+#include "rowwave.hpp"
 #include "../../include/octmae.h"
 
 namespace octmae {
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void slab_apply_kernel(const float* __restrict
       load8_f32<VEC>(gamma + k, nv, gm);
       load8_f32<VEC>(beta + k, nv, bt);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = fmaf((tile[(lb + i) * SN_LD + cc] - mu) * rs, gm[i], bt[i]);
+      for (int i = 0; i < 8; ++i) o[i] = LN_AFFINE(tile[(lb + i) * SN_LD + cc], mu, rs, gm[i], bt[i]);
       if (VEC) {
         const u32x4 w = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7])};
         *reinterpret_cast<u32x4*>(Ar + k) = w;
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void slab_bwd_dx_kernel(const bf16_t* __restri
           const float gy = d[i] * gm[it][i];
           ag[it][i] = fmaf(d[i], xh, ag[it][i]);
           ab[it][i] += d[i];
-          *w = rs * (gy - m1 - xh * m2);
+          *w = LN_DX(rs, gy, m1, xh, m2);
         }
       }
     }
