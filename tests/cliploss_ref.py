@@ -45,6 +45,42 @@ def gamma(k):
     return k * U / (1.0 - k * U)
 
 
+# ------------------------------------------------------------------------------------------------ the forward's launch plan, restated
+TARGET_WGS = 1024       # CL_TARGET_WGS
+MAX_SPLIT = 64          # CL_MAX_SPLIT
+# (n, m, d, offset) at which a workgroup of clip_lse_kernel walks more than one column tile, with the plan the constants above give:
+# tests/test_cpu_cliploss.py compares the constants with csrc/cliploss.hip and the plans with this table, so whoever changes a constant
+# is told to move the shapes; tests/test_gpu_cliploss.py runs them.
+TRIP_SHAPES = ((8, 8325, 3, 8200), (3001, 3001, 5, 0), (130, 65500, 2, 65000))
+TRIP_PLANS = (dict(row_blocks_a=1, tiles_a=131, split_a=64, row_blocks_b=131, tiles_b=1, split_b=1),          # a side: 2 or 3 trips
+              dict(row_blocks_a=47, tiles_a=47, split_a=22, row_blocks_b=47, tiles_b=47, split_b=22),         # both sides: 2 or 3 trips
+              dict(row_blocks_a=3, tiles_a=1024, split_a=64, row_blocks_b=1024, tiles_b=3, split_b=1))        # a: 16 trips; b: split 1, 3 tiles
+
+
+def split(row_blocks, col_tiles, target_wgs=TARGET_WGS):
+    """cl_split: the workgroups that share one row block's column tiles"""
+    return max(1, min(-(-target_wgs // row_blocks), col_tiles, MAX_SPLIT))
+
+
+def plan(n, m, target_wgs=TARGET_WGS):
+    """cl_plan: the a side owns rows of a and walks tiles of b, the b side the other way round"""
+    p = dict(row_blocks_a=-(-n // TILE), row_blocks_b=-(-m // TILE), tiles_a=-(-m // TILE), tiles_b=-(-n // TILE))
+    p["split_a"] = split(p["row_blocks_a"], p["tiles_a"], target_wgs)
+    p["split_b"] = split(p["row_blocks_b"], p["tiles_b"], target_wgs)
+    return p
+
+
+def ws_floats(n, m):
+    """cl_ws_floats: one (max, sum) per row and workgroup of each side"""
+    p = plan(n, m)
+    return 2 * (p["split_a"] * n + p["split_b"] * m)
+
+
+def walked_tiles(col_tiles, nsplit, y):
+    """the column tiles workgroup y of a row block visits, in its order"""
+    return list(range(y, col_tiles, nsplit))
+
+
 def _d(t):
     return t.detach().to("cpu", F64) if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t), dtype=F64)
 
@@ -184,6 +220,93 @@ def _online_lse(z, drop_tile=None):
             s = (s + e[:, c]).astype(f)
         mx, sm = nm, s
     return (mx + np.log(sm).astype(f)).astype(f)
+
+
+def _merge(m1, s1, m2, s2):
+    """cl_merge in f32: (m1, s1) + (m2, s2) of two partial log-sum-exps"""
+    f = np.float32
+    M = np.maximum(m1, m2)
+    with np.errstate(invalid="ignore"):
+        e1 = np.where(m1 == M, f(1), np.exp((m1 - M).astype(f))).astype(f)
+        e2 = np.where(m2 == M, f(1), np.exp((m2 - M).astype(f))).astype(f)
+    return M, ((s1 * e1).astype(f) + (s2 * e2).astype(f)).astype(f)
+
+
+def split_lse(z, nsplit, fault=None):
+    """The forward as launched: workgroup y of ``nsplit`` walks the 64-column tiles y, y + nsplit, ... of the f32 logits z [rows, cols]
+    with the online (max, sum) of ``_online_lse`` and the partials are merged in order.  fault in {None, "no_rescale", "inverse",
+    "restart"}: the carried sum is not rescaled when the maximum rises, is rescaled by exp(nm - mx), or is dropped at every trip."""
+    f = np.float32
+    rows, cols = z.shape
+    tiles = -(-cols // TILE)
+    M = S = None
+    for y in range(nsplit):
+        mx = np.full(rows, -np.inf, dtype=f)
+        sm = np.zeros(rows, dtype=f)
+        for ct in walked_tiles(tiles, nsplit, y):
+            blk = z[:, ct * TILE:(ct + 1) * TILE]
+            nm = np.maximum(mx, blk.max(axis=1))
+            with np.errstate(invalid="ignore", over="ignore"):
+                arg = (nm - mx) if fault == "inverse" else (mx - nm)
+                fac = np.where(mx == nm, f(1), np.exp(arg.astype(f))).astype(f)
+            if fault == "no_rescale":
+                fac = np.ones(rows, dtype=f)
+            if fault == "restart":
+                fac = np.zeros(rows, dtype=f)
+            with np.errstate(invalid="ignore", over="ignore"):
+                s = (sm * fac).astype(f)
+            e = np.exp((blk - nm[:, None]).astype(f)).astype(f)
+            for c in range(e.shape[1]):
+                s = (s + e[:, c]).astype(f)
+            mx, sm = nm, s
+        M, S = (mx, sm) if M is None else _merge(M, S, mx, sm)
+    return (M + np.log(S).astype(f)).astype(f)
+
+
+# ---- ordered scores on the first trip shape: b[j] = c_j u + noise with every a[i] close to u, so that the order of c fixes the order of
+# the tile maxima a workgroup meets, and with it which branch of nm = max(mx, tmax), sm * exp(mx - nm) each of its trips takes
+ORDERS = ("rising", "falling", "peak")
+ORDER_SCALE = 3.0         # a trip (64 tiles on) moves the tile maximum by about 2: the carried sum stays a visible part of the new one
+ORDER_MARGIN = 1e-3       # on float64 logits of size <= 4; the f32 logits differ from them by less than 1e-5 (``reference``'s ez)
+
+
+def ordered_problem(order):
+    n, m, d, off = TRIP_SHAPES[0]
+    rng = np.random.default_rng([77, ORDERS.index(order)])
+    u = np.array([2.0, -1.0, 2.0]) / 3.0
+    pos = np.arange(m) / (m - 1.0)
+    c = {"rising": 2.0 * pos - 1.0, "falling": 1.0 - 2.0 * pos, "peak": 1.0 - 4.0 * np.abs(pos - 0.5)}[order]
+    a = u + 0.3 * rng.standard_normal((n, d)) / np.sqrt(d)
+    a /= np.linalg.norm(a, axis=1, keepdims=True)
+    b = c[:, None] * u + 0.02 * rng.standard_normal((m, d))
+    _, _, wr, wc = make_problem(n, m, d, seed=78, offset=off)
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    return a, b, np.float32(ORDER_SCALE), wr, wc, off
+
+
+def trip_maxima(a, b, scale):
+    """[y] -> float64 array [trips of workgroup y, n]: the maximum of every row of the float64 logits over each tile that workgroup y of
+    the a side walks, in its order"""
+    z = float(scale) * a.astype(np.float64) @ b.astype(np.float64).T
+    p = plan(a.shape[0], b.shape[0])
+    tmax = np.stack([z[:, j0:j0 + TILE].max(axis=1) for j0 in range(0, b.shape[0], TILE)])      # [tiles, n]
+    return [tmax[walked_tiles(p["tiles_a"], p["split_a"], y)] for y in range(p["split_a"])]
+
+
+def assert_trip_order(order, walks):
+    """the condition on the inputs: what the tile maxima of every row do from trip to trip of every workgroup"""
+    assert sorted({len(w) for w in walks}) == [2, 3]
+    for w in walks:
+        step = np.diff(w, axis=0)
+        if order == "rising":                      # every trip raises the maximum of every row: the carried sum is rescaled each time
+            assert (step > ORDER_MARGIN).all()
+        elif order == "falling":                   # no trip after the first raises it: the factor is 1, the new terms are the small ones
+            assert (step < -ORDER_MARGIN).all()
+        elif len(w) == 3:                          # up, then down
+            assert (step[0] > ORDER_MARGIN).all() and (step[1] < -ORDER_MARGIN).all()
+    if order == "peak":
+        assert sum(len(w) == 3 for w in walks) == 3
+    assert float(np.abs(np.concatenate(walks)).max()) <= 4.0
 
 
 def emulate(a, b, scale, wr, wc=None, offset=0, g=1.0, fault=None):

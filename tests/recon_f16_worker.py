@@ -28,6 +28,9 @@ if __name__ == "__main__":
     for name in ("a", "d"):
         T.check_denorm(name, golden)
         passed.append("denorm " + name)
+    for denorm in (False, True):
+        T.check_past_the_grid_cap(denorm)
+        passed.append("past the cap denorm" if denorm else "past the cap")
     torch.cuda.synchronize()
     with open(a.out, "w") as f:
         json.dump({"lib": os.path.basename(_lib.LIB_PATH), "lp_is_f16": bool(ops.LP_IS_F16), "passed": passed}, f)

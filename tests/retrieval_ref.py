@@ -27,6 +27,25 @@ def counts(scores, target=None, keep=None, row_group=None, col_group=None) -> np
     return out
 
 
+# ---- the launch plan of octmae_retrieval_ranks, restated
+TILE = 64               # RR_ROWS == RR_COLS
+TARGET_WGS = 1024       # RR_TARGET_WGS
+MAX_GRID_Y = 65535
+# (n, m, d) at which a workgroup of retrieval_ranks_kernel walks more than one column tile, with (row blocks, column tiles, split):
+# tests/test_cpu_retrieval.py compares the constants with csrc/retrieval.hip and the plans with this table; tests/test_gpu_retrieval.py
+# runs the shapes
+TRIP_SHAPES = ((3, 65600, 2), (3001, 3001, 3), (65473, 131, 2))
+TRIP_PLANS = ((1, 1025, 1024),          # one workgroup of 1024 makes a second trip, onto a whole last tile
+              (47, 47, 22),             # two or three trips everywhere, a 57-column last tile
+              (1024, 3, 1))             # split 1: every workgroup walks all three tiles, the last of 3 columns
+
+
+def plan(n, m):
+    """(row blocks, column tiles, split): the grid is row blocks x split, workgroup y walks tiles y, y + split, ..."""
+    row_blocks, col_tiles = -(-n // TILE), -(-m // TILE)
+    return row_blocks, col_tiles, max(1, min(-(-TARGET_WGS // row_blocks), col_tiles, MAX_GRID_Y))
+
+
 def _np(x):
     return None if x is None else (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x))
 

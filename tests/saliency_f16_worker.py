@@ -32,7 +32,7 @@ if __name__ == "__main__":
 
     ops.ATTN_BWD_FUSED_MIN_FILL = 0.0                    # as tests/conftest.py sets it for every GPU test
     res = {"lib": os.path.basename(_lib.LIB_PATH), "lp_is_f16": bool(ops.LP_IS_F16)}
-    res["scatter_cases"] = sum(T.check_scatter(*geom) for geom in T.SCATTER_GEOM)
+    res["scatter_cases"] = sum(T.check_scatter(*geom) for geom in T.SCATTER_GEOM) + T.check_scatter_past_the_grid_cap()
     res["patch_embed"] = {f"{kind} {ids}": T.check_patch_embed(kind, ids) for kind in ("3d", "2d") for ids in (False, True)}
     res["parity"] = {v: T.measure_model_parity(v)[0] for v in ("native", "flash_compat", "flash_blocks", "vit2d")}
     torch.cuda.synchronize()

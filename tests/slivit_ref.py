@@ -263,3 +263,68 @@ def dwconv_ref64(x, wt, bias):
 def dwconv_bound(mag):
     """the issue's per-element bound for the forward and the input gradient: 50 fp32 terms (49 taps + bias / residual gradient) in any order"""
     return gamma_n(50) * mag
+
+
+# ------------------------------------------------------------------------------------------------ launch plans of csrc/convnext.hip, restated
+DW_TH, DW_TW, DW_CB = 8, 16, 32          # output pixels per tile, channels per tile
+WGRAD_CAP = 1024                         # workgroups of dwconv7_wgrad_kernel over all channel blocks: G <= 1024 / cblocks
+LS_CAP = 1024                            # ... and of layer_scale_bwd_kernel: G <= 1024 / ncb
+# shapes at which a workgroup of those kernels makes a second trip (tests/test_cpu_slivit.py compares the constants with the source and
+# the plans with these numbers; tests/test_gpu_slivit_kernels.py runs them): (B, H, W, C) -> (ntiles, cblocks, G), (M, C) -> (CVB, RP, ncb, G)
+DW_TRIP_SHAPES = ((2, 33, 100, 512), (3, 48, 112, 264))
+DW_TRIP_PLANS = ((70, 16, 64), (126, 9, 113))
+LS_TRIP_SHAPE = (2 * 1024 * 128 + 77, 8)
+LS_TRIP_PLAN = (2, 128, 1, 1024)
+
+
+def dw_wgrad_plan(B, H, W, C):
+    """(ntiles, cblocks, G): workgroup g of each channel block walks the tiles g, g + G, ... and leaves one partial of 50 x C floats"""
+    ntiles = B * (-(-H // DW_TH)) * (-(-W // DW_TW))
+    cblocks = -(-C // DW_CB)
+    return ntiles, cblocks, min(ntiles, max(1, WGRAD_CAP // cblocks))
+
+
+def ls_bwd_plan(M, C):
+    """(CVB, RP, ncb, G): a workgroup is RP rows x CVB channel vectors; workgroup g walks the rows g RP + part, + G RP, ..."""
+    CV = C // 4
+    CVB = min(CV, 256)
+    RP = 256 // CVB
+    ncb = -(-CV // CVB)
+    return CVB, RP, ncb, min(-(-M // RP), max(1, LS_CAP // ncb))
+
+
+# ---- the layer-scale gamma gradient, exactly: a dyadic family (as the retrieval tests' one) and the walk that visits the rows
+def ls_dyadic_problem(M, C, seed):
+    """dout, branch [M, C] with entries in {-2 .. 2} / 4 and an earlier gradient gg0 [C] in multiples of 1/16 below 64; gamma U(0.5, 1.5).
+    Every product dout * branch is a multiple of 1/16 of size <= 1/4 and every partial sum of up to 2^20 of them, with gg0, stays below
+    2^18 in multiples of 1/16: exact in fp32 whatever the order, fused or not.  The gamma gradient is then ONE number, and each trip of
+    each workgroup, each of the RP row parts and each of the G partials has to arrive in it."""
+    g = torch.Generator().manual_seed(seed)
+    dout = torch.randint(-2, 3, (M, C), generator=g).float() / 4
+    branch = torch.randint(-2, 3, (M, C), generator=g).float() / 4
+    gg0 = torch.randint(-1000, 1001, (C,), generator=g).float() / 16
+    gamma = torch.rand((C,), generator=g) + 0.5
+    assert M <= 2 ** 20
+    return dout, branch, gamma, gg0
+
+
+def ls_bwd_walk_sum(dout, branch, fault=None):
+    """The column sums of dout * branch (float64, exact for the dyadic family) as layer_scale_bwd_kernel's walk collects them: row r
+    belongs to part r % RP of workgroup (r // RP) % G on its trip (r // RP) // G.  fault in {None, "restart", "drop_trip", "fold"}: the
+    accumulator starts again at every trip (only a thread's last trip survives), workgroup 5 loses its second trip, the fold of the RP
+    parts stops one part short."""
+    M, C = dout.shape
+    CVB, RP, ncb, G = ls_bwd_plan(M, C)
+    r = torch.arange(M)
+    part, grp, trip = r % RP, (r // RP) % G, (r // RP) // G
+    keep = torch.ones(M, dtype=torch.bool)
+    if fault == "restart":
+        last = (M - 1 - (grp * RP + part)) // (G * RP)          # the last trip of the thread that owns the row
+        keep = trip == last
+    elif fault == "drop_trip":
+        keep = ~((grp == 5) & (trip == 1))
+    elif fault == "fold":
+        keep = part != RP - 1 if RP > 1 else keep
+    else:
+        assert fault is None
+    return (dout.double() * branch.double())[keep].sum(0)

@@ -74,6 +74,53 @@ def test_injected_faults_leave_the_bounds(fault):
     assert over["loss"] > 1.0 and max(over["da"], over["db"]) > 1.0, over
 
 
+def hip_constant(text, name):
+    return int(re.search(rf"^constexpr int {name} = (\d+);", text, re.M).group(1))
+
+
+def test_restated_plan_follows_the_kernel_constants_and_the_trip_shapes_lie_past_the_split():
+    """Whoever changes a constant of csrc/cliploss.hip is told here to move R.TRIP_SHAPES (tests/test_gpu_cliploss.py runs them)."""
+    src = open(os.path.join(ROOT, "octcubem_amd", "csrc", "cliploss.hip")).read()
+    assert hip_constant(src, "CL_TARGET_WGS") == R.TARGET_WGS and hip_constant(src, "CL_MAX_SPLIT") == R.MAX_SPLIT
+    assert hip_constant(src, "CL_ROWS") == hip_constant(src, "CL_COLS") == R.TILE and hip_constant(src, "CL_K") == R.KSTEP
+    # cl_split as written: ceil(target / row_blocks), then the two caps
+    assert re.search(r"long long s = \(CL_TARGET_WGS \+ row_blocks - 1\) / row_blocks;\s*if \(s > col_tiles\) s = col_tiles;\s*"
+                     r"if \(s > CL_MAX_SPLIT\) s = CL_MAX_SPLIT;", src)
+    assert re.search(r"return 2 \* \(\(long long\)p\.split_a \* n \+ \(long long\)p\.split_b \* m\);", src)
+    assert R.split(1, 1) == 1 and R.split(1, 200) == 64 and R.split(40, 200) == 26 and R.split(4000, 9) == 1 and R.split(512, 9) == 2
+    for (n, m, d, off), want in zip(R.TRIP_SHAPES, R.TRIP_PLANS):
+        p = R.plan(n, m)
+        assert p == want, (n, m, p)
+        assert p["tiles_a"] > p["split_a"] and n + off <= m
+        assert R.ws_floats(n, m) == 2 * (want["split_a"] * n + want["split_b"] * m)
+    first, second, third = (R.plan(n, m) for n, m, _, _ in R.TRIP_SHAPES)
+    assert first["split_a"] == R.MAX_SPLIT < first["tiles_a"] <= 3 * R.MAX_SPLIT                      # the cap itself; two or three trips
+    assert second["split_a"] < R.plan(3001, 3001, 2 * R.TARGET_WGS)["split_a"] < second["tiles_a"]       # trips even at twice the target
+    assert third["split_b"] == 1 and third["tiles_b"] == 3 and 130 % R.TILE == 2 and third["tiles_a"] == 16 * third["split_a"]
+    # no earlier case of the GPU module leaves a workgroup more than one tile: the gap these shapes close
+    for n, m in ((1, 1), (63, 63), (64, 64), (65, 65), (129, 129), (8, 136), (33, 200), (65, 70)):
+        q = R.plan(n, m)
+        assert q["split_a"] == q["tiles_a"] and q["split_b"] == q["tiles_b"]
+
+
+@pytest.mark.parametrize("order", R.ORDERS)
+def test_split_walk_restatement_on_ordered_scores(order):
+    """The ordered problems of the GPU test: their condition holds, the f32 walk as launched (split 64, two or three trips, partials
+    merged in order) keeps every row's log-sum-exp inside the derived bound, and a carried sum that is not rescaled, rescaled the wrong
+    way or dropped does not -- wherever the order of the maxima lets that fault act at all."""
+    a, b, scale, wr, wc, off = R.ordered_problem(order)
+    R.assert_trip_order(order, R.trip_maxima(a, b, scale))
+    ref = R.reference(a, b, scale, wr, wc, off)
+    z = (scale * R._fma_scores(a, b)).astype(np.float32)
+    p = R.plan(*z.shape)
+    ok = R.worst(torch.from_numpy(R.split_lse(z, p["split_a"])), ref["lse_row"])
+    over = {f: R.worst(torch.from_numpy(R.split_lse(z, p["split_a"], fault=f)), ref["lse_row"]) for f in ("no_rescale", "inverse", "restart")}
+    print(order, "worst |err| / bound", ok, over)
+    assert ok <= 1.0
+    assert over["restart"] > 1.0 and over["inverse"] > 1.0      # a dropped sum always shows; exp(nm - -inf) at the first tile is 0 * inf
+    assert (over["no_rescale"] > 1.0) == (order != "falling")   # a maximum that never rises is never rescaled: only the others see it
+
+
 def test_abi_declares_the_clip_loss_entry_points():
     from octcubem_amd import _lib
     header = open(os.path.join(ROOT, "include", "octmae.h")).read()

@@ -204,3 +204,21 @@ def test_abi_declares_retrieval_ranks():
     assert re.search(r"^ \* 19: octmae_retrieval_ranks", header, re.M)
     mk = open(os.path.join(ROOT, "octcubem_amd", "csrc", "Makefile")).read()
     assert "retrieval.hip" in re.search(r"^SRCS = (.*)$", mk, re.M).group(1)
+
+
+def test_restated_plan_follows_the_kernel_constants_and_the_trip_shapes_lie_past_the_split():
+    """Whoever changes a constant of csrc/retrieval.hip is told here to move R.TRIP_SHAPES (tests/test_gpu_retrieval.py runs them)."""
+    src = open(os.path.join(ROOT, "octcubem_amd", "csrc", "retrieval.hip")).read()
+    const = lambda name: int(re.search(rf"^constexpr int {name} = (\d+);", src, re.M).group(1))
+    assert const("RR_ROWS") == const("RR_COLS") == R.TILE and const("RR_TARGET_WGS") == R.TARGET_WGS
+    assert re.search(r"long long split = \(RR_TARGET_WGS \+ row_blocks - 1\) / row_blocks;\s*if \(split > col_tiles\) split = col_tiles;\s*"
+                     rf"if \(split > {R.MAX_GRID_Y}\) split = {R.MAX_GRID_Y};", src)
+    assert R.plan(1, 1) == (1, 1, 1) and R.plan(131, 131) == (3, 3, 3) and R.plan(64, 70000) == (1, 1094, 1024)
+    for (n, m, d), want in zip(R.TRIP_SHAPES, R.TRIP_PLANS):
+        assert R.plan(n, m) == want, (n, m, R.plan(n, m))
+        assert want[1] > want[2]                                   # more tiles than workgroups to walk them: a second trip
+    assert R.TRIP_PLANS[2][2] == 1 and R.TRIP_PLANS[0][2] == R.TARGET_WGS
+    # no other size of the GPU module leaves a workgroup more than one tile
+    for n in (1, 2, 63, 64, 65, 131):
+        for m in (1, 2, 63, 64, 65, 131):
+            assert R.plan(n, m)[1] == R.plan(n, m)[2]

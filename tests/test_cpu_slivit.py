@@ -200,3 +200,48 @@ def test_dwconv_bound_passes_another_order_and_catches_a_lost_tap(shape):
     if H * W > 1:                                             # a 1 x 1 map meets the centre tap only: flipping changes nothing there
         err = (_dwconv_f32(x, wt, bias, range(49), flip=True).double() - z64).abs()
         assert float((err > bound).double().mean()) > 0.5
+
+
+def test_restated_launch_plans_follow_the_kernel_constants_and_the_trip_shapes_lie_past_the_caps():
+    """Whoever changes a constant of csrc/convnext.hip is told here to move the shapes at which tests/test_gpu_slivit_kernels.py makes
+    a workgroup walk a second tile or a second round of rows."""
+    import re
+    src = open(os.path.join(ROOT, "octcubem_amd", "csrc", "convnext.hip")).read()
+    m = re.search(r"constexpr int DW_TH = (\d+), DW_TW = (\d+);", src)
+    assert (int(m.group(1)), int(m.group(2))) == (R.DW_TH, R.DW_TW)
+    assert int(re.search(r"constexpr int DW_CB = (\d+),", src).group(1)) == R.DW_CB
+    assert int(re.search(r"constexpr int DWW_ROWS = (\d+);", src).group(1)) == 50
+    assert int(re.search(r"int cap = (\d+) / s\.cblocks;", src).group(1)) == R.WGRAD_CAP
+    assert int(re.search(r"int cap = (\d+) / s->ncb;", src).group(1)) == R.LS_CAP
+    assert re.search(r"s->CVB = CV < 256 \? CV : 256;\s*s->RP = 256 / s->CVB;", src)
+    for shape, want in zip(R.DW_TRIP_SHAPES, R.DW_TRIP_PLANS):
+        ntiles, cblocks, G = R.dw_wgrad_plan(*shape)
+        assert (ntiles, cblocks, G) == want and G < ntiles < 2 * G           # some workgroups take two tiles, the others one
+    assert R.dw_wgrad_plan(2, 33, 100, 512)[0] - R.dw_wgrad_plan(2, 33, 100, 512)[2] == 6
+    assert R.dw_wgrad_plan(3, 33, 40, 136) == (45, 5, 45)                    # the largest earlier case: one tile per workgroup
+    assert R.dw_wgrad_plan(13, 56, 56, 96)[0] > R.dw_wgrad_plan(13, 56, 56, 96)[2] == 341 >= R.dw_wgrad_plan(12, 56, 56, 96)[0]
+    M, C = R.LS_TRIP_SHAPE
+    CVB, RP, ncb, G = R.ls_bwd_plan(M, C)
+    assert (CVB, RP, ncb, G) == R.LS_TRIP_PLAN and 2 * G * RP < M < 3 * G * RP and M % RP != 0
+    assert R.ls_bwd_plan(1031, 1032) == (256, 1, 2, 512) and R.ls_bwd_plan(1031, 136) == (34, 7, 1, 148)
+
+
+def test_dyadic_layer_scale_problem_is_exact_and_every_trip_shows_in_it():
+    """The exact gamma-gradient case of tests/test_gpu_slivit_kernels.py: its sums are fp32 numbers in any order of addition, the
+    restated walk visits every row once, and a restarted accumulator, one workgroup's dropped second trip or a fold that stops one
+    row part short each change the gradient -- which the GPU test compares with torch.equal."""
+    M, C = R.LS_TRIP_SHAPE
+    dout, branch, gamma, gg0 = R.ls_dyadic_problem(M, C, seed=5)
+    p = dout.double() * branch.double()
+    want = gg0.double() + p.sum(0)
+    assert torch.equal(want.float().double(), want) and float(p.abs().sum(0).max() + gg0.abs().max()) * 16 < 2 ** 24
+    assert torch.equal((p * 16).round(), p * 16) and float(p.abs().max()) <= 0.25
+    # fp32 sums in two very different orders: a running sum down the rows, and blocks of 4099 rows summed then added
+    run = torch.zeros(C)
+    for blk in p.float().split(4099):
+        run = run + blk.sum(0)
+    assert torch.equal(run.double(), p.sum(0)) and torch.equal(p.float().flip(0).cumsum(0)[-1].double(), p.sum(0))
+    assert torch.equal(R.ls_bwd_walk_sum(dout, branch), p.sum(0))
+    for fault in ("restart", "drop_trip", "fold"):
+        got = gg0.double() + R.ls_bwd_walk_sum(dout, branch, fault)
+        assert not torch.equal(got, want) and int((got != want).sum()) >= C - 1, fault

@@ -1,5 +1,6 @@
 """GPU: ops.clip_pair_loss (csrc/cliploss.hip) -- the loss and its three gradients against the float64 reference of
-tests/cliploss_ref.py, every row and every element within the bounds derived there; logits spanning +-3000; a NaN feature; bit
+tests/cliploss_ref.py, every row and every element within the bounds derived there, also where a forward workgroup walks several column
+tiles and carries its (max, sum) along (cliploss_ref.TRIP_SHAPES, ordered scores); logits spanning +-3000; a NaN feature; bit
 reproducibility; ClipLoss / ThreeModalityClipLoss fused against their ATen composition; the half-operand build; argument checks."""
 import functools
 import json
@@ -26,7 +27,11 @@ CASES = ((1, 1, 1, 0, True, 0.0, 100.0), (63, 63, 31, 0, True, 0.2, 1 / 0.07), (
          (65, 65, 33, 0, True, 0.2, 1 / 0.07), (129, 129, 512, 0, True, 0.2, 100.0), (8, 136, 512, 128, False, 0.0, 100.0),
          (33, 200, 65, 0, False, 0.2, 1 / 0.07), (33, 200, 65, 167, False, 0.2, 100.0), (33, 200, 65, 167, True, 0.2, 100.0),
          (65, 70, 300, 3, True, 0.2, 100.0), (65, 65, 33, 0, True, 1.0, 100.0))
-WORKER_CASES = (1, 3, 5, 8, 9)          # indices into CASES the half-build child repeats
+# ... and R.TRIP_SHAPES, appended: there a workgroup of clip_lse_kernel walks several column tiles and carries its (max, sum) along
+FIRST_TRIP_CASE = len(CASES)
+CASES += tuple((n, m, d, off, True, 0.2, scale) for (n, m, d, off), scale in zip(R.TRIP_SHAPES, (100.0, 1 / 0.07, 100.0)))
+TRIP_CASES = tuple(range(FIRST_TRIP_CASE, len(CASES)))
+WORKER_CASES = (1, 3, 5, 8, 9, FIRST_TRIP_CASE)          # indices into CASES the half-build child repeats
 
 
 def strided(x, pad=5):
@@ -72,6 +77,39 @@ def test_loss_and_gradients_inside_the_bounds(k):
         assert float(got["loss"]) == 0.0 and not got["da"].any() and not got["db"].any() and float(got["dscale"]) == 0.0
 
 
+@pytest.mark.parametrize("k", TRIP_CASES)
+def test_trip_cases_lie_past_the_split(k):
+    """The library's workspace answer equals the restated plan's, and under that plan a workgroup walks more than one tile."""
+    from octcubem_amd._lib import load
+    n, m = CASES[k][:2]
+    p = R.plan(n, m)
+    assert p == R.TRIP_PLANS[k - FIRST_TRIP_CASE]
+    assert load().octmae_clip_loss_ws_floats(n, m) == 2 * (p["split_a"] * n + p["split_b"] * m) == R.ws_floats(n, m)
+    trips_a, trips_b = -(-p["tiles_a"] // p["split_a"]), -(-p["tiles_b"] // p["split_b"])
+    assert p["tiles_a"] > p["split_a"] and trips_a >= 2
+    if k == TRIP_CASES[0]:
+        assert p["split_a"] == R.MAX_SPLIT and trips_a == 3 and len(R.walked_tiles(p["tiles_a"], p["split_a"], 63)) == 2
+    if k == TRIP_CASES[1]:
+        assert R.plan(n, m, 2 * R.TARGET_WGS)["split_a"] < p["tiles_a"] and p["tiles_b"] > p["split_b"]
+    if k == TRIP_CASES[2]:
+        assert trips_a == 16 and p["split_b"] == 1 and trips_b == 3 and n - 2 * R.TILE == 2 and CASES[k][4]
+
+
+@pytest.mark.parametrize("order", R.ORDERS)
+def test_ordered_tile_maxima_across_the_trips_of_a_workgroup(order):
+    """b[j] = c_j u + noise on the first trip shape (R.ordered_problem): the tile maxima of every row rise at every trip of a workgroup,
+    never rise after its first, or rise and then fall"""
+    a, b, scale, wr, wc, off = R.ordered_problem(order)
+    R.assert_trip_order(order, R.trip_maxima(a, b, scale))      # a condition on the inputs, from float64 logits, before the kernel runs
+    ref = R.reference(a, b, scale, wr, wc, off, g=G_UP)
+    got = run(a, b, scale, wr, wc, off)
+    torch.cuda.synchronize()
+    for key in ("loss", "da", "db", "dscale"):
+        w = R.worst(got[key], ref[key])
+        print(order, key, "worst |err| / bound", w)
+        assert w <= 1.0, (order, key, w)
+
+
 def test_logits_spanning_thousands_with_equal_probabilities():
     n, d = 70, 40
     a, b, wr, wc = R.make_problem(n, n, d, seed=5, zero_frac=0.1)
@@ -109,7 +147,7 @@ def test_a_nan_feature_gives_nan_and_the_next_call_is_clean():
         assert R.worst(clean[key], ref[key]) <= 1.0, key
 
 
-@pytest.mark.parametrize("k", [4, 8])
+@pytest.mark.parametrize("k", [4, 8, FIRST_TRIP_CASE + 1])
 def test_two_runs_are_bit_equal(k):
     a, b, scale, wr, wc, off, _ = problem(k)
     x, y = run(a, b, scale, wr, wc, off), run(a, b, scale, wr, wc, off)

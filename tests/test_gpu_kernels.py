@@ -670,6 +670,79 @@ def test_attention_backward_fused_row_constants(HD, N):
     assert torch.equal(ops.attn_bwd(qkv, o, do, lse, B, N, H, HD, scale, fused=False), d1)     # the host wrapper's two-kernel form
 
 
+@pytest.mark.parametrize("HD", [32, 64])
+def test_attention_row_constants_past_the_grid_cap(HD):
+    """octmae_attn_bwd_rowconst (attn_delta_kernel): one wave per token row on at most 4096 workgroups of 4 waves; B N = 16 646 rows
+    leave 262 rows -- 65 workgroups and two waves of the next -- a second trip.  rowc[0] = -lse log2(e) is one fp32 product: bit for
+    bit; rowc[1] = -sum_d dO O is HD exact products of 16-bit values added in fp32 in some order: within gamma_HD sum |dO O| of float64."""
+    from octcubem_amd import _lib
+    B, N, H = 2378, 7, 2
+    assert 4096 * 4 < B * N < 4096 * 4 + 4096 and (B * N - 4096 * 4) % 4 != 0
+    g = torch.Generator().manual_seed(HD)
+    o = bf(torch.randn(B * N, H * HD, generator=g)).to(DEV)
+    do = bf(torch.randn(B * N, H * HD, generator=g)).to(DEV)
+    lse = (torch.randn(B, H, N, generator=g) * 5).to(DEV)
+    buf = torch.full((2 * B * H * N + 512,), 7.0, device=DEV)
+    rc = buf[256:256 + 2 * B * H * N]
+    assert _lib.load().octmae_attn_bwd_rowconst(o.data_ptr(), do.data_ptr(), lse.data_ptr(), rc.data_ptr(), B, N, H, HD,
+                                                torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    assert bool((buf[:256] == 7.0).all()) and bool((buf[-256:] == 7.0).all())
+    rc = rc.view(2, B, H, N)
+    assert torch.equal(rc[0], -lse * 1.4426950408889634)
+    p = (do.double() * o.double()).view(B, N, H, HD)
+    want, mag = -p.sum(-1).permute(0, 2, 1), p.abs().sum(-1).permute(0, 2, 1)
+    gam = HD * 2.0 ** -24 / (1 - HD * 2.0 ** -24)
+    ratio = float(((rc[1].double() - want).abs() / (gam * mag)).max())
+    print(f"attn_delta past the cap, HD {HD}: worst |err| / bound {ratio:.3f}")
+    assert ratio <= 1.0
+
+
+def _poison_workspace(B, N, H, HD, k=3):
+    """ops.attn_bwd takes its workspace (dQ sums and the padded row constants) from torch.empty; the caching allocator would hand it the
+    block the call before left behind, correct row constants included.  k NaN-filled tensors of the workspace's size, freed at once:
+    the next torch.empty of that size gets one of them (or fresh memory), so a row constant the kernels do not write comes out as NaN."""
+    from octcubem_amd import _lib
+    numel = _lib.load().octmae_attn_bwd_fused_ws_kib(B, N, H, HD) * 256
+    blocks = [torch.full((numel,), float("nan"), device=DEV) for _ in range(k)]
+    del blocks
+
+
+@pytest.mark.parametrize("HD", [32, 64])
+def test_attention_backward_padded_row_constants_past_the_grid_cap(HD):
+    """The fused backward's row-constant kernels (attn_rowconst_pad_kernel, attn_rowconst_from_delta_kernel) give a workgroup one tile
+    of 64 padded query rows on at most 8192 workgroups: B = 2800 samples of N = 65 (three tiles each: 64 rows, one row, the all-padding
+    tile) are 8400 tiles, so the tiles of the samples from 2730 2/3 on are a second trip.  A sample's gradient does not depend on the
+    other samples: the last 100 samples alone (300 tiles, one trip) must give the same bits; and the whole batch stays at the usual
+    distance from fp64.  Every call starts from a workspace full of NaN (_poison_workspace): nothing is inherited from the call before."""
+    B, N, H = 2800, 65, 1
+    assert B * ((N + 63) // 64 + 1) > 8192 and (B - 100) * 3 < 8192
+    g = torch.Generator().manual_seed(HD + 1)
+    qkv = bf(torch.randn(B * N, 3 * H * HD, generator=g)).to(DEV)
+    do = bf(torch.randn(B * N, H * HD, generator=g)).to(DEV)
+    scale = HD ** -0.5
+    o, lse = ops.attn_fwd(qkv, B, N, H, HD, scale)
+    tail = slice((B - 100) * N, B * N)
+    delta = -(do.float() * o.float()).view(B * N, H, HD).sum(-1).contiguous()
+    for name, dl in (("pad", None), ("from_delta", delta)):
+        _poison_workspace(B, N, H, HD)
+        d = ops.attn_bwd(qkv, o, do, lse, B, N, H, HD, scale, fused=True, delta=dl)
+        assert bool(torch.isfinite(d.float()).all()), name
+        _poison_workspace(100, N, H, HD)
+        small = ops.attn_bwd(qkv[tail].contiguous(), o[tail].contiguous(), do[tail].contiguous(), lse[B - 100:].contiguous(), 100, N, H, HD,
+                             scale, fused=True, delta=None if dl is None else dl[tail].contiguous())
+        assert torch.equal(d[tail], small), (name, int((d[tail] != small).any(1).sum()))
+        if dl is None:
+            qd = qkv.double().requires_grad_(True)
+            o_ref, _ = attn_ref(qd, B, N, H, HD)
+            o_ref.backward(do.double())
+            got, ref = d.double().view(B, N, 3, H * HD), qd.grad.view(B, N, 3, H * HD)
+            errs = {k: rel(got[:, :, i], ref[:, :, i]) for i, k in enumerate("qkv")}
+            errs_tail = {k: rel(got[B - 100:, :, i], ref[B - 100:, :, i]) for i, k in enumerate("qkv")}
+            print(f"attention backward past the row-constant cap hd{HD}: {errs}, second-trip samples {errs_tail}")
+            assert max(errs.values()) < 1.5e-2 and max(errs_tail.values()) < 1.5e-2, (errs, errs_tail)
+
+
 @pytest.mark.parametrize("B,N,H,HD", [(2, 1281, 16, 64), (1, 5121, 16, 32), (3, 300, 8, 32), (2, 257, 4, 64), (1, 1000, 12, 64)])
 def test_proj_dgrad_produces_the_attention_delta(B, N, H, HD, tile_variant):
     """octmae_linear_dgrad_delta: the proj dgrad GEMM whose epilogue also writes delta = -rowsum_head(dO * O) (fp32 [B N][H]) from

@@ -101,6 +101,46 @@ def test_cast_rowscale_rounds_to_nearest_even_into_inf():
     assert _straddles(got)
 
 
+def _guarded_lp(n, guard=4096):
+    """(whole buffer, the n 16-bit elements in its middle): guard zones of a sentinel on either side"""
+    buf = torch.full((n + 2 * guard,), 0x5A5A, dtype=torch.int16, device=DEV)
+    return buf, buf[guard:guard + n].view(LP)
+
+
+def _guards_intact(buf, n, guard=4096):
+    return bool((buf[:guard] == 0x5A5A).all()) and bool((buf[guard + n:] == 0x5A5A).all())
+
+
+def test_cast_past_the_grid_cap_takes_the_unrolled_loop_and_both_tails():
+    """octmae_cast_f32_bf16 runs at most 512 workgroups of 256 lanes, 8 elements per lane and trip.  n / 8 = 7 x 512 x 256 + 77: the 77
+    lowest lanes take two trips of the loop that keeps four loads in flight and none of the single-load loop, every other lane one
+    trip of the first and three of the second; 5 elements after the last whole 8 are the scalar tail."""
+    lanes = 512 * 256
+    n = 8 * (4 * lanes + 3 * lanes + 77) + 5
+    x = _tiled(n, torch.Generator().manual_seed(3)).to(DEV)
+    buf, out = _guarded_lp(n)
+    call("octmae_cast_f32_bf16", x.data_ptr(), out.data_ptr(), n, torch.cuda.current_stream().cuda_stream)
+    exp = x.to(LP)
+    assert _guards_intact(buf, n)
+    assert bits_equal(out, exp), _show(out, exp)
+    assert bits_equal(ops.cast_bf16(x), exp)
+
+
+def test_cast_rowscale_past_the_grid_cap():
+    """octmae_cast_rowscale_f32_bf16: at most 4096 workgroups of 256 lanes, one 8-element chunk per lane and trip.  Rows of one chunk
+    (D = 8), 300 more rows than lanes: a second trip for one workgroup and 44 lanes of the next, with another row's scale."""
+    R, D, per = 4096 * 256 + 300, 8, 4
+    g = torch.Generator().manual_seed(4)
+    x = _tiled(R * D, g).view(R, D).to(DEV)
+    sc = (torch.rand(R // per, generator=g) + 0.5).to(DEV)
+    buf, out = _guarded_lp(R * D)
+    call("octmae_cast_rowscale_f32_bf16", x.data_ptr(), sc.data_ptr(), out.data_ptr(), R, D, per, torch.cuda.current_stream().cuda_stream)
+    exp = (x * sc.repeat_interleave(per).unsqueeze(1)).to(LP)
+    assert _guards_intact(buf, R * D)
+    assert bits_equal(out.view(R, D), exp), _show(out.view(R, D), exp)
+    assert bits_equal(ops.cast_bf16_rowscale(x, sc, per), exp)
+
+
 def test_gather_rows_cast_rounds_to_nearest_even_into_inf():
     e = edge_values()
     B, rows, D, n = 3, 9, 64, 6

@@ -81,6 +81,25 @@ def test_elem_mode_uses_the_partners_original_values(shape):
     assert torch.equal(got[4][~inside], x[4][~inside]) and torch.equal(got[4][inside], x[1][inside])
 
 
+def test_samples_longer_than_the_grid_cap():
+    """A pair gets ceil(4096 / pairs) workgroups of 256 threads at the most and a thread strides on over its sample's 16-byte lines (the
+    full pass) or over the lines of its box rows (the box pass).  Two pairs -> 524 288 threads each; samples of 1450 x 1452 = 2 105 400
+    floats are 526 350 lines (2062 on a second trip), the whole-plane box 1450 rows x 364 lines = 527 800 and the box that leaves a rim
+    1448 x 363 = 525 624.  Pair (0, 3) mixes both ways, pair (1, 2) cuts both ways with those two boxes."""
+    shape = (4, 1, 1450, 1452)
+    H, W = shape[-2:]
+    threads = 256 * (4096 // 2)
+    assert (H * W + 3) // 4 > threads and H * ((W + 3) // 4 + 1) > threads and (H - 2) * ((W - 4 + 3) // 4 + 1) > threads
+    x = batch(shape, 9)
+    lam = np.array([0.3, 0.5, 0.5, 0.7123456789012345], dtype=np.float32)
+    cut = [False, True, True, False]
+    boxes = [(0, 0, 0, 0), (0, H, 0, W), (2, H, 1, W - 3), (0, 0, 0, 0)]
+    want = R.mix_elem(x.clone(), lam, cut, boxes)
+    got = launch(x, *elem_tables(lam, cut, boxes))
+    assert torch.equal(got, want), int((got != want).sum())
+    assert torch.equal(got[1], x[2]) and not torch.equal(got[2], x[1]) and not torch.equal(got[0], x[0])
+
+
 def test_elem_mode_two_different_overlapping_boxes_in_one_pair():
     """Both members of a pair cut, each with its own box: where the boxes overlap the two samples swap, elsewhere each takes the other's
     original.  Pair (1, 2): one side cuts, the other is untouched."""

@@ -129,6 +129,37 @@ def test_compose_draws_non_finite_values_as_zero(golden_dir):
     assert torch.equal(got[:, 3][ok3], want[:, 3][ok3])
 
 
+def check_past_the_grid_cap(denorm):
+    """compose_kernel: one wave per token on at most 4096 workgroups of 4 (16 384 tokens).  p = 4, u = 1 (16 values per token) on two
+    frames of 516 x 516 is 33 282 tokens: a third trip for 514 of them (128 workgroups and two waves).  The same comparisons as the small
+    cases: every voxel equal without denorm, the fp64 criteria of check_denorm with it."""
+    B, T, H, W, u, p = 1, 2, 516, 516, 1, 4
+    L = (T // u) * (H // p) * (W // p)
+    assert L > 2 * 4096 * 4 and (L - 2 * 4096 * 4) % 4 != 0
+    g = torch.Generator().manual_seed(13)
+    imgs = torch.randn(B, 1, T, H, W, generator=g)
+    pred = torch.randn(B, L, u * p * p, generator=g)
+    mask = (torch.rand(B, L, generator=g) > 0.3).float()
+    got = compose(pred, imgs, mask, None, u, p, denorm=denorm)
+    if not denorm:
+        want = R.panels(pred, imgs, mask, None, u, p)
+        assert torch.equal(got, want), f"{int((got != want).sum())} voxels differ"
+        return
+    want, raw = R.panels_denorm(pred, imgs, mask, None, u, p)
+    exact = R.exact_class(raw)
+    removed = R.unpatchify(mask.unsqueeze(-1).repeat(1, 1, pred.shape[-1]), T, H, W, p, u)[:, 0] != 0
+    assert float(exact.double().mean()) >= 0.95
+    assert int((got - want).abs().max()) <= 1
+    assert torch.equal(got[:, :2], want[:, :2])
+    assert torch.equal(got[:, 2][exact], want[:, 2][exact])
+    assert torch.equal(got[:, 3][exact | ~removed], want[:, 3][exact | ~removed])
+
+
+@pytest.mark.parametrize("denorm", (False, True))
+def test_compose_tokens_past_the_grid_cap(denorm):
+    check_past_the_grid_cap(denorm)
+
+
 @pytest.mark.parametrize("name", ("a", "d"))
 def test_compose_denorm_against_fp64(name, golden_dir):
     check_denorm(name, golden_dir)
@@ -235,4 +266,4 @@ def test_half_build_runs_the_same_compose_kernel():
     assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
     res = json.load(open(_CHILD["out"]))
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
-    assert res["passed"] == [*DIRECT, "denorm a", "denorm d"], res
+    assert res["passed"] == [*DIRECT, "denorm a", "denorm d", "past the cap", "past the cap denorm"], res

@@ -3,7 +3,8 @@ get_metrics_3modalities / get_corrected_metrics / evaluate on top of it.
 
 R / C / K below are the kernel's RR_ROWS / RR_COLS / RR_K (64 rows of a per workgroup, 64 columns per tile, 32 k per LDS step; an MFMA
 step is 2 k).  Sizes: n, m from {1, 2, R-1, R, R+1, C-1, C+1, 2C+3} = {1, 2, 63, 64, 65, 131}, d from {1, 2, 3, K-1, K, K+1, 512, 515},
-paired (not the full product) so that the largest n m d = 131 * 131 * 515 keeps the numpy references well under a second.
+paired (not the full product) so that the largest n m d = 131 * 131 * 515 keeps the numpy references well under a second.  On top of
+them the three shapes of retrieval_ref.TRIP_SHAPES, where a workgroup walks more than one column tile (d of 2 or 3).
 
 Families.  ``dyadic``: entries in {-2 .. 2} / 4, every product a multiple of 1/16 and every partial sum below 2^10, so the f32 chain is
 exact and the expected counts are integer numpy arithmetic -- all four outputs EQUAL; ties everywhere, which pins the tie rule, keep and
@@ -41,6 +42,10 @@ SIZES = ((1, 1, 1), (2, 2, 2), (63, 63, 3), (64, 64, 31), (65, 65, 32), (131, 13
 assert {s[0] for s in SIZES} | {s[1] for s in SIZES} == {1, 2, RR - 1, RR, RR + 1, CC - 1, CC + 1, 2 * CC + 3}
 assert {s[2] for s in SIZES} == {1, 2, 3, KK - 1, KK, KK + 1, 512, 515}
 DYADIC_CASES = [(n, m, d, full) for (n, m, d) in SIZES for full in (False, True) if full or n == m]
+# ... and R.TRIP_SHAPES, appended: a workgroup walks several column tiles there (it keeps its four counters and rewrites flg / cgs per
+# tile): split 1024 of 1025 tiles, 22 of 47, and 1 of 3 under 1024 row blocks.  full = a target table, keep and the groups, each time.
+TRIP_CASES = [(n, m, d, full) for (n, m, d) in R.TRIP_SHAPES for full in (False, True) if full or n == m]
+DYADIC_CASES += TRIP_CASES
 
 
 def dev(x):
@@ -52,6 +57,9 @@ def side_inputs(rng, n, m, full):
     if not full:
         return None, None, None, None
     target = rng.integers(0, m, size=n).astype(np.int32)
+    if n > 8 * m and m > 8:                  # far more rows than columns: targets from half of the columns, or every column is one
+        cols = rng.permutation(m)[:m // 2]
+        target = cols[rng.integers(0, len(cols), size=n)].astype(np.int32)
     keep = (rng.random(m) < 0.7).astype(np.uint8)
     keep[target] = 1
     return target, keep, rng.integers(0, 4, size=n).astype(np.int32), rng.integers(0, 4, size=m).astype(np.int32)
@@ -90,6 +98,12 @@ def test_dyadic_counts_are_equal(n, m, d, full):
 def test_dyadic_cases_have_ties_and_groups():
     a, b, target, keep, rg, cg, want = dyadic_case(131, 131, 515, True)
     assert (want[:, 1] > 0).any() and (want[:, 0] > 0).any() and (want[:, 3] > want[:, 2]).any() and (want[:, 2] > 0).any() and not keep.all()
+    for n, m, d in R.TRIP_SHAPES:              # ... and counts that no single tile can hold: every tile's share has to arrive
+        _, _, _, keep, _, _, want = dyadic_case(n, m, d, True)
+        assert (want[:, 1] > 0).any() and (want[:, 0] > 0).any() and (want[:, 3] > want[:, 2]).any() and (want[:, 2] > 0).any()
+        tiles = [keep[j0:j0 + CC] for j0 in range(0, m, CC)]
+        assert not keep.all() and sum(0 < t.sum() < len(t) for t in tiles) >= min(len(tiles), 3) - 1      # the keep bits differ from tile to tile
+        assert m < 1000 or want[:, 3].min() > CC
 
 
 @pytest.mark.parametrize("n,m,d", ((65, 65, 3), (64, 131, 33), (131, 63, 512)))
@@ -150,13 +164,15 @@ def test_bit_copies_of_the_target_row_tie(n, m, d):
     assert (got[:, 0] <= hi).all()                                            # a twin is never counted as greater
 
 
-CONTINUOUS = ((63, 63, 31, 0.25), (131, 131, 32, 0.25), (65, 131, 33, 0.25), (131, 131, 512, 0.15), (64, 131, 515, 0.15))
+CONTINUOUS = ((63, 63, 31, 0.25), (131, 131, 32, 0.25), (65, 131, 33, 0.25), (131, 131, 512, 0.15), (64, 131, 515, 0.15)) + \
+    (R.TRIP_SHAPES[1] + (20.0,),)
 
 
 @pytest.mark.parametrize("n,m,d,c", CONTINUOUS)
 def test_continuous_positions_lie_within_the_f32_bound(n, m, d, c):
     """b = normalize(c a + unit noise); c = 0.25, lowered to 0.15 at d >= 512 where 0.25 gives R@1 above 0.9 (float64 on the CPU: R@1
-    0.18 / 0.09 / 0.11 at d = 31 / 32 / 33, 0.72 / 0.80 at 512 / 515; rows with lo != hi: none, and 1.6 % at d = 515)"""
+    0.18 / 0.09 / 0.11 at d = 31 / 32 / 33, 0.72 / 0.80 at 512 / 515; rows with lo != hi: none, and 1.6 % at d = 515).  The trip shape
+    3001 x 3001, d = 3 -- 3001 points on a sphere, the nearest about 0.036 rad away -- takes c = 20 (R@1 0.35, lo != hi in 0.07 % of the rows)"""
     rng = np.random.default_rng([n, m, d, 4])
     a = normalize(rng.standard_normal((n, d)))
     target = rng.permutation(m)[:n].astype(np.int32)

@@ -90,6 +90,35 @@ def test_patch_scatter_is_bit_exact(C, tp, p):
     assert check_scatter(C, tp, p) == 20
 
 
+def check_scatter_past_the_grid_cap():
+    """Both walks of octmae_patch_scatter run on at most 8192 workgroups of 256 threads.  p = 8, tp = 1, C = 1 (8 chunks per token),
+    B = 3 samples of 22 x 512 x 512 voxels with 87 400 of their 90 112 tokens kept: 2 097 600 chunks, 448 past the cap (one workgroup and
+    192 threads of the next make a second trip), and a zero fill of 4 325 376 float4s (a third trip for 131 072 of them)."""
+    B, C, T, H, W, tp, p, nkeep = 3, 1, 22, 512, 512, 1, 8, 87400
+    L = (T // tp) * (H // p) * (W // p)
+    assert 256 < B * nkeep * (C * tp * p * p // 8) - 8192 * 256 < 512 and B * C * T * H * W // 4 > 2 * 8192 * 256 and nkeep < L
+    g = torch.Generator().manual_seed(11)
+    dp = lp_random((B * nkeep, C * tp * p * p), g, ops.BF16)
+    ids = torch.stack([torch.randperm(L, generator=g)[:nkeep] for _ in range(B)])
+    ref = R.scatter_ref(dp.float(), ids, (B, C, T, H, W), tp, p)
+    n = B * C * T * H * W
+    buf = torch.full((n + 512,), float("nan"), device=DEV)
+    buf[:256] = 7.0
+    buf[-256:] = 7.0
+    out = buf[256:256 + n].view(B, C, T, H, W)
+    dpd, idd = dp.to(DEV), ids.to(DEV).contiguous()
+    _lib.call("octmae_patch_scatter", dpd.data_ptr(), idd.data_ptr(), 1, out.data_ptr(), B, C, T, H, W, tp, p, nkeep, ops._stream())
+    torch.cuda.synchronize()
+    assert bool((buf[:256] == 7.0).all()) and bool((buf[-256:] == 7.0).all())
+    assert same_bits(out, ref)
+    assert int((bits(out) == 0).sum()) >= (L - nkeep) * B * C * tp * p * p
+    return 1
+
+
+def test_patch_scatter_and_its_zero_fill_past_the_grid_cap():
+    assert check_scatter_past_the_grid_cap() == 1
+
+
 def test_patch_scatter_refuses_wrong_tensors():
     dp = torch.zeros(4, 768, dtype=ops.BF16, device=DEV)
     with pytest.raises(RuntimeError):
@@ -401,8 +430,22 @@ def test_switch_gives_bit_identical_input_gradients_for_the_op_by_op_blocks():
 @pytest.mark.parametrize("L", [1, 5, 257])
 @pytest.mark.parametrize("npre", [0, 1])
 def test_cam_weights_and_tokens_within_the_summation_bound(C, L, npre):
+    check_cam(3, C, L, npre)
+
+
+# cam_tokens_kernel: one wave per token row on at most 8192 workgroups of 4 (32 768 rows); cam_weights_fold_kernel: one thread per four
+# columns of a sample on at most 4096 workgroups of 256 (1 048 576).  (3, 4, 10925): 32 775 rows, 7 of them a wave's second, and 64 row
+# splits of 171 rows to fold; (65535, 68, 1): the largest batch the entry point takes, 1 114 095 column quads (65 519 a thread's second)
+# and 65 535 token rows (a second trip for all but one wave).
+@pytest.mark.parametrize("B,C,L,npre", [(3, 4, 10925, 1), (65535, 68, 1, 1)])
+def test_cam_weights_and_tokens_past_the_grid_caps(B, C, L, npre):
+    assert B * L > 8192 * 4 and (B * L) % (8192 * 4) % 4 != 0
+    assert B < 100 or B * (C // 4) > 4096 * 256
+    check_cam(B, C, L, npre)
+
+
+def check_cam(B, C, L, npre):
     g = torch.Generator().manual_seed(1000 * npre + 10 * L + C)
-    B = 3
     A = torch.randn(B, npre + L, C, generator=g)
     G = torch.randn(B, npre + L, C, generator=g)
     A[0], G[0] = A[0].abs(), G[0].abs()          # sample 0: every product is positive, every row of cam is well above 0
@@ -453,6 +496,42 @@ def test_heatmap_within_one_grey_level_of_float64(name):
         for b in range(m.shape[0]):
             assert torch.equal(ops.heatmap(m[b:b + 1].to(DEV), size)[0], out[b])
     assert torch.equal(saliency.heatmap(m.to(DEV), size), out)
+
+
+def test_heatmap_past_the_grid_cap_equals_the_samples_alone():
+    """heatmap_kernel: one thread per four voxels of a row on at most 16 384 workgroups of 256 (4 194 304).  Two samples of
+    33 x 255 x 1004 voxels are 4 224 330 such threads, 30 026 of them (117 workgroups and 74 threads) on a second trip, where they write
+    the end of sample 1.  Checked as the small cases are -- every byte within one grey level of the float64 restatement, at most 1 % of
+    them off it, counted over the whole volume and over the second-trip bytes alone -- and each sample alone (one trip) must give the
+    same bytes.  The largest voxel of each sample sits at the interior voxel (1, 2, 3) of the 3 x 5 x 7 map, as R.heat_input puts it."""
+    size = (33, 255, 1004)
+    n1 = size[0] * size[1] * size[2] // 4
+    assert n1 < 16384 * 256 < 2 * n1 and (2 * n1 - 16384 * 256) % 256 != 0
+    m = torch.randn(2, 3, 5, 7, generator=torch.Generator().manual_seed(12))
+    m[1] = m[1] * 40.0 - 3.0
+    for b in range(2):                         # the maximum to an interior voxel: no plateau of undecidable 254 / 255 bytes
+        flat = m[b].reshape(-1)
+        i, j = int(flat.argmax()), (1 * 5 + 2) * 7 + 3
+        vi, vj = float(flat[i]), float(flat[j])
+        flat[i], flat[j] = vj, vi
+    md = m.to(DEV)
+    n = 2 * 4 * n1
+    buf = torch.full((n + 512,), 0x5A, dtype=torch.uint8, device=DEV)
+    out = buf[256:256 + n].view(2, *size)
+    mnmx = torch.empty(4, device=DEV)
+    _lib.call("octmae_heatmap", md.data_ptr(), mnmx.data_ptr(), out.data_ptr(), 2, 3, 5, 7, *size, ops._stream())
+    torch.cuda.synchronize()
+    assert bool((buf[:256] == 0x5A).all()) and bool((buf[-256:] == 0x5A).all())
+    assert torch.equal(ops.heatmap(md, size), out)
+    for b in range(2):
+        alone = ops.heatmap(md[b:b + 1].contiguous(), size)[0]
+        assert torch.equal(alone, out[b]), b
+        assert int(alone.max()) in (254, 255) and int(alone.min()) < 64
+    d = (out.cpu().int() - R.heat_ref64(m, size).int()).abs().view(-1)
+    second = d[4 * 16384 * 256:]               # the bytes the second trip writes
+    print(f"heatmap past the cap: {float((d != 0).double().mean()):.4%} of the bytes off the float64 restatement, max {int(d.max())}; "
+          f"second trip {float((second != 0).double().mean()):.4%}")
+    assert int(d.max()) <= 1 and float((d != 0).double().mean()) <= 0.01 and float((second != 0).double().mean()) <= 0.01
 
 
 def test_heatmap_of_a_constant_map_is_zero_and_wrong_sizes_are_refused():
@@ -653,7 +732,7 @@ def test_half_build_scatter_patch_embed_and_model_parity():
     assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
     res = json.load(open(_CHILD["out"]))
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
-    assert res["scatter_cases"] == 20 * len(SCATTER_GEOM) and len(res["patch_embed"]) == 4 and max(res["patch_embed"].values()) <= 1.0
+    assert res["scatter_cases"] == 20 * len(SCATTER_GEOM) + 1 and len(res["patch_embed"]) == 4 and max(res["patch_embed"].values()) <= 1.0
     for variant in PARITY_BOUND_F16:
         print(f"input gradient [{variant}, half build]: rel L2 {res['parity'][variant]:.3e}")
     for variant, bound in PARITY_BOUND_F16.items():

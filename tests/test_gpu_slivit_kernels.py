@@ -11,7 +11,8 @@ they catch), no measured constant in any of them:
   * layer scale: forward and dbranch bit-equal to torch's fp32 mul / add and one cast; the gamma gradient with n = M + RP + G + 2
     (rows, the RP row parts a workgroup folds, the G partials, the accumulation).
 Shapes: maps narrower than the halo, equal to the filter, one past the 8 x 16 tile in each direction, several tiles; channel counts
-below a wave's 64 lanes x 4, a non-power-of-two, and a tail after the 32-channel blocks.  The same checks run on the half-operand build
+below a wave's 64 lanes x 4, a non-power-of-two, and a tail after the 32-channel blocks; and the shapes of slivit_ref.DW_TRIP_SHAPES /
+LS_TRIP_SHAPE, where the workgroups of the weight gradient and of the layer-scale backward outnumber their cap.  The same checks run on the half-operand build
 in a child process (tests/slivit_f16_worker.py)."""
 import ctypes
 import json
@@ -76,10 +77,10 @@ def _wgrad_ref64(dz, x):
     return gw, mag, d.sum(dim=(0, 2, 3)), d.abs().sum(dim=(0, 2, 3))
 
 
-def check_dwconv(H, W, report=None):
+def check_dwconv(H, W, report=None, cs=CS, bs=BS):
     st = ops._stream()
-    for C in CS:
-        for B in BS:
+    for C in cs:
+        for B in bs:
             x, wt, bias, dz, dres, gw0, gb0 = _problem(B, H, W, C, seed=1000 * H + 10 * W + C + B)
             n = x.numel()
             xd, wd, bd, dzd, dresd = (t.to(DEV) for t in (x, wt, bias, dz, dres))
@@ -130,10 +131,10 @@ def check_dwconv(H, W, report=None):
                 report[tag] = (ratio, ratio_i, rw, rb_)
 
 
-def check_layer_scale(report=None):
+def check_layer_scale(report=None, ms=(1, 5, 257, 1031), cs=CS + [1032]):
     st = ops._stream()
-    for M in (1, 5, 257, 1031):
-        for C in CS + [1032]:
+    for M in ms:
+        for C in cs:
             g = torch.Generator().manual_seed(77 + M + C)
             res, branch, dout = (torch.randn((M, C), generator=g) for _ in range(3))
             gamma, gg0 = torch.rand((C,), generator=g) + 0.5, torch.randn((C,), generator=g)
@@ -219,11 +220,61 @@ def check_argument_checks():
         ops.layer_scale_fwd(x.view(-1, 16), x.view(-1, 16)[:3].contiguous(), bias)
 
 
+def check_dwconv_trips(shape, report=None):
+    """A shape of R.DW_TRIP_SHAPES: by the library's own workspace answer G < ntiles, so workgroups of the weight gradient walk a second
+    tile with their accumulators kept and both LDS images rewritten; then every check of check_dwconv at that shape."""
+    B, H, W, C = shape
+    ntiles, cblocks, G = R.dw_wgrad_plan(B, H, W, C)
+    nws = _lib.load().octmae_dwconv7_bwd_weight_ws_floats(B, H, W, C)
+    assert nws == 50 * C * G and nws // (50 * C) < ntiles, f"{shape}: {ntiles} tiles, workspace for {nws / (50 * C)} workgroups"
+    check_dwconv(H, W, report, cs=[C], bs=[B])
+
+
+def check_layer_scale_trips(report=None):
+    """R.LS_TRIP_SHAPE: the small-C form (RP = 128 rows per workgroup, folded through s_red) with M > G RP by the library's own answer"""
+    M, C = R.LS_TRIP_SHAPE
+    CVB, RP, ncb, G = R.ls_bwd_plan(M, C)
+    nws = _lib.load().octmae_layer_scale_bwd_ws_floats(M, C)
+    assert nws == G * C and RP == 128 and M > (nws // C) * RP, f"M {M}: workspace for {nws / C} workgroups of {RP} rows"
+    check_layer_scale(report, ms=(M,), cs=[C])
+    check_layer_scale_exact(M, C, report)
+
+
+def check_layer_scale_exact(M, C, report=None):
+    """The gamma gradient on R.ls_dyadic_problem: every fp32 partial sum is exact, so the result EQUALS the float64 one -- each trip of
+    each workgroup, each row part folded through s_red and each of the G partials is in it or the comparison fails (the bound of
+    check_layer_scale, gamma_n of 260 000 terms, is thousands of times wider than one trip's share; tests/test_cpu_slivit.py drops trips
+    and parts from the restated walk to show what this equality sees)."""
+    st = ops._stream()
+    dout, branch, gamma, gg0 = R.ls_dyadic_problem(M, C, seed=5)
+    want = gg0.double() + (dout.double() * branch.double()).sum(0)
+    assert torch.equal(want.float().double(), want)
+    assert torch.equal(gg0.double() + R.ls_bwd_walk_sum(dout, branch), want)
+    brd, doutd, gmd = (t.to(DEV) for t in (branch, dout, gamma))
+    nws = _lib.load().octmae_layer_scale_bwd_ws_floats(M, C)
+    dbuf, db = _guarded(M * C, ops.BF16)
+    ggbuf, gg = _guarded(C)
+    wsbuf, ws = _guarded(nws)
+    gg.copy_(gg0)
+    _lib.call("octmae_layer_scale_bwd", doutd.data_ptr(), brd.data_ptr(), gmd.data_ptr(), db.data_ptr(), gg.data_ptr(), ws.data_ptr(), M, C, st)
+    assert _guards_intact(dbuf, M * C) and _guards_intact(ggbuf, C) and _guards_intact(wsbuf, nws)
+    assert torch.equal(gg.cpu().double(), want), f"layer_scale_bwd M{M} C{C}: the exact gamma gradient differs by {(gg.cpu().double() - want).tolist()}"
+    assert torch.equal(db.cpu().view(M, C), (gamma * dout).to(ops.BF16))
+    # the workspace holds the G partials: each is its workgroup's exact share
+    part = ws.cpu().double().view(nws // C, C)
+    assert torch.equal(part.sum(0), want - gg0.double())
+    if report is not None:
+        report[f"M{M} C{C} exact"] = 0.0
+
+
 def run_all_checks():
     rep = {}
     for H, W in HW:
         check_dwconv(H, W, rep)
+    for shape in R.DW_TRIP_SHAPES:
+        check_dwconv_trips(shape, rep)
     check_layer_scale(rep)
+    check_layer_scale_trips(rep)
     check_argument_checks()
     return rep
 
@@ -235,9 +286,22 @@ def test_dwconv7_forward_and_gradients_per_element(hw):
     print({k: tuple(round(v, 4) for v in r) for k, r in rep.items()})
 
 
+@pytest.mark.parametrize("shape", R.DW_TRIP_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_dwconv7_weight_gradient_past_the_workgroup_cap(shape):
+    rep = {}
+    check_dwconv_trips(shape, rep)
+    print({k: tuple(round(v, 4) for v in r) for k, r in rep.items()})
+
+
 def test_layer_scale_forward_and_backward():
     rep = {}
     check_layer_scale(rep)
+    print({k: round(v, 4) for k, v in rep.items()})
+
+
+def test_layer_scale_backward_past_the_workgroup_cap_with_folded_row_parts():
+    rep = {}
+    check_layer_scale_trips(rep)
     print({k: round(v, 4) for k, v in rep.items()})
 
 

@@ -44,12 +44,19 @@ def _perm_prefix(B, L, n, g, dtype=torch.int64):
 
 
 # ------------------------------------------------------------------------------------------------ encoder assembly
-@pytest.mark.parametrize("B,nkeep,D", [(2, 1280, 1024), (3, 10, 64), (128, 80, 512), (1, 1, 4)])
+# The grid of the four walks below is capped at 8192 workgroups of 256 threads (2 097 152 items) and a thread strides on from there: the
+# last shape of each list is the narrowest row (8 or 64 elements) with 259 to 448 items past the cap -- a second trip for one whole
+# workgroup and a part of the next (docs/GRID_CAPS.md).
+GRID_CAP_ITEMS = 8192 * 256
+
+
+@pytest.mark.parametrize("B,nkeep,D", [(2, 1280, 1024), (3, 10, 64), (128, 80, 512), (1, 1, 4), (2, 524352, 8)])
 def test_enc_assemble_equals_cat_and_gather(B, nkeep, D):
     """octmae_enc_assemble: x[b, 0] = cls + pos_cls, x[b, 1 + i] = float(tok[b, i]) + pos[ids_keep[b, i]] -- one 16-bit -> fp32
     widening and one fp32 add: torch.equal."""
     g = torch.Generator().manual_seed(B + nkeep + D)
-    L = 4 * nkeep
+    L = 4 * nkeep if nkeep < 100000 else nkeep + 5
+    assert nkeep < 100000 or 256 < B * (nkeep + 1) * (D // 4) - GRID_CAP_ITEMS < 512
     tok = torch.randn(B * nkeep, D, generator=g).to(BF16).to(DEV)
     pos = torch.randn(L, D, generator=g).to(DEV)
     cls = torch.randn(D, generator=g).to(DEV)
@@ -65,11 +72,12 @@ def test_enc_assemble_equals_cat_and_gather(B, nkeep, D):
 
 # ------------------------------------------------------------------------------------------------ decoder assembly
 @pytest.mark.parametrize("emb_has_cls", [0, 1])
-@pytest.mark.parametrize("B,nkeep,L,D", [(2, 1280, 5120, 512), (3, 10, 40, 64), (5, 17, 17, 128), (2, 49, 196, 512)])
+@pytest.mark.parametrize("B,nkeep,L,D", [(2, 1280, 5120, 512), (3, 10, 40, 64), (5, 17, 17, 128), (2, 49, 196, 512), (2, 131088, 524352, 8)])
 def test_dec_assemble_equals_gather_mask_token_and_dpos(B, nkeep, L, D, emb_has_cls):
     """octmae_dec_assemble: x[b, 1 + j] = (emb[b, r] if r = ids_restore[b, j] < nkeep else mask_token) + dpos[j]; the cls row is
     dcls + dpos_cls or, with emb_has_cls = 1 (the 2-D MAE: emb carries 1 + nkeep rows per sample, dcls = NULL), emb[b, 0] + dpos_cls."""
     g = torch.Generator().manual_seed(B + nkeep + L + D)
+    assert L < 100000 or 256 < B * (L + 1) * (D // 4) - GRID_CAP_ITEMS < 512
     erows = nkeep + emb_has_cls
     emb = torch.randn(B * erows, D, generator=g).to(BF16).to(DEV)           # every row distinct
     mask_token = torch.randn(D, generator=g).to(DEV)
@@ -90,12 +98,13 @@ def test_dec_assemble_equals_gather_mask_token_and_dpos(B, nkeep, L, D, emb_has_
 
 # ------------------------------------------------------------------------------------------------ patch gather
 @pytest.mark.parametrize("B,C,T,H,W,tp,p,nkeep", [(2, 3, 1, 224, 224, 1, 16, 49), (3, 3, 6, 64, 64, 3, 16, 8),
-                                                  (1, 1, 60, 256, 256, 3, 16, 1280)])
+                                                  (1, 1, 60, 256, 256, 3, 16, 1280), (3, 1, 22, 512, 512, 1, 8, 87400)])
 def test_patch_gather_int64_and_int32_ids(B, C, T, H, W, tp, p, nkeep):
     """octmae_patch_gather with ids: out[b * nkeep + i][(c, u, py, px)] = imgs[b][c][t tp + u][hy p + py][wx p + px] for token
     ids[b][i] -> (t, hy, wx), rounded to 16 bits.  int64 ids (ids_is_i64 = 1) and int32 ids (0) agree bit for bit with each other
     and with the permute-built expectation; C = 3 is the RGB 2-D MAE's order."""
     g = torch.Generator().manual_seed(C * T + H)
+    assert nkeep < 80000 or 256 < B * nkeep * (C * tp * p * p // 8) - GRID_CAP_ITEMS < 512
     imgs = torch.rand(B, C, T, H, W, generator=g).to(DEV)
     gt, gh, gw = T // tp, H // p, W // p
     L = gt * gh * gw
@@ -114,11 +123,12 @@ def test_patch_gather_int64_and_int32_ids(B, C, T, H, W, tp, p, nkeep):
 
 
 # ------------------------------------------------------------------------------------------------ row gather + cast
-@pytest.mark.parametrize("B,n,src_rows,D", [(2, 1280, 5121, 512), (3, 10, 11, 64), (2, 1280, 1281, 1024), (1, 1, 2, 8)])
+@pytest.mark.parametrize("B,n,src_rows,D", [(2, 1280, 5121, 512), (3, 10, 11, 64), (2, 1280, 1281, 1024), (1, 1, 2, 8), (3, 699137, 699140, 8)])
 def test_gather_rows_cast_identity_and_permutation(B, n, src_rows, D):
     """octmae_gather_rows_cast: out[b n + i] = 16-bit(src[b][1 + ids[b][i]]); ids = NULL is the identity (the encoder assembly's
     backward), ids a permutation prefix the decoder assembly's."""
     g = torch.Generator().manual_seed(B + n + D)
+    assert n < 100000 or 256 < B * n * (D // 8) - GRID_CAP_ITEMS < 512
     src = torch.randn(B, src_rows, D, generator=g).to(DEV)
     ids = _perm_prefix(B, src_rows - 1, n, g).to(DEV)
     for use_ids in (None, ids):
@@ -141,11 +151,13 @@ def _ulp(ref: torch.Tensor) -> torch.Tensor:
 
 @pytest.mark.parametrize("select_frames", [False, True])
 @pytest.mark.parametrize("norm_pix", [0, 1])
-@pytest.mark.parametrize("B,C,T,S,tp", [(2, 1, 12, 32, 3), (2, 3, 12, 32, 3), (1, 1, 60, 256, 3)])
+@pytest.mark.parametrize("B,C,T,S,tp", [(2, 1, 12, 32, 3), (2, 3, 12, 32, 3), (1, 1, 60, 256, 3), (1, 1, 195, 256, 3)])
 def test_mse_fwd_bwd_per_token_and_per_element(B, C, T, S, tp, norm_pix, select_frames):
     """octmae_mse_fwd / octmae_mse_bwd against oracle/mae3d_ref.py::forward_loss in float64: C = 1 (16-byte image reads) and C = 3
     (the scalar gather of the RGB 2-D MAE), with and without norm_pix_loss, with frame_idx = NULL and with a strictly increasing
-    non-identity int32 frame selection (pred_t_dim < T); the last shape is the ViT-L one (p = 16, u = 3, 256 x 256, T = 60)."""
+    non-identity int32 frame selection (pred_t_dim < T); the third shape is the ViT-L one (p = 16, u = 3, 256 x 256, T = 60); the last
+    has 65 x 256 = 16 640 tokens against the 4096 workgroups x 4 waves of either launch: 256 (forward) or 257 (backward, with the cls
+    row) rows are a wave's second."""
     p = 16
     pred_t = T * 2 // 3 if select_frames else T
     cfg = O.MAEConfig(input_size=S, in_chans=C, num_frames=T, t_patch_size=tp, pred_t_dim=pred_t, high_res_input_size=2 * S,
@@ -200,3 +212,37 @@ def test_mse_fwd_bwd_per_token_and_per_element(B, C, T, S, tp, norm_pix, select_
         t32 = O.patchify(im if frame_idx is None else torch.index_select(im, 2, fi.to(DEV)), cfg)
         exp = ((coef * mk).unsqueeze(-1) * (pd[:, 1:] - t32)).to(BF16)
         assert torch.equal(body, exp)
+
+
+# ------------------------------------------------------------------------------------------------ backward of the assemblies, row by row
+def test_assembly_backward_rows_past_the_grid_cap():
+    """octmae_scatter_add_rows and octmae_dec_assemble_bwd give one workgroup per table row l up to 65 535 of them; with L = 65 539 the
+    workgroups 0 .. 3 walk on to a second row and rebuild their LDS list (the keepers / the masked flags) for it.  B = 3: every output
+    element is ((0 + v_0) + v_1) + v_2 over the samples that take part, ascending b -- the same fp32 additions in torch, bit for bit."""
+    B, L, nkeep, D = 3, 65535 + 4, 16385, 4
+    g = torch.Generator().manual_seed(L)
+    ids_restore = torch.argsort(torch.argsort(torch.rand(B, L, generator=g), dim=1), dim=1).contiguous().to(DEV)
+    kept = ids_restore < nkeep
+    assert bool(kept[:, 65535:].any()) and bool((~kept[:, 65535:]).any())          # the second-trip rows have keepers and masked samples
+    src = torch.randn(B, 1 + nkeep, D, generator=g).to(DEV)
+    prior = torch.randn(L, D, generator=g).to(DEV)
+    for accumulate in (0, 1):
+        out = Guarded(L, D, torch.float32)
+        if accumulate:
+            out.out.copy_(prior)
+        call("octmae_scatter_add_rows", src.data_ptr(), ids_restore.data_ptr(), out.ptr(), B, nkeep, L, D, 1 + nkeep, 1, accumulate, _stream())
+        exp = prior.clone() if accumulate else torch.zeros(L, D, device=DEV)
+        for b in range(B):
+            rows = src[b, 1 + ids_restore[b].clamp(max=nkeep - 1)]
+            exp = torch.where(kept[b].unsqueeze(1), exp + rows, exp)
+        assert out.intact(), accumulate
+        assert torch.equal(out.out, exp), (accumulate, int((out.out != exp).any(1).sum()))
+    dx = torch.randn(B, 1 + L, D, generator=g).to(DEV)
+    ddpos, part = Guarded(L, D, torch.float32), Guarded(L, D, torch.float32)
+    call("octmae_dec_assemble_bwd", dx.data_ptr(), ids_restore.data_ptr(), ddpos.ptr(), part.ptr(), B, nkeep, L, D, _stream())
+    e_all, e_msk = torch.zeros(L, D, device=DEV), torch.zeros(L, D, device=DEV)
+    for b in range(B):
+        e_all = e_all + dx[b, 1:]
+        e_msk = torch.where(kept[b].unsqueeze(1), e_msk, e_msk + dx[b, 1:])
+    assert ddpos.intact() and part.intact()
+    assert torch.equal(ddpos.out, e_all) and torch.equal(part.out, e_msk)

@@ -103,6 +103,28 @@ def test_box_is_bit_exact(dt):
         assert got == want, (dt, name, "unaligned", got, want)
 
 
+@pytest.mark.parametrize("dt", ["u8", "f32"])
+@pytest.mark.parametrize("shape", [(1025, 513, 4), (17, 513, 1024)], ids=["narrow", "wide"])
+def test_box_rows_past_the_grid_cap(shape, dt):
+    """box_reduce_kernel: at most 2048 workgroups, each 4 waves x (64 >> lg) rows per pass, lg = log2 of the 16-byte chunks of a row
+    (capped at 6).  Narrow rows (one chunk: 256 rows per workgroup, 524 288 per pass) of a 1025 x 513 stack and wide rows (64 chunks or
+    more: 4 rows per workgroup, 8192 per pass) of a 17 x 513 one leave rows for a second pass that ends inside a workgroup.  The only
+    voxels above zero are one early one and one in a row of the second pass: a pass that is dropped moves the box."""
+    D, H, W = shape
+    rows_per_pass = 2048 * 4 * (64 if W * (1 if dt == "u8" else 4) <= 16 else 1)
+    assert W * (1 if dt == "u8" else 4) <= 16 or W * (1 if dt == "u8" else 4) >= 1024
+    assert rows_per_pass < D * H < 2 * rows_per_pass and (D * H - rows_per_pass) % 4 != 0
+    x = torch.zeros(1, D, H, W, dtype=DTYPES[dt])
+    if dt == "f32":
+        x -= 1.0                                                # a negative background is not foreground
+    x[0, 1, 7, 1] = 1
+    x[0, D - 1, H - 2, W - 2] = 3
+    assert ((D - 1) * H + H - 2) >= rows_per_pass
+    want = list(R.box(x))
+    assert want == [1, D, 7, H - 1, 1, W - 1]
+    assert ops.volume_box(x[0].cuda()).cpu().tolist() == want
+
+
 # ---- the resample ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("flips", FLIPS, ids=lambda f: f"flip{int(f[0])}{int(f[1])}")
 @pytest.mark.parametrize("crop", [False, True], ids=["whole", "box"])
