@@ -54,8 +54,10 @@ extern "C" {
  * 27: octmae_dwconv7_fwd / _bwd_input / _bwd_weight (+ _ws_floats), octmae_layer_scale_fwd / _bwd (+ _ws_floats): the depthwise 7x7
  *     convolution and the layer scale of a ConvNeXt layer (the SLIViT baseline's feature extractor, csrc/convnext.hip).
  * 28: octmae_slab_norm_fwd, octmae_slab_norm_bwd (+ octmae_slabnorm_ws_floats): the LayerNorm over a transposed token slab in front of
- *     the SLIViT head's patch projection (the OCTCube trunk with the SLIViT slice head, csrc/slabnorm.hip). */
-#define OCTMAE_ABI_VERSION 28
+ *     the SLIViT head's patch projection (the OCTCube trunk with the SLIViT slice head, csrc/slabnorm.hip).
+ * 29: octmae_retrieval_topk (+ octmae_retrieval_topk_ws): the k best candidates per query off the tiles of octmae_retrieval_ranks, with a
+ *     strict tie order (top-k cross-modal retrieval of the COEM evaluation, csrc/retrieval_topk.hip). */
+#define OCTMAE_ABI_VERSION 29
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -520,6 +522,31 @@ int octmae_rank_counts_masked(const float* scores, long long score_stride, const
 int octmae_retrieval_ranks(const float* a, long long a_stride, const float* b, long long b_stride, const int* target,
                            const uint8_t* keep, const int* row_group, const int* col_group, int* out, long long n, long long m,
                            int d, void* stream);
+
+/* ---- top-k cross-modal retrieval (csrc/retrieval_topk.hip) -------------------------------------------
+ * retinal-COEM/src/retDisease_eval/evaluate_results_test_train_visualize_all_models_top3_col_aireadi_laterality.py:186-270 forms the
+ * [n][n] logits on the CPU, masks the columns of the query's own patient and takes torch.topk.  This entry point walks the tiles of
+ * octmae_retrieval_ranks and keeps the k best candidates of every row on the chip; nothing of size n m is stored, in `ws` either.
+ *   a, b, s(i, j), keep, row_group, col_group: as octmae_retrieval_ranks (the same bits for the same operands)
+ *   candidates of row i: the columns j < m with keep[j] != 0 (keep given), col_group[j] != row_group[i] (groups given; self-exclusion
+ *           without groups is arange as both) and s(i, j) not NaN; -inf and +inf are ordinary scores
+ *   order   (s1, j1) before (s2, j2) iff s1 > s2 || (s1 == s2 && j1 < j2), IEEE comparisons (-0.0 ties with 0.0): a stable descending
+ *           sort, the order out[i][0] + out[i][1] of octmae_retrieval_ranks implies
+ *   k       1 .. 32
+ *   out_idx int32 [n][k], out_score f32 [n][k], contiguous: the first k candidates of the row in that order and their scores, bit for
+ *           bit; a row with c < k candidates holds idx -1, score -inf in slots c .. k-1 (emptiness is the index, never a score)
+ *   ws      workspace of at least octmae_retrieval_topk_ws(n, m, k) BYTES, 8-byte aligned: the partial lists [split][n][k] of
+ *           (score, index) pairs where the column tiles of a row block are split over several workgroups (small n); the query returns 0
+ *           where no split happens (ws may then be NULL) and -2 for n or m <= 0, m above 2^31 - 1 or k outside 1 .. 32
+ * Deterministic: the order is strict, the partial lists are merged in a fixed order by a second launch, no atomics; two launches give
+ * the same bits.  The library allocates nothing and does not synchronise.  Same code in the two builds of the library.
+ * -2, before any launch and with nothing written: a NULL a / b / out_idx / out_score, n, m or d <= 0, a stride below d, k outside
+ * 1 .. 32, m above 2^31 - 1, more than 2^31 - 1 row blocks of 64, one group pointer without the other, ws NULL or ws_bytes below the
+ * query where it is not 0.  (`long long int`: the query's value is a byte count.) */
+long long int octmae_retrieval_topk_ws(long long n, long long m, int k);
+int octmae_retrieval_topk(const float* a, long long a_stride, const float* b, long long b_stride, const uint8_t* keep,
+                          const int* row_group, const int* col_group, int k, int* out_idx, float* out_score, void* ws,
+                          long long ws_bytes, long long n, long long m, int d, void* stream);
 
 /* ---- contrastive loss of the COEM training step (csrc/cliploss.hip) ---------------------------------
  * retinal-COEM/src/open_clip/loss.py:148-230 (ClipLoss) and :230-385 (ThreeModalityClipLoss) form logit_scale * a @ b.T, its transpose,

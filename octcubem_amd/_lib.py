@@ -41,6 +41,8 @@ SIGNATURES = {
     "octmae_rank_counts": [_vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
     "octmae_rank_counts_masked": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
     "octmae_retrieval_ranks": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _vp],
+    "octmae_retrieval_topk_ws": [_ll, _ll, _i],
+    "octmae_retrieval_topk": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],
     "octmae_clip_loss_ws_floats": [_ll, _ll],
     "octmae_clip_loss_fwd": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],
     "octmae_clip_loss_bwd": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _ll, _ll, _i, _vp],
@@ -114,6 +116,9 @@ SIGNATURES = {
     "octmae_probe_trread": [_vp, _vp, _vp],
 }
 
+# ... except a query whose value is a byte count (long long in the header)
+RESTYPES = {"octmae_retrieval_topk_ws": _ll}
+
 _lib = None
 _on_load = []       # callbacks run once, right after the library has been loaded and bound (ops: operand-type check)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "octmae.h")
@@ -151,7 +156,7 @@ def load():
         except AttributeError as e:  # pragma: no cover
             raise OctmaeError(f"liboctmae.so does not export {name}") from e
         fn.argtypes = argtypes
-        fn.restype = C.c_int
+        fn.restype = RESTYPES.get(name, C.c_int)
     if os.path.exists(HEADER_PATH) and lib.octmae_abi_version() != expected_abi_version():
         raise OctmaeError(f"{LIB_PATH} reports ABI {lib.octmae_abi_version()}, include/octmae.h declares "
                           f"{expected_abi_version()}: rebuild (make -C octcubem_amd/csrc)")

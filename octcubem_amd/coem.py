@@ -1032,6 +1032,118 @@ def get_corrected_metrics(image_features, text_features, logit_scale, labels, ra
     return metrics
 
 
+# ---- which candidates come back: top-k retrieval (retDisease_eval/evaluate_results_test_train_visualize_all_models_top3_col_aireadi_
+# laterality.py:186-270).  The script rebuilds the [N, N] logits from the features ``evaluate`` saved, overwrites the columns of the
+# query's own patient with -1e5 and takes torch.topk for k = 1, 3, 5, 10; ops.retrieval_topk keeps the k best candidates per query
+# while it walks the tiles of the ranks kernel (csrc/retrieval_topk.hip) and excludes the group instead of masking it.  ``topk=``
+# replaces the kernel by any function of its signature (tests/retrieval_topk_ref.py: numpy), as ``ranks=`` does above.
+def _device_topk(a, b, k, **kw):
+    if not (isinstance(a, torch.Tensor) and a.is_cuda):
+        raise RuntimeError("retrieve_topk: the lists come from the HIP kernel (ops.retrieval_topk), which has no CPU fallback: pass "
+                           "features on the device, or a topk function")
+    from . import ops
+    return ops.retrieval_topk(a, b, k, **kw)
+
+
+def _as_list(labels):
+    return labels.tolist() if isinstance(labels, (torch.Tensor, np.ndarray)) else list(labels)
+
+
+def retrieve_topk(query_features, gallery_features, k, query_groups=None, gallery_groups=None, keep=None, topk=None):
+    """``(indices int64 [N, k], scores float32 [N, k])`` as numpy arrays: for every row of ``query_features`` [N, D] the k best rows of
+    ``gallery_features`` [M, D] by the UNSCALED f32 score, equal scores by ascending index.  ``query_groups`` [N] / ``gallery_groups``
+    [M] (both or neither; any hashable labels, e.g. patient ids, mapped to int32 ids through ONE dictionary for the two sides): a
+    gallery row of the query's own group is no candidate.  ``keep`` [M]: != 0 marks the gallery rows that take part.  A query with
+    fewer than k candidates has ``-1`` / ``-inf`` in the open slots.  ``topk=``: see above; without it the features must be on the GPU."""
+    topk = topk or _device_topk
+    q, g = _feat(torch.as_tensor(query_features)), _feat(torch.as_tensor(gallery_features))
+    if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise ValueError(f"retrieve_topk: expected [N, D] queries and an [M, D] gallery, got {tuple(q.shape)} and {tuple(g.shape)}")
+    if (query_groups is None) != (gallery_groups is None):
+        raise ValueError("retrieve_topk: query_groups and gallery_groups are given together or not at all")
+    kw = {}
+    if query_groups is not None:
+        ql, gl = _as_list(query_groups), _as_list(gallery_groups)
+        if len(ql) != q.shape[0] or len(gl) != g.shape[0]:
+            raise ValueError(f"retrieve_topk: {len(ql)} query groups and {len(gl)} gallery groups for {q.shape[0]} queries and "
+                             f"{g.shape[0]} gallery rows")
+        ids = {}
+        kw["row_group"] = torch.tensor([ids.setdefault(l, len(ids)) for l in ql], dtype=torch.int32, device=q.device)
+        kw["col_group"] = torch.tensor([ids.setdefault(l, len(ids)) for l in gl], dtype=torch.int32, device=q.device)
+    if keep is not None:
+        kept = torch.as_tensor(keep).reshape(-1)
+        if kept.shape[0] != g.shape[0]:
+            raise ValueError(f"retrieve_topk: keep needs {g.shape[0]} entries, got {kept.shape[0]}")
+        kw["keep"] = (kept != 0).to(device=q.device, dtype=torch.uint8)
+    idx, score = topk(q, g, int(k), **kw)
+    idx = torch.as_tensor(idx).cpu().numpy().astype(np.int64)
+    score = torch.as_tensor(score).cpu().numpy().astype(np.float32)
+    if idx.shape != (q.shape[0], int(k)) or score.shape != idx.shape:
+        raise ValueError(f"retrieve_topk: the topk function returned {idx.shape} / {score.shape} for {q.shape[0]} queries and k = {k}")
+    return idx, score
+
+
+def topk_match_accuracy(indices, query_attr, gallery_attr, topk_list=(1, 3, 5, 10)):
+    """``{k: {"Micro Accuracy": ..., "Macro Accuracy": ...}}``: how often a retrieved row carries the query's attribute (the script's
+    laterality score, for any attribute), in float64.  Micro: matches over filled slots among the first k of all rows; macro: the mean,
+    over the rows with a filled slot, of matches over filled slots.  With every slot filled these are the script's
+    ``sum(matched) / (N k)`` and ``mean(sum(matched, 1) / k)``; a ``-1`` slot counts neither as a match nor as a slot (NaN when
+    no slot is filled at all).  A k beyond ``indices.shape[1]`` raises ValueError."""
+    idx = np.asarray(indices)
+    qa, ga = np.asarray(_as_list(query_attr)), np.asarray(_as_list(gallery_attr))
+    if idx.ndim != 2 or qa.shape != (idx.shape[0],) or ga.ndim != 1:
+        raise ValueError(f"topk_match_accuracy: expected indices [N, K], N query and M gallery attributes, got {idx.shape}, {qa.shape}, "
+                         f"{ga.shape}")
+    if idx.size and (idx.max() >= ga.shape[0] or idx.min() < -1):
+        raise ValueError(f"topk_match_accuracy: an index lies outside [-1, {ga.shape[0]})")
+    out = {}
+    for k in topk_list:
+        if not 1 <= k <= idx.shape[1]:
+            raise ValueError(f"topk_match_accuracy: k = {k} with lists of {idx.shape[1]}")
+        sub = idx[:, :k]
+        filled = sub >= 0
+        matched = filled & (ga[np.where(filled, sub, 0)] == qa[:, None]) if ga.shape[0] else np.zeros_like(filled)
+        slots, hits = filled.sum(axis=1).astype(np.float64), matched.sum(axis=1).astype(np.float64)
+        some = slots > 0
+        micro = hits.sum() / slots.sum() if some.any() else float("nan")
+        macro = float(np.mean(hits[some] / slots[some])) if some.any() else float("nan")
+        out[k] = {"Micro Accuracy": float(micro), "Macro Accuracy": macro}
+    return out
+
+
+def retrieval_report(results, attribute, groups, output_dir, model_name, topk_list=(1, 3, 5, 10), ir_oct=False,
+                     attribute_name="laterality", topk=None):
+    """The script's retrieval table from what ``evaluate(..., save_retrieval_results=True)`` wrote.  ``results``: the path of a
+    ``retrieval_results_{epoch}.npz`` or the dict of its arrays; the queries are ``image_features`` and the gallery ``text_features``
+    (``ir_oct=True``: the other way round, the script's swap).  ``attribute`` [N] (e.g. 1 for a right eye) and ``groups`` [N] (e.g.
+    patient ids) describe sample i on both sides; gallery rows of the query's group are excluded.  Writes
+    ``<output_dir>/<model_name>_<attribute_name>[_ir].csv`` as pandas writes the script's ``DataFrame(results).to_csv(index=False)``:
+    the k values, the micro row, the macro row (float64 values).  Returns ``{"accuracy", "indices", "scores"}`` with lists of
+    ``max(topk_list)``.  Features loaded from a file go to the GPU when there is one and no ``topk=`` is given."""
+    import csv
+    import os
+    if isinstance(results, (str, os.PathLike)):
+        with np.load(results) as z:
+            results = {key: z[key] for key in ("image_features", "text_features")}
+    img, txt = torch.as_tensor(results["image_features"]), torch.as_tensor(results["text_features"])
+    if topk is None and not img.is_cuda and torch.cuda.is_available():
+        img, txt = img.cuda(), txt.cuda()
+    query, gallery = (txt, img) if ir_oct else (img, txt)
+    topk_list = [int(k) for k in topk_list]
+    if not topk_list or min(topk_list) < 1:
+        raise ValueError(f"retrieval_report: topk_list must hold positive ints, got {topk_list}")
+    indices, scores = retrieve_topk(query, gallery, max(topk_list), query_groups=groups, gallery_groups=groups, topk=topk)
+    accuracy = topk_match_accuracy(indices, attribute, attribute, topk_list)
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, f"{model_name}_{attribute_name}{'_ir' if ir_oct else ''}.csv")
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(list(accuracy))
+        for row in ("Micro Accuracy", "Macro Accuracy"):
+            w.writerow([accuracy[k][row] for k in accuracy])
+    return {"accuracy": accuracy, "indices": indices, "scores": scores}
+
+
 def _eval_corrected_label(text_features, t=10 ** (-8)):
     """evaluate's own get_corrected_label (train_retclip.py:257-263): 1 where two reports of the batch have the same features."""
     f = text_features.detach()
@@ -1044,6 +1156,9 @@ def evaluate(model, data, epoch, args, tb_writer=None):
     (symmetric cross entropy, or BCE against the duplicate-report targets with ``args.correct_label``) is weighted by batch size and
     summed on the device with one synchronisation at the end, and the retrieval metrics come from ``get_metrics``.  Returns ``{}``
     off the main process or when validation is not due; otherwise the ten metrics plus ``val_loss``, ``epoch``, ``num_samples``.
+    With ``args.save_retrieval_results`` the features go to ``retrieval_results_{epoch}.npz``; a positive int ``args.retrieval_topk``
+    adds the k best partners of every sample in both directions (``topk_image_to_text``, ``topk_text_to_image``, int32 [N, k], and
+    their ``*_scores``; nothing excluded -- ``retrieval_report`` excludes by group).
     Zero-shot evaluation and wandb are not part of this package."""
     import json
     import logging
@@ -1118,5 +1233,12 @@ def evaluate(model, data, epoch, args, tb_writer=None):
                       "logit_scale": torch.stack(all_scale).cpu().numpy()}
             if all_labels:
                 arrays["labels"] = np.asarray(all_labels)
+            k = getattr(args, "retrieval_topk", 0) or 0
+            if isinstance(k, int) and k > 0:
+                # the k best partners of every sample in both directions, nothing excluded (retrieval_report excludes by group)
+                from . import ops
+                for name, a, b in (("topk_image_to_text", image_all, text_all), ("topk_text_to_image", text_all, image_all)):
+                    idx, score = ops.retrieval_topk(a, b, k)
+                    arrays[name], arrays[name + "_scores"] = idx.cpu().numpy(), score.cpu().numpy()
             np.savez(os.path.join(args.checkpoint_path, f"retrieval_results_{epoch}.npz"), **arrays)
     return metrics

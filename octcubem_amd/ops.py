@@ -1131,6 +1131,78 @@ def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Ten
     return out
 
 
+RETRIEVAL_TOPK_MAX = 32     # RT_KMAX of csrc/retrieval_topk.hip
+
+
+def retrieval_topk(a: torch.Tensor, b: torch.Tensor, k: int, keep: Optional[torch.Tensor] = None,
+                   row_group: Optional[torch.Tensor] = None, col_group: Optional[torch.Tensor] = None):
+    """(idx int32 [n, k], score float32 [n, k]): per row i of ``a`` float32 [n, d] the k best rows of ``b`` float32 [m, d] under the
+    score s(i, j) of ``retrieval_ranks`` (the same f32 fmaf chain off the same MFMA tiles, the same bits; csrc/retrieval_topk.hip --
+    nothing of size [n, m] is stored).  Column j is a candidate of row i iff ``keep[j] != 0`` (``keep`` bool / uint8 [m]; None: every
+    column) and ``col_group[j] != row_group[i]`` (int32 [n] and [m], both or neither; ``arange`` as both excludes the query itself).
+    Order: higher score first, equal scores by ascending column -- a stable descending sort, IEEE comparisons (-0.0 ties with 0.0);
+    the order is strict, so the result does not depend on the launch shape and two calls give the same bits.  A row with c < k
+    candidates has ``idx = -1`` and ``score = -inf`` in slots c .. k-1; emptiness is the index.  ``k`` in 1 .. 32.  ``a`` and ``b`` may
+    be slices of wider buffers (unit column stride, any row stride >= d).  Non-finite features raise ValueError before the launch
+    (that check reads one flag back from the device).  No autograd; no 16-bit operand, so autocast changes nothing."""
+    name = "retrieval_topk"
+    for t, nm in ((a, "a"), (b, "b"), (keep, "keep"), (row_group, "row_group"), (col_group, "col_group")):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name}: {nm} must be a GPU tensor (the HIP path has no CPU fallback)")
+    for t, nm in ((a, "a"), (b, "b")):
+        if t.dtype != F32:
+            raise TypeError(f"{name}: {nm} must be float32, got {t.dtype}")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.device != b.device:
+        raise ValueError(f"{name}: expected a [n, d] and b [m, d] on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, d = a.shape
+    m = b.shape[0]
+    if n < 1 or m < 1 or d < 1:
+        raise ValueError(f"{name}: empty input {tuple(a.shape)} / {tuple(b.shape)}")
+    if m > 2 ** 31 - 1:
+        raise ValueError(f"{name}: b has {m} rows, a column index must fit int32")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= RETRIEVAL_TOPK_MAX:
+        raise ValueError(f"{name}: k must be an int in [1, {RETRIEVAL_TOPK_MAX}], got {k!r}")
+    a, b = a.detach(), b.detach()
+    for t, nm, rows in ((a, "a", n), (b, "b", m)):
+        if (d > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < d):
+            raise ValueError(f"{name}: {nm} needs unit column stride and a row stride >= {d}, got strides {tuple(t.stride())}")
+    if (row_group is None) != (col_group is None):
+        raise ValueError(f"{name}: row_group and col_group are given together or not at all")
+    for t, nm, rows in ((row_group, "row_group", n), (col_group, "col_group", m)):
+        if t is None:
+            continue
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name}: {nm} must be int32, got {t.dtype}")
+        if tuple(t.shape) != (rows,) or t.device != a.device:
+            raise ValueError(f"{name}: {nm} must be [{rows}] on {a.device}, got {tuple(t.shape)} on {t.device}")
+    if keep is not None:
+        if keep.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{name}: keep must be bool or uint8, got {keep.dtype}")
+        if tuple(keep.shape) != (m,) or keep.device != a.device:
+            raise ValueError(f"{name}: keep must be [{m}] on {a.device}, got {tuple(keep.shape)} on {keep.device}")
+        keep = keep.detach().contiguous()
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+    row_group, col_group = (None if t is None else t.detach().contiguous() for t in (row_group, col_group))
+    # max |x| is finite iff every x is (a NaN propagates through the maximum): two reductions without an [n, d] temporary, one read-back
+    bad = (~torch.isfinite(torch.stack([torch.linalg.vector_norm(t, ord=float("inf")) for t in (a, b)]))).tolist()
+    if bad[0] or bad[1]:
+        raise ValueError(f"{name}: {'a' if bad[0] else 'b'} contains non-finite values")
+    sa = a.stride(0) if n > 1 else d
+    sb = b.stride(0) if m > 1 else d
+    nws = int(load().octmae_retrieval_topk_ws(n, m, k))
+    if nws < 0:
+        raise ValueError(f"{name}: n = {n}, m = {m}, k = {k} is beyond the kernel's workspace query")
+    ws = torch.empty(nws, dtype=torch.uint8, device=a.device) if nws else None
+    idx = torch.empty((n, k), dtype=torch.int32, device=a.device)
+    score = torch.empty((n, k), dtype=F32, device=a.device)
+    # algorithmic HBM bytes: a and b read once (the re-reads per tile hit the caches), the lists written once
+    _launch(name, 2.0 * n * m * d, float(4 * (n + m) * d + 8 * n * k),
+            lambda: call("octmae_retrieval_topk", a.data_ptr(), sa, b.data_ptr(), sb, _p(keep), _p(row_group), _p(col_group), k,
+                         idx.data_ptr(), score.data_ptr(), _p(ws), nws, n, m, d, _stream()))
+    return idx, score
+
+
 from ._autocast import no_autocast as _no_autocast  # noqa: E402
 
 
