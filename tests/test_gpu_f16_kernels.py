@@ -3,8 +3,8 @@
 tests/test_gpu_f16_parity.py runs whole models on the half build; this module runs the kernel tests themselves -- every GEMM tile
 variant, the split-K hand-off, the attention tail kernels, both backward forms, the delta epilogue, the weight-gradient pairs,
 LayerNorm, the token plumbing, AdamW, the slice-pooling kernels, the operand-type edges of tests/test_gpu_lp_edges.py, the row-wise
-attention checks of tests/test_gpu_attention_rows.py, the token / loss kernels of tests/test_gpu_tokens.py and the per-element GEMM bounds
-and activation sweeps of tests/test_gpu_gemm_elements.py -- in a child
+attention checks of tests/test_gpu_attention_rows.py, the token / loss kernels of tests/test_gpu_tokens.py, the per-element GEMM bounds
+and activation sweeps of tests/test_gpu_gemm_elements.py and the planted NaN / Inf of tests/test_gpu_nonfinite.py -- in a child
 pytest process with OCTMAE_LIB pointing at the half build (the 16-bit type is chosen per process, before octcubem_amd is imported).
 
 The child is started once the collection is known to contain a test of this module (tests/conftest.py::pytest_collection_finish ->
@@ -32,11 +32,11 @@ SUITES = ["tests/test_gpu_kernels.py", "tests/test_gpu_gemm_small.py",
           "tests/test_gpu_slicehead.py::test_slice_pool_kernels_vs_fp32_composition",
           "tests/test_gpu_slicehead.py::test_slice_pool_sidecar_matches_its_gradient",
           "tests/test_gpu_lp_edges.py", "tests/test_gpu_attention_rows.py", "tests/test_gpu_tokens.py",
-          "tests/test_gpu_layernorm_rows.py", "tests/test_gpu_gemm_elements.py"]
+          "tests/test_gpu_layernorm_rows.py", "tests/test_gpu_gemm_elements.py", "tests/test_gpu_nonfinite.py"]
 # tests per module the child must run (passed + skipped), as collected with -m gpu when this module was written
 MIN_TESTS = {"tests.test_gpu_kernels": 533, "tests.test_gpu_gemm_small": 20, "tests.test_gpu_slicehead": 37,
              "tests.test_gpu_lp_edges": 66, "tests.test_gpu_attention_rows": 21, "tests.test_gpu_tokens": 41,
-             "tests.test_gpu_layernorm_rows": 116, "tests.test_gpu_gemm_elements": 423}
+             "tests.test_gpu_layernorm_rows": 116, "tests.test_gpu_gemm_elements": 423, "tests.test_gpu_nonfinite": 677}
 # (test id, skip reason) pairs the half build may skip: none today
 ALLOWED_SKIPS = set()
 

@@ -44,13 +44,14 @@ class Guarded:
     """Tensors of one role as views inside ONE sentinel-filled buffer.  Every view starts 256 bytes aligned (fp32; 128 bytes for the
     16-bit copy) plus ``offs`` elements, with at least GUARD elements of sentinel on either side."""
 
-    def __init__(self, lengths, dtype=torch.float32, offs=0, fill=None):
+    def __init__(self, lengths, dtype=torch.float32, offs=0, fill=None, sentinel=None):
         offs = [offs] * len(lengths) if isinstance(offs, int) else list(offs)
+        sentinel = SENT[dtype] if sentinel is None else sentinel          # (tests/test_gpu_nonfinite.py surrounds the inputs with NaN)
         self.starts, pos = [], GUARD
         for n, o in zip(lengths, offs):
             self.starts.append(pos + o)
             pos = (pos + o + n + 63) // 64 * 64 + GUARD
-        self.buf = torch.full((pos,), SENT[dtype], dtype=dtype, device=DEV)
+        self.buf = torch.full((pos,), sentinel, dtype=dtype, device=DEV)
         assert self.buf.data_ptr() % 16 == 0
         self.views = [self.buf[s:s + n] for s, n in zip(self.starts, lengths)]
         inside = torch.zeros(pos, dtype=torch.bool, device=DEV)
@@ -92,10 +93,11 @@ class Guarded:
 class World:
     """p, g, m, v, the 16-bit copy and sumsq of one table, each role in a Guarded buffer of its own"""
 
-    def __init__(self, lengths, offs=None, lp_null=()):
+    def __init__(self, lengths, offs=None, lp_null=(), sentinel=None):
+        """sentinel: what surrounds p, g, m, v in place of SENT (the 16-bit copy and sumsq are outputs and keep theirs)"""
         offs = offs or {}
         self.lengths = list(lengths)
-        self.P, self.G, self.M, self.V = (Guarded(lengths, offs=offs.get(r, 0), fill=0.0) for r in "pgmv")
+        self.P, self.G, self.M, self.V = (Guarded(lengths, offs=offs.get(r, 0), fill=0.0, sentinel=sentinel) for r in "pgmv")
         self.LP = Guarded(lengths, dtype=LPT, offs=offs.get("lp", 0))
         self.SQ = Guarded([len(lengths)], fill=0.0)
         self.lp_null = set(lp_null)
@@ -113,7 +115,8 @@ class World:
         lp, sq = VARIANTS[variant]
         tab = self.table(lp=lp)
         assert (tab.lp_table is not None) == lp
-        gs_t = None if gs is None else torch.tensor([gs], dtype=torch.float32, device=DEV)
+        # gs: a number, or a one-element device tensor the caller placed (its data pointer is what the kernel is handed)
+        gs_t = gs if gs is None or isinstance(gs, torch.Tensor) else torch.tensor([gs], dtype=torch.float32, device=DEV)
         self.SQ.views[0].zero_()
         for b in self.roles.values():
             b.snapshot()
