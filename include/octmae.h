@@ -56,8 +56,10 @@ extern "C" {
  * 28: octmae_slab_norm_fwd, octmae_slab_norm_bwd (+ octmae_slabnorm_ws_floats): the LayerNorm over a transposed token slab in front of
  *     the SLIViT head's patch projection (the OCTCube trunk with the SLIViT slice head, csrc/slabnorm.hip).
  * 29: octmae_retrieval_topk (+ octmae_retrieval_topk_ws): the k best candidates per query off the tiles of octmae_retrieval_ranks, with a
- *     strict tie order (top-k cross-modal retrieval of the COEM evaluation, csrc/retrieval_topk.hip). */
-#define OCTMAE_ABI_VERSION 29
+ *     strict tie order (top-k cross-modal retrieval of the COEM evaluation, csrc/retrieval_topk.hip).
+ * 30: octmae_mae_compose_nc, octmae_white_border (+ octmae_white_border_ws_floats): the RGB / raw-level panels and the border blanking of
+ *     the 2-D half of the validation pass (csrc/recon2d.hip). */
+#define OCTMAE_ABI_VERSION 30
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -439,6 +441,38 @@ int octmae_mse_bwd(const float* pred, const float* imgs, const int* frame_idx, c
  * a batch stride below L * PD.  -2: denorm outside {0, 1}, more than 2^31 - 1 tokens. */
 int octmae_mae_compose(const float* pred, long long pred_batch_stride, const float* imgs, const int* frame_idx, const float* mask,
                        uint8_t* out, int B, int T, int H, int W, int u_sz, int p, int L, int denorm, void* stream);
+
+/* ---- the 2-D half of the validation pass (csrc/recon2d.hip) -------------------------------------------
+ * The four panels of octmae_mae_compose for C channels and any affine grey scale (custom_util/misc.py:1134-1223 get_visible_images_2d
+ * with untransform_image_no_normalization :730-731, or the inverse of a Normalize transform).
+ *   pred       f32 [L][PD] per sample, PD = u_sz * p * p * C in the order (a < u_sz, py, px, c < C), samples pred_batch_stride floats
+ *              apart as in octmae_mae_compose.  u_sz = 1, T = 1: models_mae_2d.patchify's order; C = 1: models_mae.patchify's.
+ *   imgs       f32 [B][C][T][H][W];  mask f32 [B][L], != 0 = removed.  Predicted frame f is frame f of the volume (Tp <= T).
+ *   out        uint8 [B][4][Tp][H][W][C], channels innermost; panels as octmae_mae_compose.
+ *   level      g_c(v) = (int) clip(((v * scale_c) + shift_c) * 255, 0, 255), each operation rounded to fp32 on its own; a non-finite v
+ *              gives 0.  scale 1, shift 0: untransform_image_no_normalization bit for bit.  C = 1: only scale0 / shift0 are used.
+ *   denorm     as octmae_mae_compose: mean / unbiased variance (+ 1e-6) of the target patch over all PD elements.
+ * -1: what octmae_mae_compose answers with -1, C outside {1, 3}, a non-finite scale or shift, more predicted frames than T.
+ * -2: u_sz > 1 with C > 1 (no caller states that element order), denorm outside {0, 1}, more than 2^31 - 1 tokens. */
+int octmae_mae_compose_nc(const float* pred, long long pred_batch_stride, const float* imgs, const float* mask, uint8_t* out, int B, int C,
+                          int T, int H, int W, int u_sz, int p, int L, float scale0, float scale1, float scale2, float shift0,
+                          float shift1, float shift2, int denorm, void* stream);
+/* find_and_convert_large_white_region(image, 'tensor') (custom_util/misc.py:1438-1484) for a batch, in place, two launches on `stream`.
+ *   imgs    f32 [B][T][H][W], 16-byte aligned, W % 4 == 0.  white = frame 0 > max - k * (max - min) over all T frames, k = float(15 / 255),
+ *           the difference, the product and the second difference each rounded to fp32; a NaN anywhere: nothing is white.
+ *           Per row of frame 0: the run of white columns from the first white column f (followed iff f < left_idle_from; when it ends at
+ *           a column e >= left_ext_from, [e, e + 5) is marked too) and the run down from the last white column l (followed iff
+ *           l >= right_live_from; when it ends at a column s < right_ext_below the reference assigns [s : s - 5], which is
+ *           [s, W + s - 5) for s <= 4 and empty otherwise).  Marked pixels become 0, then every frame becomes a copy of frame 0.
+ *   region  uint8 [B][T][H][W], written in full: 1 = marked, the same for every frame.
+ *   ws      octmae_white_border_ws_floats(B, T, H, W) floats (caller-owned, need not be initialised); the query returns -1 for
+ *           non-positive sizes or W % 4, -2 past 2^31 - 1.
+ * The four limits are the reference's comparisons with 0.01 * W, 0.05 * W, W - 0.01 * W and W - 0.05 * W, evaluated by the caller in
+ * double (octcubem_amd/ops.py: white_border_limits); each lies in [0, W + 1].  -1: NULL / non-positive / misaligned arguments, W % 4,
+ * a limit outside its range.  -2: more than 2^31 - 1 rows. */
+int octmae_white_border_ws_floats(int B, int T, int H, int W);
+int octmae_white_border(float* imgs, uint8_t* region, float* ws, int B, int T, int H, int W, int left_idle_from, int left_ext_from,
+                        int right_live_from, int right_ext_below, void* stream);
 
 /* ---- saliency: input gradients, Grad-CAM, heat volumes (csrc/saliency.hip) ---------------------------
  * retinal-COEM/src/oph_vis_util/base_cam_retclip_3mod.py (the reference's Grad-CAM base class over pytorch_grad_cam) and its

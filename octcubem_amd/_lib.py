@@ -90,6 +90,9 @@ SIGNATURES = {
     "octmae_mse_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_mse_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_mae_compose": [_vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "octmae_mae_compose_nc": [_vp, _ll, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _vp],
+    "octmae_white_border_ws_floats": [_i, _i, _i, _i],
+    "octmae_white_border": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_patch_scatter": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_cam_ws_floats": [_i, _i, _i],
     "octmae_cam_weights": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],

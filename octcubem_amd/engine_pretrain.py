@@ -1,6 +1,7 @@
 """Pre-training inner loops with the reference's signatures: ``train_one_epoch`` (3-D volumes only) and
 ``train_one_epoch_joint`` (3-D volumes + 2-D/512 B-scans, per-frame loss feedback for self-paced sampling) plus the two
-epoch schedules of the joint recipe, and ``eval_one_epoch``, the validation pass with its reconstruction dumps.
+epoch schedules of the joint recipe, ``eval_one_epoch``, the validation pass with its reconstruction dumps (3-D, and the 2-D half of
+the joint recipe), and ``eval_one_epoch_2d``, the validation pass of the 2-D MAE.
 
 ``train_one_epoch``: pre-training inner loop with the reference's signature and per-iteration order of operations
 (OCTCube/engine_pretrain.py:31-91; Pre-training/engine_pretrain.py:29-204 is the same loop plus the 2-D branch):
@@ -183,22 +184,29 @@ def eval_one_epoch(model: torch.nn.Module, data_loader: Iterable, device: torch.
     ``args.output_dir/val_images_<epoch>`` (misc.get_visible_images) -> ``loss`` / ``mask_ratio`` meters, ``val_loss`` to the writer.
     ``data_loader`` yields ``(samples, img_names)``.  Returns the averaged stats, or None on a non-finite loss (as engine_finetune).
     Not reproduced: the per-step device synchronise, ``forward_patch_embed`` / ``get_patch_embed_images`` (analysis output nothing
-    reads), the checkpoint deletion on a non-finite loss, and the secondary 2-D loader of the joint recipe -- ``joint`` only picks
-    ``img_names[0]`` as there; ``mask_ratio_2d``, ``data_loader_2d``, ``all_image_dict``, ``analysis``, ``agg_data`` and ``fp32`` /
-    ``fp16`` (bf16 operands, fp32 everything else) are accepted and ignored.
+    reads) and the checkpoint deletion on a non-finite loss; ``all_image_dict``, ``analysis``, ``agg_data`` and ``fp32`` / ``fp16``
+    (bf16 operands, fp32 everything else) are accepted and ignored.  ``joint`` picks ``img_names[0]`` as there.
+    With ``joint`` and a ``data_loader_2d``, every dump step also does what :298-322 does: the next batch of the 2-D loader (which
+    restarts when exhausted, as in ``train_one_epoch_joint``; the reference's bare ``next`` raises StopIteration there) goes to the
+    device, its bright borders are blanked (misc.blank_white_borders: the reference's per-sample find_and_convert_large_white_region
+    loop as two launches), the model runs on it with ``mask_ratio_2d`` and misc.get_visible_images_2d writes
+    ``val_images_<epoch>/visible_2d/<name>`` under the names ``batch[1][-1]``.  The 2-D loss enters no meter: the returned stats are
+    those of the 3-D loader alone, as in the reference.
     The pass leaves ``.grad`` as it found it: the parameter arena attaches its gradient views when a model's first forward creates it
     (octcubem_amd/arena.py), also under no_grad; parameters that came in without a gradient go out without one, and the next forward
     with grad enabled re-attaches the views (``arena.rebind_grads``).  Nothing computes a gradient inside the pass, so a parameter that
     came in with a gradient keeps it untouched, and a model without an arena is left exactly as it was."""
     no_grad_at_entry = [p for p in model.parameters() if p.grad is None]
     try:
-        return _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, visible_frame_freq)
+        return _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, visible_frame_freq,
+                               data_loader_2d if joint else None, mask_ratio_2d)
     finally:
         for p in no_grad_at_entry:
             p.grad = None
 
 
-def _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, visible_frame_freq):
+def _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, visible_frame_freq, data_loader_2d=None,
+                    mask_ratio_2d=None):
     img_save_dir = os.path.join(args.output_dir, f"val_images_{epoch}")
     os.makedirs(img_save_dir, exist_ok=True)
     model.eval()
@@ -208,6 +216,7 @@ def _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, 
     print_freq = 20
     accum_iter = args.accum_iter
     n_iter = len(data_loader)
+    secondary_iter = iter(data_loader_2d) if data_loader_2d is not None else None
     for data_iter_step, (samples, img_names) in enumerate(metric_logger.log_every(data_loader, print_freq, header)):
         samples = samples.to(device, non_blocking=True)
         if samples.dim() == 6:
@@ -223,11 +232,83 @@ def _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, 
                 img_names = img_names[0]
             vars_ = {"reconstruct_imgs": pred, "samples": samples, "mask": mask, "img_names": img_names}
             misc.get_visible_images(vars_, model, img_save_dir)
+            if secondary_iter is not None:
+                try:
+                    secondary_data = next(secondary_iter)
+                except StopIteration:
+                    secondary_iter = iter(data_loader_2d)
+                    secondary_data = next(secondary_iter)
+                img_names_2d = secondary_data[1][-1]
+                sample_2d, pre_mask = misc.blank_white_borders(secondary_data[0].to(device, non_blocking=True))
+                _, pred_2d, mask_2d = model(sample_2d, mask_ratio=mask_ratio_2d)
+                vars_2d_ = {"reconstruct_imgs": pred_2d, "samples": sample_2d, "mask": mask_2d, "img_names": img_names_2d,
+                            "pre_mask": pre_mask}
+                misc.get_visible_images_2d(vars_2d_, model, img_save_dir)
         metric_logger.update(loss=loss_value)
         metric_logger.update(mask_ratio=args.mask_ratio)
         loss_value_reduce = misc.all_reduce_mean(loss_value)
         if log_writer is not None and (data_iter_step + 1) % accum_iter == 0:
             epoch_1000x = int((data_iter_step / n_iter + epoch) * 1000 * getattr(args, "repeat_aug", 1))
+            log_writer.add_scalar("val_loss", loss_value_reduce, epoch_1000x)
+    metric_logger.synchronize_between_processes()
+    print("Averaged stats:", metric_logger)
+    return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
+
+
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+@torch.no_grad()
+def eval_one_epoch_2d(model: torch.nn.Module, data_loader: Iterable, device: torch.device, epoch: int, log_writer=None, args=None,
+                      visible_frame_freq=20, inverse_imagenet_transform=None, **ignored):
+    """Validation pass of the 2-D MAE (models_mae_2d): the primary path of OCTCube/engine_pretrain.py:172-330, that file's
+    ``eval_one_epoch``, under a name of its own because this module's ``eval_one_epoch`` is the 3-D / joint one.  Per batch
+    ``loss, pred, mask = model(samples, mask_ratio=args.mask_ratio)`` on [B, C, H, W] images -> non-finite guard (returns None, as
+    ``eval_one_epoch``) -> on the main process, when ``(step + 1) % (20 * visible_frame_freq) == 0`` (this file's condition, one step
+    later than the other one's), the panels of the WHOLE batch into ``args.output_dir/val_images_<epoch>/visible_2d/<name>``
+    (misc.get_visible_images_2d) -> ``loss`` / ``mask_ratio`` meters, ``val_loss`` to the writer.  ``data_loader`` yields
+    ``(samples, img_names)``.  Departures: the reference indexes ``img_names[0]`` and then takes the ``len`` of that string, so it
+    draws as many images as the first name has characters; here every image of the batch is drawn under its own name.  With
+    ``inverse_imagenet_transform`` (any value but None, as there) the levels are those of the inverse ImageNet Normalize
+    (``v * std + mean``, in the kernel) instead of the raw ones.  The joint branch of that function (it can never run with a 2-D
+    model) and ``fp32`` / ``fp16`` / ``analysis`` / ``all_image_dict`` are accepted through ``**ignored``.  ``.grad`` is left as
+    ``eval_one_epoch`` leaves it."""
+    no_grad_at_entry = [p for p in model.parameters() if p.grad is None]
+    try:
+        return _eval_one_epoch_2d(model, data_loader, device, epoch, log_writer, args, visible_frame_freq,
+                                  inverse_imagenet_transform is not None)
+    finally:
+        for p in no_grad_at_entry:
+            p.grad = None
+
+
+def _eval_one_epoch_2d(model, data_loader, device, epoch, log_writer, args, visible_frame_freq, imagenet):
+    img_save_dir = os.path.join(args.output_dir, f"val_images_{epoch}")
+    os.makedirs(img_save_dir, exist_ok=True)
+    model.eval()
+    metric_logger = misc.MetricLogger(delimiter="  ")
+    metric_logger.add_meter("mask_ratio", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
+    header = "Epoch: [{}]".format(epoch)
+    print_freq = 20
+    accum_iter = args.accum_iter
+    n_iter = len(data_loader)
+    for data_iter_step, (samples, img_names) in enumerate(metric_logger.log_every(data_loader, print_freq, header)):
+        samples = samples.to(device, non_blocking=True)
+        loss, pred, mask = model(samples, mask_ratio=args.mask_ratio)
+        loss_value = loss.item()
+        if not math.isfinite(loss_value):
+            print("Loss is {}, stopping evaluation".format(loss_value))
+            return None
+        if (data_iter_step + 1) % (print_freq * visible_frame_freq) == 0 and misc.is_main_process():
+            vars_ = {"reconstruct_imgs": pred, "samples": samples, "mask": mask, "img_names": img_names}
+            if imagenet:
+                vars_.update(mean=IMAGENET_MEAN, std=IMAGENET_STD)
+            misc.get_visible_images_2d(vars_, model, img_save_dir)
+        metric_logger.update(loss=loss_value)
+        metric_logger.update(mask_ratio=args.mask_ratio)
+        loss_value_reduce = misc.all_reduce_mean(loss_value)
+        if log_writer is not None and (data_iter_step + 1) % accum_iter == 0:
+            epoch_1000x = int((data_iter_step / n_iter + epoch) * 1000)
             log_writer.add_scalar("val_loss", loss_value_reduce, epoch_1000x)
     metric_logger.synchronize_between_processes()
     print("Averaged stats:", metric_logger)

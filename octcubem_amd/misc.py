@@ -483,3 +483,88 @@ def get_visible_images(vars_: dict, model, save_dir: str, pad_to_pred_t_dim=True
             row = v[:, z].transpose(1, 0, 2).reshape(v.shape[2], 4 * v.shape[3])       # [H, 4 W]: the panels left to right
             Image.fromarray(row).save(os.path.join(d, f"frame_{z + offset}{suffix}.png"))
     return vols
+
+
+# ------------------------------------------------------------------------------------------------
+# the 2-D half of the validation pass: border blanking and the panels of the B-scan triplets / RGB images
+# ------------------------------------------------------------------------------------------------
+def blank_white_borders(samples: torch.Tensor, inplace: bool = False):
+    """The reference's preparation of a 2-D validation batch (Pre-training/engine_pretrain.py:304-308: one
+    find_and_convert_large_white_region call per sample) as two launches for the whole batch: ``samples`` [B, 1, T, H, W] (or
+    [B, T, H, W]) on the GPU -> ``(blanked, pre_mask)`` of the same shape, ``pre_mask`` bool.  Per sample the bright bands that touch the
+    left / right edge of frame 0 are set to 0 and every frame becomes a copy of that frame (ops.white_border, csrc/recon2d.hip).  The
+    input is left alone unless ``inplace`` (then it must be contiguous float32)."""
+    from . import ops
+    if samples.dim() not in (4, 5) or (samples.dim() == 5 and samples.shape[1] != 1):
+        raise ValueError(f"blank_white_borders: expected [B, 1, T, H, W] or [B, T, H, W], got {tuple(samples.shape)}")
+    x = samples.detach()
+    if not inplace:
+        x = x.to(dtype=torch.float32, copy=True).contiguous()
+    elif x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("blank_white_borders(inplace=True) needs a contiguous float32 tensor")
+    out, region = ops.white_border(x.view(x.shape[0], *x.shape[-3:]))
+    return out.view(x.shape), region.view(x.shape)
+
+
+def find_and_convert_large_white_region(image: torch.Tensor, img_type: str = "tensor"):
+    """The reference's function (custom_util/misc.py:1438-1484) with its name and its return pair ``(return_img, connected_region)`` for
+    a [T, H, W] or [H, W] tensor; the input is not modified.  The work runs on the GPU (a CPU tensor is copied there and the results
+    come back to its device); W must be a multiple of 4.  ``img_type='pil'`` is the dataset-side CPU branch and is not provided."""
+    if img_type != "tensor":
+        raise NotImplementedError("find_and_convert_large_white_region: only img_type='tensor' (the 'pil' branch is dataset-side CPU code)")
+    if image.dim() not in (2, 3):
+        raise ValueError(f"find_and_convert_large_white_region: expected [T, H, W] or [H, W], got {tuple(image.shape)}")
+    dev = image.device
+    x = image.detach().to(device=dev if dev.type == "cuda" else "cuda", dtype=torch.float32, copy=True).contiguous()
+    out, region = blank_white_borders(x.view(1, *([1] * (3 - x.dim())), *x.shape), inplace=True)
+    return out.view(image.shape).to(device=dev, dtype=image.dtype), region.view(image.shape).to(dev)
+
+
+_IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".gif", ".webp")
+
+
+def get_visible_images_2d(vars_: dict, model, save_dir: str):
+    """The reference's 2-D reconstruction dump (custom_util/misc.py:1134-1223) with its signature and its ``vars_`` keys
+    (``reconstruct_imgs`` = pred, ``samples``, ``mask``, ``img_names``; further keys are ignored): per image i one file
+    ``save_dir/visible_2d/<img_names[i]>`` holding the four panels (original, masked, reconstruction, reconstruction pasted with the
+    visible patches) side by side, [H, 4 W] grey or [H, 4 W, 3] RGB.  The panels come from ONE kernel (ops.mae_compose_nc):
+    for 5-D ``samples`` (the B-scan triplets of the joint model) ``model.reconstruct(..., normalization=False)``, whose three frames
+    become the three colour channels; for 4-D ``samples`` (the 2-D MAE) ``model.reconstruct``, with the optional keys ``mean`` / ``std``
+    handed on (the inverse of the loader's Normalize).  Both draw the raw levels of untransform_image_no_normalization, as the
+    reference does here.  Departures: every channel is drawn (the reference's show_image draws channel 0 through a colour map it
+    rescales per panel), and there is no matplotlib figure: Pillow writes the file, ``.png`` appended when the name has no image
+    extension; without Pillow ``<name>.npy`` is written.  A wrapper is unwrapped through ``.module``.  Returns the uint8 tensor
+    ``reconstruct`` gave ([N, 4, Tp, H, W] or [N, 4, H, W, C]), on the host."""
+    net = getattr(model, "module", model)
+    names = [str(n) for n in vars_["img_names"]]
+    samples = vars_["samples"]
+    if samples.dim() == 5:
+        pan = net.reconstruct(samples, vars_["reconstruct_imgs"], vars_["mask"], normalization=False)
+    elif vars_.get("mean") is not None:
+        pan = net.reconstruct(samples, vars_["reconstruct_imgs"], vars_["mask"], mean=vars_["mean"], std=vars_["std"])
+    else:
+        pan = net.reconstruct(samples, vars_["reconstruct_imgs"], vars_["mask"])
+    pan = pan.cpu()
+    if pan.shape[0] != len(names):
+        raise ValueError(f"get_visible_images_2d: {len(names)} img_names for {pan.shape[0]} images")
+    rows = pan.permute(0, 3, 1, 4, 2) if samples.dim() == 5 else pan.permute(0, 2, 1, 3, 4)      # [N, H, 4, W, C]
+    N, H, _, W, C = rows.shape
+    if C not in (1, 3):
+        raise ValueError(f"get_visible_images_2d: 1 or 3 channels (or frames) per image, got {C}")
+    rows = rows.reshape(N, H, 4 * W, C).contiguous().numpy()
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    for i, name in enumerate(names):
+        path = os.path.join(save_dir, "visible_2d", name)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        img = rows[i, :, :, 0] if C == 1 else rows[i]
+        if Image is None:
+            import numpy as np
+            np.save(path + ".npy", img)
+            continue
+        if not name.lower().endswith(_IMAGE_EXTENSIONS):
+            path += ".png"
+        Image.fromarray(img).save(path)
+    return pan

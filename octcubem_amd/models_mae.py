@@ -343,17 +343,25 @@ class MaskedAutoencoderViT(nn.Module):
 
     @no_autocast
     @torch.no_grad()
-    def reconstruct(self, imgs, pred, mask, denormalize=False):
+    def reconstruct(self, imgs, pred, mask, denormalize=False, normalization=True):
         """What the reference's validation pass draws (custom_util/misc.py:1225-1299 get_visible_images), as one kernel over what
         ``forward`` returned: uint8 [N, 4, Tp, H, W] = original frames, masked input, reconstruction, reconstruction pasted with the
         visible patches, in the grey levels of untransform_image (:727-728) and bit-equal to that chain.  Patch size, temporal patch
         and the frame selection are forward_loss's (the 512^2 B-scan branch by shape alone); ``pred`` may be the strided view
         ``forward`` returns (no copy).  ``denormalize=False`` is the reference: the raw prediction, also for a norm_pix_loss model;
-        True maps it back through the per-patch mean / variance of the target first.  A non-finite value is drawn as 0."""
+        True maps it back through the per-patch mean / variance of the target first.  A non-finite value is drawn as 0.
+        ``normalization=False`` gives the raw levels ``(int) clip(v * 255, 0, 255)`` of untransform_image_no_normalization (:730-731)
+        instead, as get_visible_images_2d (:1134-1223) draws the B-scan triplets of the joint recipe: the same four panels in the
+        same shape, from ops.mae_compose_nc; every predicted frame must be the frame of the same index (T == 3, or pred_t_dim == T)."""
         if self.in_chans != 1:
             raise NotImplementedError("reconstruct: one channel (every call site of the reference's visualiser has in_chans == 1)")
         imgs = imgs.float().contiguous()
         pe_mod = self.high_res_patch_embed if self._is_high_res(imgs) else self.patch_embed
+        if not normalization:
+            if self._frame_idx(imgs.shape[2], "cpu") is not None:
+                raise NotImplementedError("reconstruct(normalization=False): the predicted frames must be the volume's first frames in order")
+            return ops.mae_compose_nc(pred.float(), imgs, mask.float(), self.t_pred_patch_size, pe_mod.patch_size[0],
+                                      denorm=bool(denormalize))[..., 0]
         return ops.mae_compose(pred.float(), imgs, mask.float(), self._frame_idx(imgs.shape[2], imgs.device),
                                self.t_pred_patch_size, pe_mod.patch_size[0], bool(denormalize))
 

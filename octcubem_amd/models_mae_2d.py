@@ -202,6 +202,24 @@ class MaskedAutoencoderViT(nn.Module):
             return loss, frame_loss
         return loss
 
+    @torch.no_grad()
+    def reconstruct(self, imgs, pred, mask, denormalize=False, mean=None, std=None):
+        """What the reference's 2-D validation pass draws (custom_util/misc.py:1134-1223 get_visible_images_2d), as one kernel over
+        what ``forward`` returned: uint8 [N, 4, H, W, C] = original, masked input, reconstruction, reconstruction pasted with the
+        visible patches, channels innermost (what Pillow reads).  ``mean=None``: the raw levels ``(int) clip(v * 255, 0, 255)`` of
+        untransform_image_no_normalization (:730-731), bit-equal to that chain.  With ``mean`` / ``std`` (one value per channel) the
+        level is ``(int) clip((v * std + mean) * 255, 0, 255)``: the inverse of the loader's Normalize, the role of the reference's
+        ``inverse_imagenet_transform``.  ``pred`` may be the strided view ``forward`` returns (no copy).  ``denormalize=True`` maps a
+        norm_pix_loss prediction back through the per-patch mean / variance of the target first.  A non-finite value is drawn as 0."""
+        if (mean is None) != (std is None):
+            raise ValueError("reconstruct: give mean and std together, or neither")
+        imgs = imgs.float().contiguous()
+        N, C, H, W = imgs.shape
+        scale, shift = (1.0, 0.0) if mean is None else (std, mean)
+        out = ops.mae_compose_nc(pred.float(), imgs.view(N, C, 1, H, W), mask.float(), 1, self.patch_embed.patch_size[0], scale, shift,
+                                 bool(denormalize))
+        return out[:, :, 0]
+
     def forward(self, imgs, mask_ratio=0.75, return_frame_loss=False, noise=None):
         self.prepare()
         imgs = imgs.float().contiguous()

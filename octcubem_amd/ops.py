@@ -11,6 +11,7 @@ the data-parallel reducer uses to overlap the RCCL all-reduce with backward.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Callable, List, Optional, Sequence
 
@@ -995,6 +996,95 @@ def mae_compose(pred: torch.Tensor, imgs: torch.Tensor, mask: torch.Tensor, fram
             lambda: call("octmae_mae_compose", pred.data_ptr(), bs, imgs.data_ptr(), _p(frame_idx), mask.data_ptr(), out.data_ptr(),
                          Bn, T, Hh, Ww, u, p, L, int(bool(denorm)), _stream()))
     return out
+
+
+def mae_compose_nc(pred: torch.Tensor, imgs: torch.Tensor, mask: torch.Tensor, u: int, p: int, scale=(1.0, 1.0, 1.0),
+                   shift=(0.0, 0.0, 0.0), denorm: bool = False) -> torch.Tensor:
+    """The four panels of ``mae_compose`` for ``C`` channels and any affine grey scale (get_visible_images_2d, custom_util/misc.py:
+    1134-1223): uint8 [B, 4, Tp, H, W, C], channels innermost.  ``pred`` f32 [B, L, u*p*p*C] in the order (a < u, py, px, c < C) --
+    models_mae_2d.patchify's for u = 1, models_mae.patchify's for C = 1 -- contiguous or the ``pred_full[:, 1:, :]`` view;
+    ``imgs`` f32 [B, C, T, H, W]; ``mask`` f32 [B, L], 1 = removed.  The level of channel c is
+    ``(int) clip(((v * scale[c]) + shift[c]) * 255, 0, 255)``, every operation rounded to fp32 on its own: the defaults are the
+    reference's untransform_image_no_normalization bit for bit, ``scale = std`` / ``shift = mean`` the inverse of a Normalize
+    transform.  A scalar ``scale`` / ``shift`` stands for every channel.  Predicted frame f is frame f of ``imgs``.  Everything the
+    entry point refuses is refused here first, before a launch.  No autograd."""
+    if pred.dim() != 3 or imgs.dim() != 5:
+        raise RuntimeError(f"mae_compose_nc: expected pred [B, L, PD] and imgs [B, C, T, H, W], got {tuple(pred.shape)} and {tuple(imgs.shape)}")
+    Bn, L, PD = pred.shape
+    _, Cc, T, Hh, Ww = imgs.shape
+    u, p = int(u), int(p)
+    if Cc not in (1, 3):
+        raise RuntimeError(f"mae_compose_nc: 1 or 3 channels, got {Cc}")
+    if u > 1 and Cc > 1:
+        raise RuntimeError(f"mae_compose_nc: a temporal patch of {u} frames with {Cc} channels has no caller and no stated element order")
+    if u < 1 or p < 4 or p % 4 or Ww % 4:
+        raise RuntimeError(f"mae_compose_nc: p and W must be multiples of 4 and u positive, got u={u}, p={p}, W={Ww}")
+
+    def three(v, what):
+        v = [float(v)] * 3 if isinstance(v, (int, float)) else [float(x) for x in v]
+        if len(v) == 1:
+            v = v * 3
+        if len(v) < Cc or len(v) > 3 or not all(math.isfinite(x) for x in v):
+            raise RuntimeError(f"mae_compose_nc: {what} must hold {Cc} finite values, got {v}")
+        return v + [v[-1]] * (3 - len(v))
+    sc, sh = three(scale, "scale"), three(shift, "shift")
+    if imgs.shape[0] != Bn or Bn < 1 or L < 1 or PD != u * p * p * Cc or Hh % p or Ww % p or L % ((Hh // p) * (Ww // p)):
+        raise RuntimeError(f"mae_compose_nc: pred {tuple(pred.shape)} does not tile imgs {tuple(imgs.shape)} with u={u}, p={p}")
+    Tp = L // ((Hh // p) * (Ww // p)) * u
+    if Tp > T:
+        raise RuntimeError(f"mae_compose_nc: the prediction has {Tp} frames, the volume {T}")
+    pred, mask = pred.detach(), mask.detach()
+    imgs = _chk(imgs.detach(), F32, "mae_compose_nc imgs")
+    if not pred.is_cuda or pred.dtype != F32:
+        raise RuntimeError(f"mae_compose_nc pred: expected a float32 GPU tensor, got {pred.dtype} on {pred.device}")
+    if pred.stride(2) != 1 or pred.stride(1) != PD or (Bn > 1 and (pred.stride(0) < L * PD or pred.stride(0) % 4)):
+        pred = pred.contiguous()
+    bs = pred.stride(0) if Bn > 1 else L * PD
+    mask = _chk(mask.reshape(Bn, L), F32, "mae_compose_nc mask")
+    out = torch.empty((Bn, 4, Tp, Hh, Ww, Cc), dtype=torch.uint8, device=imgs.device)
+    nel = Bn * Tp * Hh * Ww * Cc
+    _launch("mae_compose_nc", 0.0, float(4 * Bn * L * PD + 4 * nel * (2 if denorm else 1) + 4 * Bn * L + 4 * nel),
+            lambda: call("octmae_mae_compose_nc", pred.data_ptr(), bs, imgs.data_ptr(), mask.data_ptr(), out.data_ptr(), Bn, Cc, T, Hh,
+                         Ww, u, p, L, *sc, *sh, int(bool(denorm)), _stream()))
+    return out
+
+
+def white_border_limits(W: int):
+    """The four column limits of the reference's border blanking (custom_util/misc.py:1458-1473) as integers, each found with the
+    reference's own double expression: the left run is followed iff ``not (f > 0.01 * W)`` i.e. f < limits[0]; it is extended iff its
+    end ``e > 0.05 * W`` i.e. e >= limits[1]; the right run is followed iff ``not (l < W - 0.01 * W)`` i.e. l >= limits[2]; its slice
+    is assigned iff ``s < W - 0.05 * W`` i.e. s < limits[3].  At W = 512: (6, 26, 507, 487)."""
+    W = int(W)
+    cols = range(W + 1)
+    return (next(i for i in cols if i > 0.01 * W), next(i for i in cols if i > 0.05 * W),
+            next(i for i in cols if not (i < W - 0.01 * W)), next(i for i in cols if not (i < W - 0.05 * W)))
+
+
+def white_border(imgs: torch.Tensor):
+    """find_and_convert_large_white_region(image, 'tensor') (custom_util/misc.py:1438-1484) for a batch, IN PLACE: ``imgs`` f32
+    [B, T, H, W] (contiguous, W a multiple of 4).  Per image the white pixels of frame 0 are those above max - 15/255 (max - min) over
+    all frames; the runs of white columns that touch the left / right edge of a row are set to 0, and every frame becomes a copy of
+    the blanked frame 0.  Returns ``(imgs, region)``, ``region`` bool [B, T, H, W] of the marked pixels.  Two launches, no
+    synchronisation.  No autograd."""
+    if imgs.dim() != 4:
+        raise RuntimeError(f"white_border: expected imgs [B, T, H, W], got {tuple(imgs.shape)}")
+    _chk(imgs, F32, "white_border imgs")
+    Bn, T, Hh, Ww = imgs.shape
+    if min(Bn, T, Hh, Ww) < 1 or Ww % 4:
+        raise RuntimeError(f"white_border: needs a non-empty batch and a width that is a multiple of 4, got {tuple(imgs.shape)}")
+    if imgs.requires_grad:
+        raise RuntimeError("white_border: edits its input in place and has no backward")
+    n_ws = load().octmae_white_border_ws_floats(Bn, T, Hh, Ww)
+    if n_ws <= 0:
+        raise RuntimeError(f"white_border: no workspace size for {tuple(imgs.shape)} (rc={n_ws})")
+    ws = torch.empty(n_ws, dtype=F32, device=imgs.device)
+    region = torch.empty(imgs.shape, dtype=torch.uint8, device=imgs.device)
+    lim = white_border_limits(Ww)
+    npx = Bn * T * Hh * Ww
+    # algorithmic HBM bytes: every frame read once for the extremes, every frame and every mark written (frame 0's rows are re-read from cache)
+    _launch("white_border", 0.0, float(4 * npx + 4 * npx + npx),
+            lambda: call("octmae_white_border", imgs.data_ptr(), region.data_ptr(), ws.data_ptr(), Bn, T, Hh, Ww, *lim, _stream()))
+    return imgs, region.view(torch.bool)
 
 
 def _rank_counts(name: str, scores: torch.Tensor, labels: torch.Tensor, valid: Optional[torch.Tensor]) -> torch.Tensor:
