@@ -58,8 +58,10 @@ extern "C" {
  * 29: octmae_retrieval_topk (+ octmae_retrieval_topk_ws): the k best candidates per query off the tiles of octmae_retrieval_ranks, with a
  *     strict tie order (top-k cross-modal retrieval of the COEM evaluation, csrc/retrieval_topk.hip).
  * 30: octmae_mae_compose_nc, octmae_white_border (+ octmae_white_border_ws_floats): the RGB / raw-level panels and the border blanking of
- *     the 2-D half of the validation pass (csrc/recon2d.hip). */
-#define OCTMAE_ABI_VERSION 30
+ *     the 2-D half of the validation pass (csrc/recon2d.hip).
+ * 31: octmae_cam_eigen (+ octmae_cam_eigen_ws_floats), octmae_cam_accumulate: the eigen-smoothed Grad-CAM map by matrix-free power
+ *     iterations and the normalise-flip-fold of test-time-augmentation smoothing (csrc/saliency.hip). */
+#define OCTMAE_ABI_VERSION 31
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -476,7 +478,7 @@ int octmae_white_border(float* imgs, uint8_t* region, float* ws, int B, int T, i
 
 /* ---- saliency: input gradients, Grad-CAM, heat volumes (csrc/saliency.hip) ---------------------------
  * retinal-COEM/src/oph_vis_util/base_cam_retclip_3mod.py (the reference's Grad-CAM base class over pytorch_grad_cam) and its
- * compute_input_gradient=True.  All four are deterministic (no floating-point atomics).
+ * compute_input_gradient=True.  All of them are deterministic (no floating-point atomics).
  *
  * The adjoint of octmae_patch_gather: dimgs f32 [B][C][T][H][W] receives, at the voxels of kept token ids[b][i], row b * nkeep + i of
  * dpatch ([B*nkeep][C*tp*p*p] of the library's 16-bit operand type, conv-weight order (c,u,py,px): what the PatchEmbed dgrad GEMM
@@ -496,6 +498,35 @@ int octmae_patch_scatter(const void* dpatch_lp, const void* ids, int ids_is_i64,
 int octmae_cam_ws_floats(int B, int L, int C);
 int octmae_cam_weights(const float* G, float* w, float* ws, int B, int L, int n_prefix, int C, void* stream);
 int octmae_cam_tokens(const float* A, const float* w, float* cam, int B, int L, int n_prefix, int C, void* stream);
+/* Eigen-smoothed Grad-CAM (pytorch_grad_cam's eigen_smooth: get_2d_projection on the weighted activations) without the [L][C] product
+ * and without an SVD.  Per sample, with M[l][c] = w[c] A[n_prefix + l][c] and Mc = M - (mean over l of M), the map is Mc v1, v1 the
+ * first right singular vector of Mc, found by `iters` power iterations on Mc^T Mc.  Neither M nor Mc is ever stored:
+ *   abar[c] = mean_l A[l][c]                       (the two launches of octmae_cam_weights, on A)
+ *   v = 1 / sqrt(C) in every column, then `iters` times
+ *     u[l] = sum_c q[c] A[l][c] - sum_c q[c] abar[c],  q = v o w          one wave per token row; both sums in the same order
+ *     t[c] = w[c] (sum_l u[l] A[l][c] - abar[c] sum_l u[l])              row splits, folded in ascending order
+ *     v    = t / ||t||_2                                                 one workgroup per sample; ||t|| = 0 leaves v as it is
+ *   proj = Mc v (the u of one more pass), lambda = ||proj||^2, residual = ||Mc^T proj - lambda v||_2 / lambda
+ *   proj is negated when sum_l proj[l] (Mc 1)[l] < 0: the map correlates positively with the centred plain CAM.  (LAPACK's sign is
+ *   arbitrary and pytorch_grad_cam keeps whatever it gets: a deliberate departure.)
+ *   cam[b][l] = relu ? max(0, proj) : proj          f32 [B][L];  residual f32 [B]
+ * 3 launches per iteration and 7 around them; the iteration count is fixed by the argument, there is no convergence test on the device:
+ * `residual` is how a caller sees a map that has not converged (it falls as (sigma2 / sigma1)^(2 iters)).  lambda == 0 (L == 1, constant
+ * columns whose mean is exact, w == 0): the map is all zero and the residual 0.  A non-finite value in the patch rows or the weights of
+ * sample b makes residual[b] NaN (the map of that sample is then unspecified); every other sample is untouched by it.  Deterministic:
+ * no floating-point atomics, every sum in a fixed order.  The n_prefix leading rows are never read.
+ * ws: octmae_cam_eigen_ws_floats(B, L, C) floats (-1 / -2 for sizes it refuses), 16-byte aligned.
+ * -1, before any launch: NULL, non-positive B / L / C / iters, n_prefix < 0, C % 4, A / w / ws not 16-byte aligned.  -2: B above 65535. */
+int octmae_cam_eigen_ws_floats(int B, int L, int C);
+int octmae_cam_eigen(const float* A, const float* w, float* cam, float* residual, float* ws, int B, int L, int n_prefix, int C,
+                     int iters, int relu, void* stream);
+/* One pass of test-time-augmentation smoothing folded into an accumulator (pytorch_grad_cam: scale_cam_image on the map of each
+ * augmented pass, the augmentation undone, then the mean): cam, acc f32 [B][n], n = rows x width,
+ *   acc[b][r][x] (first ? = : +=) weight * (cam[b][r][x'] - mn_b) / (1e-7f + (mx_b - mn_b)),   x' = flip ? width - 1 - x : x,
+ * mn_b / mx_b the minimum / maximum of cam[b] (written to mnmx f32 [B][2] by a first launch).  A constant map contributes 0.
+ * acc and cam must not overlap.  -1, before any launch: NULL, non-positive B / n / width, n % width.  -2: n above 2^31 - 1 - 256. */
+int octmae_cam_accumulate(float* acc, const float* cam, float* mnmx, int B, int n, int width, int flip, float weight, int first,
+                          void* stream);
 /* Heat volume of a coarse saliency map: m f32 [B][t][h][w] -> out uint8 [B][F][H][W].  Per sample mn = min m, mx = max m (written to
  * mnmx f32 [B][2] by a first launch), v = (m - mn) / (1e-7f + (mx - mn)) on the COARSE map, then v resampled linearly along t -> F and
  * bilinearly over (h, w) -> (H, W) with F.interpolate's align_corners=False positions (src = (dst + 0.5) in / out - 0.5, negative -> 0,

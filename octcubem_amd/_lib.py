@@ -97,6 +97,9 @@ SIGNATURES = {
     "octmae_cam_ws_floats": [_i, _i, _i],
     "octmae_cam_weights": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "octmae_cam_tokens": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "octmae_cam_eigen_ws_floats": [_i, _i, _i],
+    "octmae_cam_eigen": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "octmae_cam_accumulate": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "octmae_heatmap": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "octmae_mt_chunk_elems": [],
     "octmae_mt_sumsq": [_vp, _vp, _vp, _i, _vp, _vp],

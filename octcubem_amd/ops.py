@@ -1648,6 +1648,57 @@ def cam_tokens(A: torch.Tensor, w: torch.Tensor, n_prefix: int = 1) -> torch.Ten
     return cam
 
 
+def cam_eigen(A: torch.Tensor, w: torch.Tensor, n_prefix: int = 1, iters: int = 32, relu: bool = True):
+    """Eigen-smoothed Grad-CAM (pytorch_grad_cam's ``eigen_smooth``): ``(cam, residual)``, float32 [B, L] and [B].  Per sample the map is
+    the projection of the centred weighted activations ``Mc = M - mean_l M``, ``M[l, c] = w[c] A[n_prefix + l, c]``, on their first right
+    singular vector, found by ``iters`` power iterations on ``Mc^T Mc`` that never form ``M`` (include/octmae.h: octmae_cam_eigen).
+    The sign is fixed so that the map correlates positively with the centred plain CAM; ``relu=False`` returns the signed projection.
+    ``residual`` = ||Mc^T Mc v - lambda v|| / lambda: about (sigma2 / sigma1)^(2 iters), NaN for a sample with a non-finite value, 0 with
+    an all-zero map where Mc vanishes.  3 iters + 7 deterministic launches; no autograd."""
+    A, w = A.detach(), w.detach()
+    Bn, L, C = _chk_stream(A, n_prefix, "cam_eigen A")
+    _chk(w, F32, "cam_eigen w")
+    if tuple(w.shape) != (Bn, C) or w.device != A.device:
+        raise RuntimeError(f"cam_eigen: w is {tuple(w.shape)} on {w.device}, expected {(Bn, C)} on {A.device}")
+    iters = int(iters)
+    if iters < 1:
+        raise RuntimeError(f"cam_eigen: iters = {iters}, at least one power iteration is needed")
+    n = load().octmae_cam_eigen_ws_floats(Bn, L, C)
+    if n < 0 or Bn > 65535:
+        raise RuntimeError(f"cam_eigen: unsupported size {tuple(A.shape)}")
+    ws = torch.empty((n,), dtype=F32, device=A.device)
+    cam = torch.empty((Bn, L), dtype=F32, device=A.device)
+    res = torch.empty((Bn,), dtype=F32, device=A.device)
+    # per iteration A is read twice (rows, transposed product); once more for the mean, once for the centred plain CAM
+    _launch("cam_eigen", 4.0 * (iters + 2) * Bn * L * C, 4.0 * (2 * iters + 4) * Bn * L * C,
+            lambda: call("octmae_cam_eigen", A.data_ptr(), w.data_ptr(), cam.data_ptr(), res.data_ptr(), ws.data_ptr(), Bn, L, n_prefix, C,
+                         iters, int(bool(relu)), _stream()))
+    return cam, res
+
+
+def cam_accumulate(acc: torch.Tensor, cam: torch.Tensor, width: int, flip: bool, weight: float, first: bool) -> torch.Tensor:
+    """One pass of augmentation smoothing folded into ``acc`` in place (and returned): ``cam``, ``acc`` float32 [B, n] with
+    ``n % width == 0``; ``acc[b, r, x] (first ? = : +=) weight * (cam[b, r, x'] - min_b) / (1e-7 + max_b - min_b)`` with ``x' = width - 1
+    - x`` when ``flip`` (pytorch_grad_cam's scale_cam_image, then the horizontal flip undone).  ``first`` stores, so ``acc`` may be
+    uninitialised.  A constant map contributes 0.  Two launches; no autograd."""
+    cam = cam.detach()
+    _chk(acc, F32, "cam_accumulate acc")
+    _chk(cam, F32, "cam_accumulate cam")
+    width = int(width)
+    if (cam.dim() != 2 or acc.shape != cam.shape or acc.device != cam.device or cam.numel() < 1 or width < 1 or cam.shape[1] % width
+            or acc.requires_grad):
+        raise RuntimeError(f"cam_accumulate: expected float32 acc and cam [B, n] with n % width == 0 on one device, got {tuple(acc.shape)}, "
+                           f"{tuple(cam.shape)} and width {width}")
+    if acc.data_ptr() == cam.data_ptr():
+        raise RuntimeError("cam_accumulate: acc and cam must not be the same buffer")
+    Bn, n = cam.shape
+    mnmx = torch.empty((Bn, 2), dtype=F32, device=cam.device)
+    _launch("cam_accumulate", 4.0 * Bn * n, 4.0 * Bn * n * (3 if first else 4),
+            lambda: call("octmae_cam_accumulate", acc.data_ptr(), cam.data_ptr(), mnmx.data_ptr(), Bn, n, width, int(bool(flip)),
+                         float(weight), int(bool(first)), _stream()))
+    return acc
+
+
 def heatmap(m: torch.Tensor, size) -> torch.Tensor:
     """uint8 [B, F, H, W] heat volume of the float32 map ``m`` [B, t, h, w], ``size`` = (F, H, W) with W % 4 == 0: per sample
     v = (m - min) / (1e-7 + (max - min)) on the coarse map, resampled linearly along t and bilinearly over (h, w)

@@ -11,6 +11,9 @@
                                         and again: these figures are CACHE-WARM, not HBM rates
   Grad-CAM reduction, fused / ATen      ops.cam_weights + ops.cam_tokens against relu((G[:, 1:].mean(1, keepdim=True) * A[:, 1:]).sum(-1))
   heat volume, fused / ATen             ops.heatmap against normalise -> F.interpolate(trilinear) -> floor -> uint8
+  eigen-smoothed map / plain reduction  ops.cam_eigen at 32 iterations against ops.cam_tokens, both behind ops.cam_weights, on the model's
+                                        streams (4 x 5121 x 1024) and at the en-face size (4 x 257 x 1024); cache-warm as above
+  aug_smooth                            grad_cam(aug_smooth=True): six passes and six folds, against one plain grad_cam
 
 HIP events around each call on the launch stream, everything warmed up first, the two forms of a pair alternated inside one loop so that
 both see the same machine; the median and the spread (min .. max) of the repeats are reported.  Until this has run on an MI355X no time
@@ -131,6 +134,34 @@ def main():
     lines += [f"Grad-CAM reduction over A, G f32 {tuple(A.shape)}: {nb / 1e6:.1f} MB read, cache-warm ({a.inner} calls per event pair on the same buffers, which fit the last-level cache); max |fused - ATen| / max |ATen| = {err:.1e}",
               f"  fused HIP kernels     {fmt(tf)}   {nb / statistics.median(tf) / 1e9:7.3f} TB/s algorithmic, cache-warm",
               f"  ATen ops on the GPU   {fmt(ta)}   {nb / statistics.median(ta) / 1e9:7.3f} TB/s algorithmic, cache-warm   x {statistics.median(ta) / statistics.median(tf):.1f}"]
+    # the eigen-smoothed map (32 power iterations: 103 launches) against the plain reduction (3 launches), on the model's own streams and
+    # on random streams of the en-face size; both forms include ops.cam_weights.  Cache-warm as above: A alone is read 66 times per call
+    g2 = torch.Generator().manual_seed(2)
+    enface = (torch.randn(B, 257, 1024, generator=g2).to(dev), torch.randn(B, 257, 1024, generator=g2).to(dev))
+    for label, Ae, Ge, inner in (("ViT-L volume", A, G, max(1, a.inner // 10)), ("en-face image", *enface, a.inner)):
+        plain = lambda: ops.cam_tokens(Ae, ops.cam_weights(Ge, 1), 1)                 # noqa: E731
+        eigen = lambda: ops.cam_eigen(Ae, ops.cam_weights(Ge, 1), 1, 32)              # noqa: E731
+        for _ in range(2):
+            plain(); eigen()
+        residual = eigen()[1]
+        torch.cuda.synchronize()
+        tp, te = [], []
+        for _ in range(a.reps):
+            tp.append(timed(plain, inner)); te.append(timed(eigen, inner))
+        lines += [f"eigen-smoothed map, {label}, A, G f32 {tuple(Ae.shape)}, 32 iterations, cache-warm ({inner} calls per event pair on the same "
+                  f"buffers); residual after 32 iterations: max {float(residual.max()):.1e}",
+                  f"  plain reduction       {fmt(tp)}",
+                  f"  ops.cam_eigen         {fmt(te)}   x {statistics.median(te) / statistics.median(tp):.1f}   "
+                  f"{statistics.median(te) * 1e3 / 103:.1f} us per launch"]
+    # augmentation smoothing: six forward + backward passes and six folds against one plain pass
+    one = lambda: saliency.grad_cam(model, x, tgt)                                     # noqa: E731
+    six = lambda: saliency.grad_cam(model, x, tgt, aug_smooth=True)                    # noqa: E731
+    one(); six()
+    torch.cuda.synchronize()
+    t1, t6 = [], []
+    for _ in range(a.reps):
+        t1.append(timed(one)); t6.append(timed(six))
+    lines += [f"grad_cam, aug_smooth (six passes)   plain {fmt(t1)}   aug_smooth {fmt(t6)}   x {statistics.median(t6) / statistics.median(t1):.2f}"]
     size = (T, H, W)
     hv, hr = ops.heatmap(cam, size), aten_heat(cam, size)
     d = (hv.int() - hr.int()).abs()
