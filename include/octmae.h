@@ -38,14 +38,15 @@ extern "C" {
  * 16: octmae_mae_compose (the reconstruction volumes of the validation pass, csrc/recon.hip).
  * 17: octmae_image_resample, octmae_image_resample_plan (the 2-D image transforms in front of the 2-D towers, csrc/image2d.hip).
  * 18: octmae_rank_counts (the rank counts behind AUROC / average precision of the fine-tune evaluation, csrc/metrics.hip).
- * 19: octmae_retrieval_ranks (the retrieval ranks of the COEM validation off f32 MFMA tiles, csrc/retrieval.hip).
+ * 19: octmae_retrieval_ranks (the retrieval ranks of the COEM validation off f32 MFMA tiles, csrc/retrieval.hip; the tile itself is
+ *     csrc/simtile.hpp, shared with 24 and 29 since 31 without a change to any entry point or to the device code).
  * 20: octmae_mix_batch (mixup / cutmix of a fine-tune batch in place, csrc/mixup.hip).
  * 21: octmae_rank_counts_masked (rank counts over a per-column population: the multi-task evaluation, csrc/metrics.hip).
  * 22: octmae_image_stats, octmae_image_augment, octmae_aug_desc (RandAugment's image operations on the device, csrc/augment2d.hip).
  * 23: octmae_patch_scatter, octmae_cam_weights (+ octmae_cam_ws_floats), octmae_cam_tokens, octmae_heatmap (input gradients, Grad-CAM
  *     and heat volumes, csrc/saliency.hip).
  * 24: octmae_clip_loss_fwd, octmae_clip_loss_bwd (+ octmae_clip_loss_ws_floats): the contrastive loss of the COEM training step and its
- *     gradients off f32 MFMA tiles, csrc/cliploss.hip.
+ *     gradients off the f32 MFMA tiles of 19, csrc/cliploss.hip.
  * 25: octmae_join_fwd, octmae_join_bwd (+ octmae_join_ws_floats): normalise, concatenate and LayerNorm the tower outputs in front of
  *     the COEM classification head, csrc/join.hip.
  * 26: octmae_ln_apply (csrc/layernorm.hip), octmae_gelu_apply (csrc/recompute.hip): the LayerNorm and GELU outputs rebuilt in the

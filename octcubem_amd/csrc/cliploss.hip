@@ -1,6 +1,7 @@
 // The contrastive loss of the COEM training step (retinal-COEM/src/open_clip/loss.py:148-230 ClipLoss, :230-385 ThreeModalityClipLoss):
 // logit_scale * a @ b.T, its transpose, two cross entropies and their autograd, as one walk over f32 MFMA tiles of a . b^T that keeps
-// no [n][m] array -- csrc/retrieval.hip's walk with a log-sum-exp in place of its counts, plus a backward.
+// no [n][m] array -- csrc/retrieval.hip's walk (the tile, its staging and its k loop are csrc/simtile.hpp's) with a log-sum-exp in
+// place of its counts, plus a backward.
 //   a f32 [n][d], b f32 [m][d] (row strides >= d);  s(i, j) = the f32 chain acc = fmaf(a[i][k], b[j][k], acc), k = 0 .. d-1 (retrieval.hip's
 //   score, from v_mfma_f32_32x32x2_f32);  z = scale * s (one rounding; scale is read from device memory);  t_i = i + offset
 //     L = sum_i wr_i (lse_j z(i, j) - z(i, t_i))  +  sum_i wc_i (lse_i' z(i', t_i) - z(i, t_i))          (second sum only with wc)
@@ -22,42 +23,21 @@
 #include <cstdint>
 #include <cmath>
 #include "common.hpp"
+#include "simtile.hpp"
 #include "../../include/octmae.h"
 
 namespace octmae {
 
-constexpr int CL_ROWS = 64;        // rows of the owning side per workgroup
-constexpr int CL_COLS = 64;        // rows of the other side per tile
-constexpr int CL_K = 32;           // k per LDS step
-constexpr int CL_LD = CL_K + 1;    // LDS row pitch of the operand images
-constexpr int CL_GLD = CL_COLS + 1;   // LDS row pitch of the G tile
-constexpr int CL_THREADS = 256;
+constexpr int CL_GLD = SIM_COLS + 1;   // LDS row pitch of the G tile
 constexpr int CL_DC = 256;         // feature columns per backward workgroup: 2 column halves (waves) x CL_NQ accumulators x 32
 constexpr int CL_NQ = 4;
-constexpr int CL_TARGET_WGS = 1024;   // forward workgroups wanted in flight before the columns stop being split
-constexpr int CL_MAX_SPLIT = 64;
-constexpr int CL_SMEM = 2 * CL_ROWS * CL_LD;   // floats: the two operand images; the G tile lies over them
-static_assert(CL_ROWS == 64 && CL_COLS == 64 && CL_THREADS == 256, "2 x 2 waves of 32 x 32");
-static_assert(CL_ROWS * CL_GLD <= CL_SMEM, "the G tile fits over the operand images");
+constexpr int CL_MAX_SPLIT = 64;   // the cap on the forward's column split: its workspace holds one (max, sum) per split and row
+constexpr int CL_SMEM = 2 * SIM_ROWS * SIM_LD;   // floats: the two operand images; the G tile lies over them
+static_assert(SIM_ROWS * CL_GLD <= CL_SMEM, "the G tile fits over the operand images");
 static_assert(CL_DC == 2 * CL_NQ * 32, "two waves side by side, CL_NQ accumulators each");
 
-// dst[r][k] = src[row_of(r)][k0 + k] for the 64 x CL_K image; 0 where row_of(r) < 0 or k0 + k >= d
-template <class RowOf>
-__device__ __forceinline__ void cl_stage(float* __restrict__ dst, const float* __restrict__ src, long long stride, RowOf row_of, int k0,
-                                         int d) {
-#pragma unroll
-  for (int s = 0; s < CL_ROWS * CL_K / CL_THREADS; ++s) {
-    const int e = s * CL_THREADS + (int)threadIdx.x;
-    const int r = e / CL_K, k = e % CL_K;
-    const long long row = row_of(r);
-    float v = 0.0f;
-    if (row >= 0 && k0 + k < d) v = src[row * stride + k0 + k];
-    dst[r * CL_LD + k] = v;
-  }
-}
-
-// acc[g] = s(x, y) for x = i0 + wr * 32 + r (this lane's row) and y = j0 + wc * 32 + (g & 3) + 8 (g >> 2) + 4 h: retrieval.hip's tile,
-// the other side as the MFMA's A operand.  Ends with a barrier: the images may be rewritten.
+// acc[g] = s(x, y) for x = i0 + wr * 32 + r (this lane's row) and y = SIM_COL(j0 + wc * 32, g, h): the tile of csrc/simtile.hpp, the
+// other side as the MFMA's A operand.  Ends with a barrier: the images may be rewritten.
 __device__ __forceinline__ f32x16 cl_score_tile(float* As, float* Bs, const float* __restrict__ x, long long xs, long long i0, long long nx,
                                                 const float* __restrict__ y, long long ys, long long j0, long long ny, int d) {
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -65,21 +45,9 @@ __device__ __forceinline__ f32x16 cl_score_tile(float* As, float* Bs, const floa
   f32x16 acc;
 #pragma unroll
   for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
-  for (int k0 = 0; k0 < d; k0 += CL_K) {
-    cl_stage(As, x, xs, [&](int rr) -> long long { return i0 + rr < nx ? i0 + rr : -1; }, k0, d);
-    cl_stage(Bs, y, ys, [&](int cc) -> long long { return j0 + cc < ny ? j0 + cc : -1; }, k0, d);
-    __syncthreads();
-    const float* pb = &Bs[(wc * 32 + r) * CL_LD + h];
-    const float* pa = &As[(wr * 32 + r) * CL_LD + h];
-    if (d - k0 >= CL_K) {
-#pragma unroll
-      for (int s = 0; s < CL_K / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pb[2 * s], pa[2 * s], acc, 0, 0, 0);
-    } else {
-      const int steps = (d - k0 + 1) / 2;                   // the k past d of an odd tail is a zero pair
-      for (int s = 0; s < steps; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pb[2 * s], pa[2 * s], acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  auto x_row = [&](int rr) -> long long { return i0 + rr < nx ? i0 + rr : -1; };
+  auto y_row = [&](int cc) -> long long { return j0 + cc < ny ? j0 + cc : -1; };
+  SIM_SCORE_TILE(acc, As, Bs, x, xs, x_row, y, ys, y_row);
   return acc;
 }
 
@@ -95,45 +63,38 @@ __device__ __forceinline__ void cl_merge(float& m1, float& s1, float m2, float s
 
 // part[(blockIdx.y * nx + i) * 2 + {0, 1}] = (max, sum) of row i of x over the column tiles this workgroup walks;
 // tsc[i] = s(i, i + offset) from the workgroups with blockIdx.y == 0 when tsc is given
-__global__ __launch_bounds__(CL_THREADS) void clip_lse_kernel(const float* __restrict__ x, long long xs, const float* __restrict__ y,
+__global__ __launch_bounds__(SIM_THREADS) void clip_lse_kernel(const float* __restrict__ x, long long xs, const float* __restrict__ y,
                                                              long long ys, const float* __restrict__ scale_p, float* __restrict__ part,
                                                              float* __restrict__ tsc, long long offset, long long nx, long long ny, int d,
                                                              int col_tiles) {
   __shared__ float smem[CL_SMEM];
-  __shared__ float red[CL_ROWS * 2];
+  __shared__ float red[SIM_ROWS * 2];
   float* As = smem;
-  float* Bs = smem + CL_ROWS * CL_LD;
+  float* Bs = smem + SIM_ROWS * SIM_LD;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave & 1, wc = wave >> 1, r = lane & 31, h = lane >> 5;
-  const long long i0 = (long long)blockIdx.x * CL_ROWS;
+  const long long i0 = (long long)blockIdx.x * SIM_ROWS;
   const float scale = *scale_p;
 
   if (tsc != nullptr && blockIdx.y == 0) {                      // workgroup-uniform
     float t = 0.0f;
-    for (int k0 = 0; k0 < d; k0 += CL_K) {
-      cl_stage(As, x, xs, [&](int rr) -> long long { return i0 + rr < nx ? i0 + rr : -1; }, k0, d);
-      cl_stage(Bs, y, ys, [&](int rr) -> long long { return i0 + rr < nx ? i0 + rr + offset : -1; }, k0, d);   // n + offset <= m: checked
-      __syncthreads();
-      if (tid < CL_ROWS) {
-        const int kc = d - k0 < CL_K ? d - k0 : CL_K;
-        for (int k = 0; k < kc; ++k) t = __builtin_fmaf(As[tid * CL_LD + k], Bs[tid * CL_LD + k], t);
-      }
-      __syncthreads();
-    }
-    if (tid < CL_ROWS && i0 + tid < nx) tsc[i0 + tid] = t;
+    auto x_row = [&](int rr) -> long long { return i0 + rr < nx ? i0 + rr : -1; };
+    auto t_row = [&](int rr) -> long long { return i0 + rr < nx ? i0 + rr + offset : -1; };   // n + offset <= m: checked
+    SIM_TARGET_CHAIN(t, As, Bs, x, xs, x_row, y, ys, t_row);
+    if (tid < SIM_ROWS && i0 + tid < nx) tsc[i0 + tid] = t;
   }
 
   const int il = wr * 32 + r;
   float mx = -INFINITY, sm = 0.0f;
   for (int ct = (int)blockIdx.y; ct < col_tiles; ct += (int)gridDim.y) {
-    const long long j0 = (long long)ct * CL_COLS;
+    const long long j0 = (long long)ct * SIM_COLS;
     const f32x16 acc = cl_score_tile(As, Bs, x, xs, i0, nx, y, ys, j0, ny, d);
     float z[16];
     float tmax = -INFINITY;
     bool any = false;
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-      const bool in = j0 + wc * 32 + (g & 3) + 8 * (g >> 2) + 4 * h < ny;
+      const bool in = SIM_COL(j0 + wc * 32, g, h) < ny;
       z[g] = scale * acc[g];
       if (in) tmax = fmaxf(tmax, z[g]);
       any |= in;
@@ -143,7 +104,7 @@ __global__ __launch_bounds__(CL_THREADS) void clip_lse_kernel(const float* __res
       float s = sm * (mx == nm ? 1.0f : expf(mx - nm));
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const bool in = j0 + wc * 32 + (g & 3) + 8 * (g >> 2) + 4 * h < ny;
+        const bool in = SIM_COL(j0 + wc * 32, g, h) < ny;
         if (in) s += expf(z[g] - nm);
       }
       sm = s;
@@ -176,9 +137,9 @@ __global__ __launch_bounds__(CL_THREADS) void clip_lse_kernel(const float* __res
 }
 
 // lse[i] = log sum over the `split` partials of row i, merged in order
-__global__ __launch_bounds__(CL_THREADS) void clip_finish_kernel(const float* __restrict__ part, int split, long long nx,
+__global__ __launch_bounds__(SIM_THREADS) void clip_finish_kernel(const float* __restrict__ part, int split, long long nx,
                                                                 float* __restrict__ lse) {
-  const long long i = (long long)blockIdx.x * CL_THREADS + threadIdx.x;
+  const long long i = (long long)blockIdx.x * SIM_THREADS + threadIdx.x;
   if (i >= nx) return;
   float m = part[i * 2], s = part[i * 2 + 1];
   for (int p = 1; p < split; ++p) cl_merge(m, s, part[((long long)p * nx + i) * 2], part[((long long)p * nx + i) * 2 + 1]);
@@ -188,19 +149,19 @@ __global__ __launch_bounds__(CL_THREADS) void clip_finish_kernel(const float* __
 // fixed-order float64 sum of one value per thread-strided index: v(i) for i = tid, tid + 256, ...; then a tree over the 256 threads
 template <class F>
 __device__ __forceinline__ double cl_block_sum(long long n, F v) {
-  __shared__ double acc[CL_THREADS];
+  __shared__ double acc[SIM_THREADS];
   double t = 0.0;
-  for (long long i = threadIdx.x; i < n; i += CL_THREADS) t += v(i);
+  for (long long i = threadIdx.x; i < n; i += SIM_THREADS) t += v(i);
   acc[threadIdx.x] = t;
   __syncthreads();
-  for (int w = CL_THREADS / 2; w > 0; w >>= 1) {
+  for (int w = SIM_THREADS / 2; w > 0; w >>= 1) {
     if ((int)threadIdx.x < w) acc[threadIdx.x] += acc[threadIdx.x + w];
     __syncthreads();
   }
   return acc[0];
 }
 
-__global__ __launch_bounds__(CL_THREADS) void clip_loss_kernel(const float* __restrict__ scale_p, const float* __restrict__ wr,
+__global__ __launch_bounds__(SIM_THREADS) void clip_loss_kernel(const float* __restrict__ scale_p, const float* __restrict__ wr,
                                                               const float* __restrict__ wc, const float* __restrict__ lse_row,
                                                               const float* __restrict__ lse_col, const float* __restrict__ tsc,
                                                               long long offset, long long n, float* __restrict__ loss) {
@@ -214,7 +175,7 @@ __global__ __launch_bounds__(CL_THREADS) void clip_loss_kernel(const float* __re
   if (threadIdx.x == 0) *loss = (float)L;
 }
 
-__global__ __launch_bounds__(CL_THREADS) void clip_dscale_kernel(const float* __restrict__ gout, const float* __restrict__ dsp, long long n,
+__global__ __launch_bounds__(SIM_THREADS) void clip_dscale_kernel(const float* __restrict__ gout, const float* __restrict__ dsp, long long n,
                                                                 float* __restrict__ dscale) {
   const double S = cl_block_sum(n, [&](long long i) -> double { return (double)dsp[i]; });
   if (threadIdx.x == 0) *dscale = (float)((double)*gout * S);
@@ -230,7 +191,7 @@ __device__ __forceinline__ float cl_weight(const float* __restrict__ w, long lon
 //   G(x, y) = wx_x (exp(z - lx_x) - [y - x == delta]) + wy_y (exp(z - ly_y) - [y - x == delta])
 // (a term whose weight table is NULL is left out: its log-sum-exps are not read).  dsp[x] = sum_y G(x, y) s(x, y) from the
 // workgroups of chunk 0 when dsp is given.  dx == NULL: only dsp.
-__global__ __launch_bounds__(CL_THREADS) void clip_grad_kernel(const float* __restrict__ x, long long xs, const float* __restrict__ y,
+__global__ __launch_bounds__(SIM_THREADS) void clip_grad_kernel(const float* __restrict__ x, long long xs, const float* __restrict__ y,
                                                               long long ys, const float* __restrict__ scale_p,
                                                               const float* __restrict__ gout, const float* __restrict__ wx, long long wx_shift,
                                                               long long wx_cnt, const float* __restrict__ lx, const float* __restrict__ wy,
@@ -238,13 +199,13 @@ __global__ __launch_bounds__(CL_THREADS) void clip_grad_kernel(const float* __re
                                                               long long delta, float* __restrict__ dx, long long dxs,
                                                               float* __restrict__ dsp, long long nx, long long ny, int d) {
   __shared__ float smem[CL_SMEM];
-  __shared__ double redd[CL_ROWS];
+  __shared__ double redd[SIM_ROWS];
   float* As = smem;
-  float* Bs = smem + CL_ROWS * CL_LD;
+  float* Bs = smem + SIM_ROWS * SIM_LD;
   float* Gs = smem;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave & 1, wc = wave >> 1, r = lane & 31, h = lane >> 5;
-  const long long i0 = (long long)blockIdx.x * CL_ROWS;
+  const long long i0 = (long long)blockIdx.x * SIM_ROWS;
   const int c0 = (int)blockIdx.y * CL_DC;
   const float scale = *scale_p;
   const int il = wr * 32 + r;
@@ -261,13 +222,13 @@ __global__ __launch_bounds__(CL_THREADS) void clip_grad_kernel(const float* __re
 #pragma unroll
     for (int g = 0; g < 16; ++g) out[q][g] = 0.0f;
 
-  const long long tiles = (ny + CL_COLS - 1) / CL_COLS;
+  const long long tiles = (ny + SIM_COLS - 1) / SIM_COLS;
   for (long long ct = 0; ct < tiles; ++ct) {
-    const long long j0 = ct * CL_COLS;
+    const long long j0 = ct * SIM_COLS;
     const f32x16 acc = cl_score_tile(As, Bs, x, xs, i0, nx, y, ys, j0, ny, d);      // ends with a barrier: Gs may be written
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-      const int yl = wc * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
+      const int yl = SIM_COL(wc * 32, g, h);
       const long long yj = j0 + yl;
       float G = 0.0f;
       if (xin && yj < ny) {
@@ -284,7 +245,7 @@ __global__ __launch_bounds__(CL_THREADS) void clip_grad_kernel(const float* __re
     if (want_dx) {
       const float* pg = &Gs[il * CL_GLD + h];                    // MFMA A operand: lane = row x of the block, k = y = 2 step + h
 #pragma unroll 8
-      for (int s = 0; s < CL_COLS / 2; ++s) {
+      for (int s = 0; s < SIM_COLS / 2; ++s) {
         const float ga = pg[2 * s];
         const long long yrow = j0 + 2 * s + h;
         const bool yok = yrow < ny;
@@ -309,7 +270,7 @@ __global__ __launch_bounds__(CL_THREADS) void clip_grad_kernel(const float* __re
       const int c = c0 + wc * (CL_NQ * 32) + q * 32 + r;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const long long row = i0 + wr * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
+        const long long row = SIM_COL(i0 + wr * 32, g, h);
         if (row < nx && c < d) dx[row * dxs + c] = coef * out[q][g];
       }
     }
@@ -328,21 +289,14 @@ struct ClPlan {
   int split_a, split_b;
 };
 
-static int cl_split(long long row_blocks, int col_tiles) {
-  long long s = (CL_TARGET_WGS + row_blocks - 1) / row_blocks;
-  if (s > col_tiles) s = col_tiles;
-  if (s > CL_MAX_SPLIT) s = CL_MAX_SPLIT;
-  return s < 1 ? 1 : (int)s;
-}
-
 static bool cl_plan(long long n, long long m, ClPlan* p) {
   if (n <= 0 || m <= 0 || n > 0x7fffffffLL || m > 0x7fffffffLL) return false;
-  p->row_blocks_a = (n + CL_ROWS - 1) / CL_ROWS;
-  p->row_blocks_b = (m + CL_ROWS - 1) / CL_ROWS;
-  p->tiles_a = (int)((m + CL_COLS - 1) / CL_COLS);
-  p->tiles_b = (int)((n + CL_COLS - 1) / CL_COLS);
-  p->split_a = cl_split(p->row_blocks_a, p->tiles_a);
-  p->split_b = cl_split(p->row_blocks_b, p->tiles_b);
+  p->row_blocks_a = (n + SIM_ROWS - 1) / SIM_ROWS;
+  p->row_blocks_b = (m + SIM_ROWS - 1) / SIM_ROWS;
+  p->tiles_a = (int)((m + SIM_COLS - 1) / SIM_COLS);
+  p->tiles_b = (int)((n + SIM_COLS - 1) / SIM_COLS);
+  p->split_a = (int)sim_split(p->row_blocks_a, p->tiles_a, CL_MAX_SPLIT);
+  p->split_b = (int)sim_split(p->row_blocks_b, p->tiles_b, CL_MAX_SPLIT);
   return true;
 }
 
@@ -372,21 +326,21 @@ extern "C" int octmae_clip_loss_fwd(const float* a, long long a_stride, const fl
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* part_a = ws;
   float* part_b = ws + 2 * (long long)p.split_a * n;
-  hipLaunchKernelGGL(clip_lse_kernel, dim3((unsigned)p.row_blocks_a, (unsigned)p.split_a), dim3(CL_THREADS), 0, st, a, a_stride, b, b_stride,
+  hipLaunchKernelGGL(clip_lse_kernel, dim3((unsigned)p.row_blocks_a, (unsigned)p.split_a), dim3(SIM_THREADS), 0, st, a, a_stride, b, b_stride,
                      scale, part_a, tscore, offset, n, m, d, p.tiles_a);
   OCTMAE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(clip_finish_kernel, dim3((unsigned)((n + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, st, part_a, p.split_a, n,
+  hipLaunchKernelGGL(clip_finish_kernel, dim3((unsigned)((n + SIM_THREADS - 1) / SIM_THREADS)), dim3(SIM_THREADS), 0, st, part_a, p.split_a, n,
                      lse_row);
   OCTMAE_LAUNCH_CHECK();
   if (wc) {
-    hipLaunchKernelGGL(clip_lse_kernel, dim3((unsigned)p.row_blocks_b, (unsigned)p.split_b), dim3(CL_THREADS), 0, st, b, b_stride, a, a_stride,
+    hipLaunchKernelGGL(clip_lse_kernel, dim3((unsigned)p.row_blocks_b, (unsigned)p.split_b), dim3(SIM_THREADS), 0, st, b, b_stride, a, a_stride,
                        scale, part_b, (float*)nullptr, 0LL, m, n, d, p.tiles_b);
     OCTMAE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(clip_finish_kernel, dim3((unsigned)((m + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, st, part_b, p.split_b, m,
+    hipLaunchKernelGGL(clip_finish_kernel, dim3((unsigned)((m + SIM_THREADS - 1) / SIM_THREADS)), dim3(SIM_THREADS), 0, st, part_b, p.split_b, m,
                        lse_col);
     OCTMAE_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(clip_loss_kernel, dim3(1), dim3(CL_THREADS), 0, st, scale, wr, wc, lse_row, lse_col, tscore, offset, n, loss);
+  hipLaunchKernelGGL(clip_loss_kernel, dim3(1), dim3(SIM_THREADS), 0, st, scale, wr, wc, lse_row, lse_col, tscore, offset, n, loss);
   OCTMAE_LAUNCH_CHECK();
   return 0;
 }
@@ -407,18 +361,18 @@ extern "C" int octmae_clip_loss_bwd(const float* a, long long a_stride, const fl
   const unsigned chunks = (unsigned)((d + CL_DC - 1) / CL_DC);
   if (da || dscale) {
     // the a side: x = a (own term: wr, lse_row), y = b (wc seen at j - offset, lse_col); partner y - x == offset
-    hipLaunchKernelGGL(clip_grad_kernel, dim3((unsigned)p.row_blocks_a, da ? chunks : 1u), dim3(CL_THREADS), 0, st, a, a_stride, b, b_stride,
+    hipLaunchKernelGGL(clip_grad_kernel, dim3((unsigned)p.row_blocks_a, da ? chunks : 1u), dim3(SIM_THREADS), 0, st, a, a_stride, b, b_stride,
                        scale, gout, wr, 0LL, n, lse_row, wc, offset, n, lse_col, offset, da, da_stride, dscale ? ws : (float*)nullptr, n, m, d);
     OCTMAE_LAUNCH_CHECK();
   }
   if (db) {
     // the b side: x = b (own term: wc seen at j - offset, lse_col), y = a (wr, lse_row); partner y - x == -offset
-    hipLaunchKernelGGL(clip_grad_kernel, dim3((unsigned)p.row_blocks_b, chunks), dim3(CL_THREADS), 0, st, b, b_stride, a, a_stride, scale, gout,
+    hipLaunchKernelGGL(clip_grad_kernel, dim3((unsigned)p.row_blocks_b, chunks), dim3(SIM_THREADS), 0, st, b, b_stride, a, a_stride, scale, gout,
                        wc, offset, n, lse_col, wr, 0LL, n, lse_row, -offset, db, db_stride, (float*)nullptr, m, n, d);
     OCTMAE_LAUNCH_CHECK();
   }
   if (dscale) {
-    hipLaunchKernelGGL(clip_dscale_kernel, dim3(1), dim3(CL_THREADS), 0, st, gout, ws, n, dscale);
+    hipLaunchKernelGGL(clip_dscale_kernel, dim3(1), dim3(SIM_THREADS), 0, st, gout, ws, n, dscale);
     OCTMAE_LAUNCH_CHECK();
   }
   return 0;

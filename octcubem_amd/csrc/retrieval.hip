@@ -12,8 +12,9 @@
 // plain VALU fmaf chain yields, which is how t_i is made: the workgroup stages its 64 rows of a beside the 64 TARGET rows of b through
 // the same LDS tiles and 64 threads run the chain.  A bit copy of the target row elsewhere in b therefore ties exactly.
 //
-// One workgroup of 256 threads (2 x 2 waves) owns RR_ROWS = 64 rows of a and walks column tiles of RR_COLS = 64 rows of b; per tile it
-// walks d in LDS steps of RR_K = 32 (two [64][33] f32 images, 16.5 KiB: eight workgroups per CU).  A wave holds one 32 x 32 accumulator,
+// The tile is csrc/simtile.hpp's, which retrieval_topk.hip and cliploss.hip walk too: one workgroup of 256 threads (2 x 2 waves) owns
+// SIM_ROWS = 64 rows of a and walks column tiles of SIM_COLS = 64 rows of b; per tile it walks d in LDS steps of SIM_K = 32 (two
+// [64][33] f32 images, 16.5 KiB: eight workgroups per CU).  A wave holds one 32 x 32 accumulator,
 // TRANSPOSED: b is the MFMA's A operand and a its B operand, so a lane's 16 registers are 16 columns j of ONE row i and the four counters
 // of that row live in four registers across the whole column loop.  Tails are masked by index: a row past n or a column past m takes no
 // part in any count (its LDS image is zero, not a sentinel score -- any f32 is a legal score), and the k loop ends at d (an odd d runs
@@ -24,60 +25,37 @@
 //   of the library hold the same code.  No fast-math flag on this file.
 #include <cstdint>
 #include "common.hpp"
+#include "simtile.hpp"
 #include "../../include/octmae.h"
 
 namespace octmae {
 
-constexpr int RR_ROWS = 64;        // R: rows of a per workgroup
-constexpr int RR_COLS = 64;        // C: rows of b (columns of the score matrix) per tile
-constexpr int RR_K = 32;           // K: k per LDS step (16 MFMA steps of 2)
-constexpr int RR_LD = RR_K + 1;    // LDS row pitch in floats: the 32 rows a half-wave reads land on 32 banks
-constexpr int RR_THREADS = 256;
-constexpr int RR_TARGET_WGS = 1024;   // workgroups wanted in flight before the columns stop being split (256 CUs x 4)
-static_assert(RR_ROWS == RR_COLS && RR_ROWS == 64 && RR_THREADS == 256, "2 x 2 waves of 32 x 32, one staging routine for both operands");
-static_assert(RR_K % 2 == 0 && (RR_ROWS * RR_K) % RR_THREADS == 0, "whole MFMA steps, whole staging passes");
-
-// dst[r][k] = src[row_of(r)][k0 + k] for the 64 x RR_K image; 0 where row_of(r) < 0 or k0 + k >= d (masked again by index downstream)
-template <class RowOf>
-__device__ __forceinline__ void rr_stage(float* __restrict__ dst, const float* __restrict__ src, long long stride, RowOf row_of, int k0,
-                                         int d) {
-#pragma unroll
-  for (int s = 0; s < RR_ROWS * RR_K / RR_THREADS; ++s) {
-    const int e = s * RR_THREADS + (int)threadIdx.x;
-    const int r = e / RR_K, k = e % RR_K;
-    const long long row = row_of(r);
-    float v = 0.0f;
-    if (row >= 0 && k0 + k < d) v = src[row * stride + k0 + k];
-    dst[r * RR_LD + k] = v;
-  }
-}
-
 // out[0] = 1 where a target is no column of b or is not kept (the entry point reads it back before the main launch)
-__global__ __launch_bounds__(RR_THREADS) void retrieval_check_kernel(const int* __restrict__ target, const uint8_t* __restrict__ keep,
+__global__ __launch_bounds__(SIM_THREADS) void retrieval_check_kernel(const int* __restrict__ target, const uint8_t* __restrict__ keep,
                                                                     long long n, int m, int* __restrict__ flag) {
-  const long long i = (long long)blockIdx.x * RR_THREADS + threadIdx.x;
+  const long long i = (long long)blockIdx.x * SIM_THREADS + threadIdx.x;
   if (i >= n) return;
   const long long t = target ? (long long)target[i] : i;
   if (t < 0 || t >= m || (keep && keep[t] == 0)) *flag = 1;
 }
 
-__global__ __launch_bounds__(RR_THREADS) void retrieval_ranks_kernel(const float* __restrict__ a, long long as,
+__global__ __launch_bounds__(SIM_THREADS) void retrieval_ranks_kernel(const float* __restrict__ a, long long as,
                                                                     const float* __restrict__ b, long long bs,
                                                                     const int* __restrict__ target, const uint8_t* __restrict__ keep,
                                                                     const int* __restrict__ row_group, const int* __restrict__ col_group,
                                                                     int* __restrict__ out, long long n, int m, int d, int col_tiles) {
-  __shared__ float As[RR_ROWS * RR_LD];
-  __shared__ float Bs[RR_COLS * RR_LD];
-  __shared__ float ts[RR_ROWS];      // t_i
-  __shared__ int tg[RR_ROWS];        // target[i], -1 past n
-  __shared__ int cgs[RR_COLS];       // col_group[j]
-  __shared__ int flg[RR_COLS];       // bit 0: j takes part in the ranking, bit 1: j < m
+  __shared__ float As[SIM_ROWS * SIM_LD];
+  __shared__ float Bs[SIM_COLS * SIM_LD];
+  __shared__ float ts[SIM_ROWS];      // t_i
+  __shared__ int tg[SIM_ROWS];        // target[i], -1 past n
+  __shared__ int cgs[SIM_COLS];       // col_group[j]
+  __shared__ int flg[SIM_COLS];       // bit 0: j takes part in the ranking, bit 1: j < m
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave & 1, wc = wave >> 1, r = lane & 31, h = lane >> 5;
-  const long long i0 = (long long)blockIdx.x * RR_ROWS;
+  const long long i0 = (long long)blockIdx.x * SIM_ROWS;
   const bool grouped = row_group != nullptr;
 
-  if (tid < RR_ROWS) {
+  if (tid < SIM_ROWS) {
     const long long i = i0 + tid;
     tg[tid] = i < n ? (target ? target[i] : (int)i) : -1;
   }
@@ -87,17 +65,9 @@ __global__ __launch_bounds__(RR_THREADS) void retrieval_ranks_kernel(const float
   // ---- t_i: the same chain on the VALU, a rows against their target rows of b
   {
     float t = 0.0f;
-    for (int k0 = 0; k0 < d; k0 += RR_K) {
-      rr_stage(As, a, as, a_row, k0, d);
-      rr_stage(Bs, b, bs, [&](int rr) -> long long { return (long long)tg[rr]; }, k0, d);
-      __syncthreads();
-      if (tid < RR_ROWS) {
-        const int kc = d - k0 < RR_K ? d - k0 : RR_K;
-        for (int k = 0; k < kc; ++k) t = __builtin_fmaf(As[tid * RR_LD + k], Bs[tid * RR_LD + k], t);
-      }
-      __syncthreads();
-    }
-    if (tid < RR_ROWS) ts[tid] = t;
+    auto t_row = [&](int rr) -> long long { return (long long)tg[rr]; };
+    SIM_TARGET_CHAIN(t, As, Bs, a, as, a_row, b, bs, t_row);
+    if (tid < SIM_ROWS) ts[tid] = t;
   }
   __syncthreads();
 
@@ -109,35 +79,21 @@ __global__ __launch_bounds__(RR_THREADS) void retrieval_ranks_kernel(const float
   int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
 
   for (int ct = (int)blockIdx.y; ct < col_tiles; ct += (int)gridDim.y) {
-    const long long j0 = (long long)ct * RR_COLS;
+    const long long j0 = (long long)ct * SIM_COLS;
     f32x16 acc;
 #pragma unroll
     for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
-    if (tid < RR_COLS) {
+    if (tid < SIM_COLS) {
       const long long j = j0 + tid;
       const bool in = j < m;
       flg[tid] = in ? (2 | ((keep == nullptr || keep[j] != 0) ? 1 : 0)) : 0;
       cgs[tid] = in && grouped ? col_group[j] : 0;
     }
-    for (int k0 = 0; k0 < d; k0 += RR_K) {
-      rr_stage(As, a, as, a_row, k0, d);
-      rr_stage(Bs, b, bs, [&](int cc) -> long long { return j0 + cc < m ? j0 + cc : -1; }, k0, d);
-      __syncthreads();
-      const float* pb = &Bs[(wc * 32 + r) * RR_LD + h];      // MFMA A operand: lane = score column j, k = 2 step + h
-      const float* pa = &As[il * RR_LD + h];                 // MFMA B operand: lane = score row i
-      if (d - k0 >= RR_K) {
-#pragma unroll
-        for (int s = 0; s < RR_K / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pb[2 * s], pa[2 * s], acc, 0, 0, 0);
-      } else {
-        const int steps = (d - k0 + 1) / 2;                   // the k past d of an odd tail is a zero pair
-        for (int s = 0; s < steps; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pb[2 * s], pa[2 * s], acc, 0, 0, 0);
-      }
-      __syncthreads();
-    }
-    // acc[g] = s(i, j) with j = j0 + wc * 32 + (g & 3) + 8 (g >> 2) + 4 h
+    auto b_row = [&](int cc) -> long long { return j0 + cc < m ? j0 + cc : -1; };
+    SIM_SCORE_TILE(acc, As, Bs, a, as, a_row, b, bs, b_row);
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-      const int jl = wc * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
+      const int jl = SIM_COL(wc * 32, g, h);
       const int f = flg[jl];
       const long long j = j0 + jl;
       const float s = acc[g];
@@ -177,14 +133,14 @@ extern "C" int octmae_retrieval_ranks(const float* a, long long a_stride, const 
   if (m > 0x7fffffffLL) return -2;                        // a count can reach m; target holds int column indices
   if (!target && n != m) return -2;
   if ((row_group == nullptr) != (col_group == nullptr)) return -2;
-  const long long row_blocks = (n + RR_ROWS - 1) / RR_ROWS;
+  const long long row_blocks = (n + SIM_ROWS - 1) / SIM_ROWS;
   if (row_blocks > 0x7fffffffLL) return -2;               // the row block is the grid's x
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(out, 0, (size_t)n * 4 * sizeof(int), st);
   if (e != hipSuccess) return (int)e;
   if (target || keep) {
     // every target must be a kept column of b (an index past m would also be read as a row of b): one flag through out[0]
-    hipLaunchKernelGGL(retrieval_check_kernel, dim3((unsigned)((n + RR_THREADS - 1) / RR_THREADS)), dim3(RR_THREADS), 0, st, target, keep,
+    hipLaunchKernelGGL(retrieval_check_kernel, dim3((unsigned)((n + SIM_THREADS - 1) / SIM_THREADS)), dim3(SIM_THREADS), 0, st, target, keep,
                        n, (int)m, out);
     OCTMAE_LAUNCH_CHECK();
     int bad = 0;
@@ -196,12 +152,9 @@ extern "C" int octmae_retrieval_ranks(const float* a, long long a_stride, const 
       return e != hipSuccess ? (int)e : -2;
     }
   }
-  const int col_tiles = (int)((m + RR_COLS - 1) / RR_COLS);
-  long long split = (RR_TARGET_WGS + row_blocks - 1) / row_blocks;
-  if (split > col_tiles) split = col_tiles;
-  if (split > 65535) split = 65535;
-  if (split < 1) split = 1;
-  hipLaunchKernelGGL(retrieval_ranks_kernel, dim3((unsigned)row_blocks, (unsigned)split), dim3(RR_THREADS), 0, st, a, a_stride, b, b_stride,
+  const int col_tiles = (int)((m + SIM_COLS - 1) / SIM_COLS);
+  const long long split = sim_split(row_blocks, col_tiles, 65535);   // the grid's y
+  hipLaunchKernelGGL(retrieval_ranks_kernel, dim3((unsigned)row_blocks, (unsigned)split), dim3(SIM_THREADS), 0, st, a, a_stride, b, b_stride,
                      target, keep, row_group, col_group, out, n, (int)m, d, col_tiles);
   OCTMAE_LAUNCH_CHECK();
   return 0;

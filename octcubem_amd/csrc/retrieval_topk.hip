@@ -8,9 +8,9 @@
 //     (s1, j1) comes before (s2, j2) iff s1 > s2 || (s1 == s2 && j1 < j2): IEEE comparisons, a STRICT order on the candidates of a row
 //     out[i][0 .. k) = the first k candidates in that order; a row with c < k candidates has idx -1, score -inf in slots c .. k-1
 //
-// The walk is retrieval_ranks_kernel's, restated (that file is left alone, its device code cannot change): 256 threads as 2 x 2 waves,
-// RT_ROWS = 64 rows of a per workgroup, column tiles of RT_COLS = 64 rows of b, d in LDS steps of RT_K = 32, the accumulator transposed
-// so that a lane holds 16 columns of one row; tails are masked by index, an odd d ends on a zero operand pair.
+// The walk is retrieval_ranks_kernel's, from the same header (csrc/simtile.hpp): 256 threads as 2 x 2 waves, SIM_ROWS = 64 rows of a
+// per workgroup, column tiles of SIM_COLS = 64 rows of b, d in LDS steps of SIM_K = 32, the accumulator transposed so that a lane
+// holds 16 columns of one row; tails are masked by index, an odd d ends on a zero operand pair.
 // Selection: per row a sorted list of k (score, index) pairs in LDS (pitch RT_KMAX + 1: the 32 rows a half-wave touches at one
 // position land on 32 banks).  After a tile's k loop every lane tests its 16 scores against the row's k-th entry and sets one bit
 // per passing column in the row's 64-bit mask (an integer OR in LDS), and the tile is spilled to a [64][65] LDS image that ALIASES the
@@ -28,23 +28,16 @@
 //   hold the same code.  No fast-math flag on this file.
 #include <cstdint>
 #include "common.hpp"
+#include "simtile.hpp"
 #include "../../include/octmae.h"
 
 namespace octmae {
 
-constexpr int RT_ROWS = 64;        // R: rows of a per workgroup
-constexpr int RT_COLS = 64;        // C: rows of b (columns of the score matrix) per tile
-constexpr int RT_K = 32;           // K: k per LDS step (16 MFMA steps of 2)
-constexpr int RT_LD = RT_K + 1;    // LDS row pitch of the operand images in floats
-constexpr int RT_THREADS = 256;
-constexpr int RT_TARGET_WGS = 1024;   // workgroups wanted in flight before the columns stop being split (256 CUs x 4)
 constexpr int RT_KMAX = 32;        // the largest k: one list entry per lane of a half-wave in the merge
 constexpr int RT_LP = RT_KMAX + 1; // list pitch
-constexpr int RT_SP = RT_COLS + 1; // pitch of the spilled score tile
+constexpr int RT_SP = SIM_COLS + 1; // pitch of the spilled score tile
 constexpr int RT_MERGE_THREADS = 64;
-static_assert(RT_ROWS == RT_COLS && RT_ROWS == 64 && RT_THREADS == 256, "2 x 2 waves of 32 x 32, one staging routine for both operands");
-static_assert(RT_K % 2 == 0 && (RT_ROWS * RT_K) % RT_THREADS == 0, "whole MFMA steps, whole staging passes");
-static_assert(RT_ROWS * RT_SP <= (RT_ROWS + RT_COLS) * RT_LD, "the spilled tile fits the two operand images it aliases");
+static_assert(SIM_ROWS * RT_SP <= (SIM_ROWS + SIM_COLS) * SIM_LD, "the spilled tile fits the two operand images it aliases");
 static_assert(2 * RT_KMAX == RT_MERGE_THREADS, "the merge holds two lists of RT_KMAX, one entry per lane");
 
 struct RtPair {
@@ -56,45 +49,30 @@ static_assert(sizeof(RtPair) == 8, "ws holds [split][n][k] pairs of 8 bytes");
 // (s1, j1) before (s2, j2): the strict order of the contract
 __device__ __forceinline__ bool rt_before(float s1, int j1, float s2, int j2) { return s1 > s2 || (s1 == s2 && j1 < j2); }
 
-// dst[r][k] = src[row_of(r)][k0 + k] for the 64 x RT_K image; 0 where row_of(r) < 0 or k0 + k >= d (masked again by index downstream)
-template <class RowOf>
-__device__ __forceinline__ void rt_stage(float* __restrict__ dst, const float* __restrict__ src, long long stride, RowOf row_of, int k0,
-                                         int d) {
-#pragma unroll
-  for (int s = 0; s < RT_ROWS * RT_K / RT_THREADS; ++s) {
-    const int e = s * RT_THREADS + (int)threadIdx.x;
-    const int r = e / RT_K, k = e % RT_K;
-    const long long row = row_of(r);
-    float v = 0.0f;
-    if (row >= 0 && k0 + k < d) v = src[row * stride + k0 + k];
-    dst[r * RT_LD + k] = v;
-  }
-}
-
 // pairs == nullptr: the lists are final and go to out_idx / out_score; otherwise list y of row i goes to pairs[(y n + i) k ..]
-__global__ __launch_bounds__(RT_THREADS) void retrieval_topk_kernel(const float* __restrict__ a, long long as,
+__global__ __launch_bounds__(SIM_THREADS) void retrieval_topk_kernel(const float* __restrict__ a, long long as,
                                                                    const float* __restrict__ b, long long bs,
                                                                    const uint8_t* __restrict__ keep, const int* __restrict__ row_group,
                                                                    const int* __restrict__ col_group, int kk, int* __restrict__ out_idx,
                                                                    float* __restrict__ out_score, RtPair* __restrict__ pairs, long long n,
                                                                    int m, int d, int col_tiles) {
-  __shared__ float ops[(RT_ROWS + RT_COLS) * RT_LD];   // the operand images; between two barriers the spilled score tile [64][RT_SP]
-  __shared__ float ls[RT_ROWS * RT_LP];                // the lists: scores, descending
-  __shared__ int lj[RT_ROWS * RT_LP];                  //            and their columns
-  __shared__ int cnt[RT_ROWS];                         // filled entries of a list
-  __shared__ unsigned pass[RT_ROWS * 2];               // the columns of this tile that passed the row's prefilter, one bit each
-  __shared__ int rgs[RT_ROWS];                         // row_group[i]
-  __shared__ int cgs[RT_COLS];                         // col_group[j]
-  __shared__ int flg[RT_COLS];                         // 1: j < m and kept
+  __shared__ float ops[(SIM_ROWS + SIM_COLS) * SIM_LD];   // the operand images; between two barriers the spilled score tile [64][RT_SP]
+  __shared__ float ls[SIM_ROWS * RT_LP];                // the lists: scores, descending
+  __shared__ int lj[SIM_ROWS * RT_LP];                  //            and their columns
+  __shared__ int cnt[SIM_ROWS];                         // filled entries of a list
+  __shared__ unsigned pass[SIM_ROWS * 2];               // the columns of this tile that passed the row's prefilter, one bit each
+  __shared__ int rgs[SIM_ROWS];                         // row_group[i]
+  __shared__ int cgs[SIM_COLS];                         // col_group[j]
+  __shared__ int flg[SIM_COLS];                         // 1: j < m and kept
   float* As = ops;
-  float* Bs = ops + RT_ROWS * RT_LD;
+  float* Bs = ops + SIM_ROWS * SIM_LD;
   float* St = ops;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave & 1, wc = wave >> 1, r = lane & 31, h = lane >> 5;
-  const long long i0 = (long long)blockIdx.x * RT_ROWS;
+  const long long i0 = (long long)blockIdx.x * SIM_ROWS;
   const bool grouped = row_group != nullptr;
 
-  if (tid < RT_ROWS) {
+  if (tid < SIM_ROWS) {
     const long long i = i0 + tid;
     cnt[tid] = 0;
     pass[2 * tid] = pass[2 * tid + 1] = 0u;
@@ -110,39 +88,26 @@ __global__ __launch_bounds__(RT_THREADS) void retrieval_topk_kernel(const float*
   const int rg = rgs[il];
 
   for (int ct = (int)blockIdx.y; ct < col_tiles; ct += (int)gridDim.y) {
-    const long long j0 = (long long)ct * RT_COLS;
+    const long long j0 = (long long)ct * SIM_COLS;
     f32x16 acc;
 #pragma unroll
     for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
-    if (tid < RT_COLS) {
+    if (tid < SIM_COLS) {
       const long long j = j0 + tid;
       const bool in = j < m;
       flg[tid] = in && (keep == nullptr || keep[j] != 0) ? 1 : 0;
       cgs[tid] = in && grouped ? col_group[j] : 0;
     }
-    for (int k0 = 0; k0 < d; k0 += RT_K) {
-      rt_stage(As, a, as, a_row, k0, d);
-      rt_stage(Bs, b, bs, [&](int cc) -> long long { return j0 + cc < m ? j0 + cc : -1; }, k0, d);
-      __syncthreads();
-      const float* pb = &Bs[(wc * 32 + r) * RT_LD + h];      // MFMA A operand: lane = score column j, k = 2 step + h
-      const float* pa = &As[il * RT_LD + h];                 // MFMA B operand: lane = score row i
-      if (d - k0 >= RT_K) {
-#pragma unroll
-        for (int s = 0; s < RT_K / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pb[2 * s], pa[2 * s], acc, 0, 0, 0);
-      } else {
-        const int steps = (d - k0 + 1) / 2;                   // the k past d of an odd tail is a zero pair
-        for (int s = 0; s < steps; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pb[2 * s], pa[2 * s], acc, 0, 0, 0);
-      }
-      __syncthreads();
-    }
-    // acc[g] = s(i, j) with j = j0 + wc * 32 + (g & 3) + 8 (g >> 2) + 4 h.  Prefilter against the row's k-th entry, spill the tile.
+    auto b_row = [&](int cc) -> long long { return j0 + cc < m ? j0 + cc : -1; };
+    SIM_SCORE_TILE(acc, As, Bs, a, as, a_row, b, bs, b_row);
+    // Prefilter against the row's k-th entry, spill the tile.
     {
       const bool full = cnt[il] == kk;
       const float thr = ls[il * RT_LP + kk - 1];
       unsigned bits = 0u;
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int cl = (g & 3) + 8 * (g >> 2) + 4 * h;        // the column within this wave's 32
+        const int cl = SIM_COL(0, g, h);                      // the column within this wave's 32
         const int jl = wc * 32 + cl;
         const float s = acc[g];
         if (flg[jl] != 0 && (!grouped || cgs[jl] != rg) && s == s && (!full || s > thr)) bits |= 1u << cl;
@@ -151,7 +116,7 @@ __global__ __launch_bounds__(RT_THREADS) void retrieval_topk_kernel(const float*
       if (bits != 0u) atomicOr(&pass[2 * il + wc], bits);     // the two half-waves share the word; an integer OR is order-free
     }
     __syncthreads();
-    if (tid < RT_ROWS && i0 + tid < n && (pass[2 * tid] | pass[2 * tid + 1]) != 0u) {
+    if (tid < SIM_ROWS && i0 + tid < n && (pass[2 * tid] | pass[2 * tid + 1]) != 0u) {
       float* S = &ls[tid * RT_LP];
       int* J = &lj[tid * RT_LP];
       int c = cnt[tid];
@@ -173,10 +138,10 @@ __global__ __launch_bounds__(RT_THREADS) void retrieval_topk_kernel(const float*
       }
       cnt[tid] = c;
     }
-    if (tid < RT_ROWS) pass[2 * tid] = pass[2 * tid + 1] = 0u;
+    if (tid < SIM_ROWS) pass[2 * tid] = pass[2 * tid + 1] = 0u;
     __syncthreads();                                          // the next tile rewrites flg / cgs and the operand images under St
   }
-  if (tid < RT_ROWS && i0 + tid < n) {
+  if (tid < SIM_ROWS && i0 + tid < n) {
     const long long i = i0 + tid;
     const int c = cnt[tid];
     if (pairs == nullptr) {
@@ -256,13 +221,7 @@ __global__ __launch_bounds__(RT_MERGE_THREADS) void retrieval_topk_merge_kernel(
 }
 
 static long long rt_split(long long n, long long m) {
-  const long long row_blocks = (n + RT_ROWS - 1) / RT_ROWS;
-  const long long col_tiles = (m + RT_COLS - 1) / RT_COLS;
-  long long split = (RT_TARGET_WGS + row_blocks - 1) / row_blocks;
-  if (split > col_tiles) split = col_tiles;
-  if (split > 65535) split = 65535;
-  if (split < 1) split = 1;
-  return split;
+  return sim_split((n + SIM_ROWS - 1) / SIM_ROWS, (m + SIM_COLS - 1) / SIM_COLS, 65535);   // the grid's y
 }
 
 }  // namespace octmae
@@ -282,19 +241,19 @@ extern "C" int octmae_retrieval_topk(const float* a, long long a_stride, const f
   if (k < 1 || k > RT_KMAX) return -2;
   if (m > 0x7fffffffLL) return -2;                        // out_idx holds int column indices
   if ((row_group == nullptr) != (col_group == nullptr)) return -2;
-  const long long row_blocks = (n + RT_ROWS - 1) / RT_ROWS;
+  const long long row_blocks = (n + SIM_ROWS - 1) / SIM_ROWS;
   if (row_blocks > 0x7fffffffLL) return -2;               // the row block is the grid's x
   const long long need = octmae_retrieval_topk_ws(n, m, k);
   if (need > 0 && (!ws || ws_bytes < need)) return -2;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int col_tiles = (int)((m + RT_COLS - 1) / RT_COLS);
+  const int col_tiles = (int)((m + SIM_COLS - 1) / SIM_COLS);
   const long long split = rt_split(n, m);
   RtPair* pairs = split > 1 ? reinterpret_cast<RtPair*>(ws) : nullptr;
-  hipLaunchKernelGGL(retrieval_topk_kernel, dim3((unsigned)row_blocks, (unsigned)split), dim3(RT_THREADS), 0, st, a, a_stride, b, b_stride,
+  hipLaunchKernelGGL(retrieval_topk_kernel, dim3((unsigned)row_blocks, (unsigned)split), dim3(SIM_THREADS), 0, st, a, a_stride, b, b_stride,
                      keep, row_group, col_group, k, out_idx, out_score, pairs, n, (int)m, d, col_tiles);
   OCTMAE_LAUNCH_CHECK();
   if (split > 1) {
-    // split > 1 only below RT_TARGET_WGS row blocks: n fits the grid's x
+    // split > 1 only below SIM_TARGET_WGS row blocks: n fits the grid's x
     hipLaunchKernelGGL(retrieval_topk_merge_kernel, dim3((unsigned)n), dim3(RT_MERGE_THREADS), 0, st, pairs, (int)split, k, out_idx,
                        out_score, n);
     OCTMAE_LAUNCH_CHECK();

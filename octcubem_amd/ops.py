@@ -1148,6 +1148,67 @@ def rank_counts_masked(scores: torch.Tensor, labels: torch.Tensor, valid: torch.
     return _rank_counts("rank_counts_masked", scores, labels, valid)
 
 
+def _pair_shapes(name: str, a, b, others, fits: Optional[str] = None, f32_others: bool = False):
+    """The operand contract of the ops on the f32 similarity tile (csrc/simtile.hpp): ``a`` float32 [n, d] and ``b`` float32 [m, d]
+    on one GPU, none empty, row counts in int32.  ``others``: (tensor or None, name) pairs that must be GPU tensors too, and float32
+    with ``f32_others``.  ``fits``: what of the op must fit int32 over the rows of ``b``; None: both row counts index tiles.
+    Returns (n, m, d)."""
+    operands = ((a, "a"), (b, "b")) + tuple(others)
+    for t, nm in operands:
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name}: {nm} must be a GPU tensor (the HIP path has no CPU fallback)")
+    for t, nm in operands if f32_others else operands[:2]:
+        if t is not None and t.dtype != F32:
+            raise TypeError(f"{name}: {nm} must be float32, got {t.dtype}")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.device != b.device:
+        raise ValueError(f"{name}: expected a [n, d] and b [m, d] on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, d = a.shape
+    m = b.shape[0]
+    if n < 1 or m < 1 or d < 1:
+        raise ValueError(f"{name}: empty input {tuple(a.shape)} / {tuple(b.shape)}")
+    if fits is not None and m > 2 ** 31 - 1:
+        raise ValueError(f"{name}: b has {m} rows, {fits} must fit int32")
+    if fits is None and max(n, m) > 2 ** 31 - 1:
+        raise ValueError(f"{name}: {max(n, m)} rows, the kernel indexes tiles with int32")
+    return n, m, d
+
+
+def _pair_strides(name: str, a: torch.Tensor, b: torch.Tensor):
+    """The row strides the kernels take for the checked ``a`` and ``b``: unit column stride, any row stride >= d (slices of wider
+    buffers); a single row has no stride to speak of and passes d.  Apart from ``_pair_shapes`` because ``retrieval_topk`` refuses a
+    bad ``k`` between the two."""
+    d = a.shape[1]
+    for t, nm in ((a, "a"), (b, "b")):
+        if (d > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < d):
+            raise ValueError(f"{name}: {nm} needs unit column stride and a row stride >= {d}, got strides {tuple(t.stride())}")
+    return (a.stride(0) if a.shape[0] > 1 else d), (b.stride(0) if b.shape[0] > 1 else d)
+
+
+def _pair_tables(name: str, dev, n: int, m: int, target, keep, row_group, col_group):
+    """The per-row and per-column tables of the retrieval ops: ``target`` and ``row_group`` int32 [n], ``col_group`` int32 [m] (the
+    groups together or not at all), ``keep`` bool / uint8 [m], each optional and on ``dev``.  Returns them detached and contiguous,
+    ``keep`` as uint8."""
+    if (row_group is None) != (col_group is None):
+        raise ValueError(f"{name}: row_group and col_group are given together or not at all")
+    for t, nm, rows in ((target, "target", n), (row_group, "row_group", n), (col_group, "col_group", m)):
+        if t is None:
+            continue
+        if t.dtype != torch.int32:
+            raise TypeError(f"{name}: {nm} must be int32, got {t.dtype}")
+        if tuple(t.shape) != (rows,) or t.device != dev:
+            raise ValueError(f"{name}: {nm} must be [{rows}] on {dev}, got {tuple(t.shape)} on {t.device}")
+    if keep is not None:
+        if keep.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{name}: keep must be bool or uint8, got {keep.dtype}")
+        if tuple(keep.shape) != (m,) or keep.device != dev:
+            raise ValueError(f"{name}: keep must be [{m}] on {dev}, got {tuple(keep.shape)} on {keep.device}")
+        keep = keep.detach().contiguous()
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+    target, row_group, col_group = (None if t is None else t.detach().contiguous() for t in (target, row_group, col_group))
+    return target, keep, row_group, col_group
+
+
 def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
                     row_group: Optional[torch.Tensor] = None, col_group: Optional[torch.Tensor] = None) -> torch.Tensor:
     """int32 [n, 4] per row i of ``a`` float32 [n, d] against the rows of ``b`` float32 [m, d], with s(i, j) the f32 fmaf chain over k
@@ -1162,44 +1223,13 @@ def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Ten
     features raise ValueError before the launch (that check reads one flag back from the device; a target that is not kept is refused
     the same way).  No autograd; no 16-bit operand, so autocast changes nothing."""
     name = "retrieval_ranks"
-    for t, nm in ((a, "a"), (b, "b"), (target, "target"), (keep, "keep"), (row_group, "row_group"), (col_group, "col_group")):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"{name}: {nm} must be a GPU tensor (the HIP path has no CPU fallback)")
-    for t, nm in ((a, "a"), (b, "b")):
-        if t.dtype != F32:
-            raise TypeError(f"{name}: {nm} must be float32, got {t.dtype}")
-    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.device != b.device:
-        raise ValueError(f"{name}: expected a [n, d] and b [m, d] on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
-    n, d = a.shape
-    m = b.shape[0]
-    if n < 1 or m < 1 or d < 1:
-        raise ValueError(f"{name}: empty input {tuple(a.shape)} / {tuple(b.shape)}")
-    if m > 2 ** 31 - 1:
-        raise ValueError(f"{name}: b has {m} rows, a count must fit int32")
+    n, m, d = _pair_shapes(name, a, b, ((target, "target"), (keep, "keep"), (row_group, "row_group"), (col_group, "col_group")),
+                           fits="a count")
     a, b = a.detach(), b.detach()
-    for t, nm, rows in ((a, "a", n), (b, "b", m)):
-        if (d > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < d):
-            raise ValueError(f"{name}: {nm} needs unit column stride and a row stride >= {d}, got strides {tuple(t.stride())}")
+    sa, sb = _pair_strides(name, a, b)
     if target is None and n != m:
         raise ValueError(f"{name}: without target the partner of row i is column i, which needs n == m; got n={n}, m={m}")
-    if (row_group is None) != (col_group is None):
-        raise ValueError(f"{name}: row_group and col_group are given together or not at all")
-    for t, nm, rows in ((target, "target", n), (row_group, "row_group", n), (col_group, "col_group", m)):
-        if t is None:
-            continue
-        if t.dtype != torch.int32:
-            raise TypeError(f"{name}: {nm} must be int32, got {t.dtype}")
-        if tuple(t.shape) != (rows,) or t.device != a.device:
-            raise ValueError(f"{name}: {nm} must be [{rows}] on {a.device}, got {tuple(t.shape)} on {t.device}")
-    if keep is not None:
-        if keep.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"{name}: keep must be bool or uint8, got {keep.dtype}")
-        if tuple(keep.shape) != (m,) or keep.device != a.device:
-            raise ValueError(f"{name}: keep must be [{m}] on {a.device}, got {tuple(keep.shape)} on {keep.device}")
-        keep = keep.detach().contiguous()
-        if keep.dtype == torch.bool:
-            keep = keep.view(torch.uint8)
-    target, row_group, col_group = (None if t is None else t.detach().contiguous() for t in (target, row_group, col_group))
+    target, keep, row_group, col_group = _pair_tables(name, a.device, n, m, target, keep, row_group, col_group)
     # one flag for every host-side refusal that needs the data: a single read-back
     bad = torch.stack([(~torch.isfinite(a)).any(), (~torch.isfinite(b)).any(),
                        ((target < 0) | (target >= m)).any() if target is not None else a.new_zeros((), dtype=torch.bool)]).tolist()
@@ -1211,8 +1241,6 @@ def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Ten
         kept = keep[target.long()] if target is not None else keep
         if not bool((kept != 0).all()):
             raise ValueError(f"{name}: every target must be a kept column")
-    sa = a.stride(0) if n > 1 else d
-    sb = b.stride(0) if m > 1 else d
     out = torch.empty((n, 4), dtype=torch.int32, device=a.device)
     # algorithmic HBM bytes: a and b read once (the re-reads per tile hit the caches), the counts written once
     _launch(name, 2.0 * n * m * d, float(4 * (n + m) * d + 16 * n),
@@ -1236,50 +1264,16 @@ def retrieval_topk(a: torch.Tensor, b: torch.Tensor, k: int, keep: Optional[torc
     be slices of wider buffers (unit column stride, any row stride >= d).  Non-finite features raise ValueError before the launch
     (that check reads one flag back from the device).  No autograd; no 16-bit operand, so autocast changes nothing."""
     name = "retrieval_topk"
-    for t, nm in ((a, "a"), (b, "b"), (keep, "keep"), (row_group, "row_group"), (col_group, "col_group")):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"{name}: {nm} must be a GPU tensor (the HIP path has no CPU fallback)")
-    for t, nm in ((a, "a"), (b, "b")):
-        if t.dtype != F32:
-            raise TypeError(f"{name}: {nm} must be float32, got {t.dtype}")
-    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.device != b.device:
-        raise ValueError(f"{name}: expected a [n, d] and b [m, d] on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
-    n, d = a.shape
-    m = b.shape[0]
-    if n < 1 or m < 1 or d < 1:
-        raise ValueError(f"{name}: empty input {tuple(a.shape)} / {tuple(b.shape)}")
-    if m > 2 ** 31 - 1:
-        raise ValueError(f"{name}: b has {m} rows, a column index must fit int32")
+    n, m, d = _pair_shapes(name, a, b, ((keep, "keep"), (row_group, "row_group"), (col_group, "col_group")), fits="a column index")
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= RETRIEVAL_TOPK_MAX:
         raise ValueError(f"{name}: k must be an int in [1, {RETRIEVAL_TOPK_MAX}], got {k!r}")
     a, b = a.detach(), b.detach()
-    for t, nm, rows in ((a, "a", n), (b, "b", m)):
-        if (d > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < d):
-            raise ValueError(f"{name}: {nm} needs unit column stride and a row stride >= {d}, got strides {tuple(t.stride())}")
-    if (row_group is None) != (col_group is None):
-        raise ValueError(f"{name}: row_group and col_group are given together or not at all")
-    for t, nm, rows in ((row_group, "row_group", n), (col_group, "col_group", m)):
-        if t is None:
-            continue
-        if t.dtype != torch.int32:
-            raise TypeError(f"{name}: {nm} must be int32, got {t.dtype}")
-        if tuple(t.shape) != (rows,) or t.device != a.device:
-            raise ValueError(f"{name}: {nm} must be [{rows}] on {a.device}, got {tuple(t.shape)} on {t.device}")
-    if keep is not None:
-        if keep.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"{name}: keep must be bool or uint8, got {keep.dtype}")
-        if tuple(keep.shape) != (m,) or keep.device != a.device:
-            raise ValueError(f"{name}: keep must be [{m}] on {a.device}, got {tuple(keep.shape)} on {keep.device}")
-        keep = keep.detach().contiguous()
-        if keep.dtype == torch.bool:
-            keep = keep.view(torch.uint8)
-    row_group, col_group = (None if t is None else t.detach().contiguous() for t in (row_group, col_group))
+    sa, sb = _pair_strides(name, a, b)
+    _, keep, row_group, col_group = _pair_tables(name, a.device, n, m, None, keep, row_group, col_group)
     # max |x| is finite iff every x is (a NaN propagates through the maximum): two reductions without an [n, d] temporary, one read-back
     bad = (~torch.isfinite(torch.stack([torch.linalg.vector_norm(t, ord=float("inf")) for t in (a, b)]))).tolist()
     if bad[0] or bad[1]:
         raise ValueError(f"{name}: {'a' if bad[0] else 'b'} contains non-finite values")
-    sa = a.stride(0) if n > 1 else d
-    sb = b.stride(0) if m > 1 else d
     nws = int(load().octmae_retrieval_topk_ws(n, m, k))
     if nws < 0:
         raise ValueError(f"{name}: n = {n}, m = {m}, k = {k} is beyond the kernel's workspace query")
@@ -1360,23 +1354,8 @@ def clip_pair_loss(a: torch.Tensor, b: torch.Tensor, logit_scale, wr: torch.Tens
     caller's skip-step logic reads it.  ``offset`` outside 0 <= offset <= m - n raises ValueError before any launch.  No 16-bit operand,
     and an enclosing autocast changes nothing."""
     name = "clip_pair_loss"
-    for t, nm in ((a, "a"), (b, "b"), (logit_scale, "logit_scale"), (wr, "wr"), (wc, "wc")):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"{name}: {nm} must be a GPU tensor (the HIP path has no CPU fallback)")
-    for t, nm in ((a, "a"), (b, "b"), (logit_scale, "logit_scale"), (wr, "wr"), (wc, "wc")):
-        if t is not None and t.dtype != F32:
-            raise TypeError(f"{name}: {nm} must be float32, got {t.dtype}")
-    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.device != b.device:
-        raise ValueError(f"{name}: expected a [n, d] and b [m, d] on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
-    n, d = a.shape
-    m = b.shape[0]
-    if n < 1 or m < 1 or d < 1:
-        raise ValueError(f"{name}: empty input {tuple(a.shape)} / {tuple(b.shape)}")
-    if max(n, m) > 2 ** 31 - 1:
-        raise ValueError(f"{name}: {max(n, m)} rows, the kernel indexes tiles with int32")
-    for t, nm, rows in ((a, "a", n), (b, "b", m)):
-        if (d > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < d):
-            raise ValueError(f"{name}: {nm} needs unit column stride and a row stride >= {d}, got strides {tuple(t.stride())}")
+    n, m, d = _pair_shapes(name, a, b, ((logit_scale, "logit_scale"), (wr, "wr"), (wc, "wc")), f32_others=True)
+    _pair_strides(name, a, b)
     if logit_scale.numel() != 1 or logit_scale.device != a.device:
         raise ValueError(f"{name}: logit_scale must be one element on {a.device}, got {tuple(logit_scale.shape)} on {logit_scale.device}")
     for t, nm in ((wr, "wr"), (wc, "wc")):

@@ -46,7 +46,7 @@ def gamma(k):
 
 
 # ------------------------------------------------------------------------------------------------ the forward's launch plan, restated
-TARGET_WGS = 1024       # CL_TARGET_WGS
+TARGET_WGS = 1024       # SIM_TARGET_WGS (csrc/simtile.hpp)
 MAX_SPLIT = 64          # CL_MAX_SPLIT
 # (n, m, d, offset) at which a workgroup of clip_lse_kernel walks more than one column tile, with the plan the constants above give:
 # tests/test_cpu_cliploss.py compares the constants with csrc/cliploss.hip and the plans with this table, so whoever changes a constant
@@ -58,7 +58,7 @@ TRIP_PLANS = (dict(row_blocks_a=1, tiles_a=131, split_a=64, row_blocks_b=131, ti
 
 
 def split(row_blocks, col_tiles, target_wgs=TARGET_WGS):
-    """cl_split: the workgroups that share one row block's column tiles"""
+    """sim_split under CL_MAX_SPLIT: the workgroups that share one row block's column tiles"""
     return max(1, min(-(-target_wgs // row_blocks), col_tiles, MAX_SPLIT))
 
 

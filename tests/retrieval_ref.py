@@ -28,8 +28,8 @@ def counts(scores, target=None, keep=None, row_group=None, col_group=None) -> np
 
 
 # ---- the launch plan of octmae_retrieval_ranks, restated
-TILE = 64               # RR_ROWS == RR_COLS
-TARGET_WGS = 1024       # RR_TARGET_WGS
+TILE = 64               # SIM_ROWS == SIM_COLS (csrc/simtile.hpp)
+TARGET_WGS = 1024       # SIM_TARGET_WGS
 MAX_GRID_Y = 65535
 # (n, m, d) at which a workgroup of retrieval_ranks_kernel walks more than one column tile, with (row blocks, column tiles, split):
 # tests/test_cpu_retrieval.py compares the constants with csrc/retrieval.hip and the plans with this table; tests/test_gpu_retrieval.py

@@ -13,8 +13,8 @@ import torch
 from tests.retrieval_ref import TRIP_SHAPES, chain_scores, f64_scores, _np  # noqa: F401
 
 # ---- the launch plan of octmae_retrieval_topk, restated (the walk of the ranks kernel plus the lists)
-TILE = 64               # RT_ROWS == RT_COLS
-TARGET_WGS = 1024       # RT_TARGET_WGS
+TILE = 64               # SIM_ROWS == SIM_COLS (csrc/simtile.hpp)
+TARGET_WGS = 1024       # SIM_TARGET_WGS
 MAX_GRID_Y = 65535
 K_MAX = 32              # RT_KMAX
 PAIR_BYTES = 8          # sizeof(RtPair): f32 score, int32 index

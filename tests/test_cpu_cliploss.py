@@ -79,13 +79,18 @@ def hip_constant(text, name):
 
 
 def test_restated_plan_follows_the_kernel_constants_and_the_trip_shapes_lie_past_the_split():
-    """Whoever changes a constant of csrc/cliploss.hip is told here to move R.TRIP_SHAPES (tests/test_gpu_cliploss.py runs them)."""
+    """Whoever changes a constant of the tile (csrc/simtile.hpp) or of csrc/cliploss.hip is told here to move R.TRIP_SHAPES
+    (tests/test_gpu_cliploss.py runs them)."""
     src = open(os.path.join(ROOT, "octcubem_amd", "csrc", "cliploss.hip")).read()
-    assert hip_constant(src, "CL_TARGET_WGS") == R.TARGET_WGS and hip_constant(src, "CL_MAX_SPLIT") == R.MAX_SPLIT
-    assert hip_constant(src, "CL_ROWS") == hip_constant(src, "CL_COLS") == R.TILE and hip_constant(src, "CL_K") == R.KSTEP
-    # cl_split as written: ceil(target / row_blocks), then the two caps
-    assert re.search(r"long long s = \(CL_TARGET_WGS \+ row_blocks - 1\) / row_blocks;\s*if \(s > col_tiles\) s = col_tiles;\s*"
-                     r"if \(s > CL_MAX_SPLIT\) s = CL_MAX_SPLIT;", src)
+    tile = open(os.path.join(ROOT, "octcubem_amd", "csrc", "simtile.hpp")).read()
+    assert '#include "simtile.hpp"' in src and not re.search(r"^constexpr int CL_(ROWS|COLS|K|TARGET_WGS) ", src, re.M)
+    assert hip_constant(tile, "SIM_TARGET_WGS") == R.TARGET_WGS and hip_constant(src, "CL_MAX_SPLIT") == R.MAX_SPLIT
+    assert hip_constant(tile, "SIM_ROWS") == hip_constant(tile, "SIM_COLS") == R.TILE and hip_constant(tile, "SIM_K") == R.KSTEP
+    # sim_split as written: ceil(target / row_blocks), then the two caps; both sides of the loss pass CL_MAX_SPLIT
+    assert re.search(r"long long split = \(SIM_TARGET_WGS \+ row_blocks - 1\) / row_blocks;\s*if \(split > col_tiles\) split = col_tiles;\s*"
+                     r"if \(split > cap\) split = cap;", tile)
+    for side in "ab":
+        assert re.search(rf"p->split_{side} = \(int\)sim_split\(p->row_blocks_{side}, p->tiles_{side}, CL_MAX_SPLIT\);", src), side
     assert re.search(r"return 2 \* \(\(long long\)p\.split_a \* n \+ \(long long\)p\.split_b \* m\);", src)
     assert R.split(1, 1) == 1 and R.split(1, 200) == 64 and R.split(40, 200) == 26 and R.split(4000, 9) == 1 and R.split(512, 9) == 2
     for (n, m, d, off), want in zip(R.TRIP_SHAPES, R.TRIP_PLANS):

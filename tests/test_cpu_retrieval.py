@@ -207,12 +207,17 @@ def test_abi_declares_retrieval_ranks():
 
 
 def test_restated_plan_follows_the_kernel_constants_and_the_trip_shapes_lie_past_the_split():
-    """Whoever changes a constant of csrc/retrieval.hip is told here to move R.TRIP_SHAPES (tests/test_gpu_retrieval.py runs them)."""
+    """Whoever changes a constant of the tile (csrc/simtile.hpp) or the cap that csrc/retrieval.hip hands its split rule is told here
+    to move R.TRIP_SHAPES (tests/test_gpu_retrieval.py runs them)."""
     src = open(os.path.join(ROOT, "octcubem_amd", "csrc", "retrieval.hip")).read()
-    const = lambda name: int(re.search(rf"^constexpr int {name} = (\d+);", src, re.M).group(1))
-    assert const("RR_ROWS") == const("RR_COLS") == R.TILE and const("RR_TARGET_WGS") == R.TARGET_WGS
-    assert re.search(r"long long split = \(RR_TARGET_WGS \+ row_blocks - 1\) / row_blocks;\s*if \(split > col_tiles\) split = col_tiles;\s*"
-                     rf"if \(split > {R.MAX_GRID_Y}\) split = {R.MAX_GRID_Y};", src)
+    tile = open(os.path.join(ROOT, "octcubem_amd", "csrc", "simtile.hpp")).read()
+    const = lambda name: int(re.search(rf"^constexpr int {name} = (\d+);", tile, re.M).group(1))
+    assert '#include "simtile.hpp"' in src and not re.search(r"^constexpr int RR_", src, re.M)     # the file has no tile of its own
+    assert const("SIM_ROWS") == const("SIM_COLS") == R.TILE and const("SIM_TARGET_WGS") == R.TARGET_WGS
+    # sim_split as written: ceil(target / row_blocks), then the two caps; this file's cap is the grid's y
+    assert re.search(r"long long split = \(SIM_TARGET_WGS \+ row_blocks - 1\) / row_blocks;\s*if \(split > col_tiles\) split = col_tiles;\s*"
+                     r"if \(split > cap\) split = cap;", tile)
+    assert re.search(rf"const long long split = sim_split\(row_blocks, col_tiles, {R.MAX_GRID_Y}\);", src)
     assert R.plan(1, 1) == (1, 1, 1) and R.plan(131, 131) == (3, 3, 3) and R.plan(64, 70000) == (1, 1094, 1024)
     for (n, m, d), want in zip(R.TRIP_SHAPES, R.TRIP_PLANS):
         assert R.plan(n, m) == want, (n, m, R.plan(n, m))

@@ -60,12 +60,18 @@ def test_all_rows_padded_when_nothing_is_a_candidate():
 
 
 def test_restated_plan_follows_the_kernel_constants_and_the_workspace_follows_the_plan():
-    """Whoever changes a constant of csrc/retrieval_topk.hip is told here to move the shapes of tests/test_gpu_retrieval_topk.py."""
+    """Whoever changes a constant of the tile (csrc/simtile.hpp) or of csrc/retrieval_topk.hip is told here to move the shapes of
+    tests/test_gpu_retrieval_topk.py."""
     src = open(os.path.join(ROOT, "octcubem_amd", "csrc", "retrieval_topk.hip")).read()
-    const = lambda name: int(re.search(rf"^constexpr int {name} = (\d+);", src, re.M).group(1))
-    assert const("RT_ROWS") == const("RT_COLS") == T.TILE and const("RT_TARGET_WGS") == T.TARGET_WGS and const("RT_KMAX") == T.K_MAX
-    assert re.search(r"long long split = \(RT_TARGET_WGS \+ row_blocks - 1\) / row_blocks;\s*if \(split > col_tiles\) split = col_tiles;\s*"
-                     rf"if \(split > {T.MAX_GRID_Y}\) split = {T.MAX_GRID_Y};", src)
+    tile = open(os.path.join(ROOT, "octcubem_amd", "csrc", "simtile.hpp")).read()
+    const = lambda name, text=tile: int(re.search(rf"^constexpr int {name} = (\d+);", text, re.M).group(1))
+    assert '#include "simtile.hpp"' in src and not re.search(r"^constexpr int RT_(ROWS|COLS|K|TARGET_WGS) ", src, re.M)
+    assert const("SIM_ROWS") == const("SIM_COLS") == T.TILE and const("SIM_TARGET_WGS") == T.TARGET_WGS
+    assert const("RT_KMAX", src) == T.K_MAX
+    # sim_split as written: ceil(target / row_blocks), then the two caps; this file's cap is the grid's y
+    assert re.search(r"long long split = \(SIM_TARGET_WGS \+ row_blocks - 1\) / row_blocks;\s*if \(split > col_tiles\) split = col_tiles;\s*"
+                     r"if \(split > cap\) split = cap;", tile)
+    assert re.search(rf"return sim_split\(\(n \+ SIM_ROWS - 1\) / SIM_ROWS, \(m \+ SIM_COLS - 1\) / SIM_COLS, {T.MAX_GRID_Y}\);", src)
     assert re.search(r"static_assert\(sizeof\(RtPair\) == 8,", src) and T.PAIR_BYTES == 8
     assert re.search(r"return split > 1 \? split \* n \* k \* \(long long\)sizeof\(RtPair\) : 0;", src)
     # the same walk as the ranks kernel: its trip shapes are past this split too
