@@ -61,8 +61,10 @@ extern "C" {
  * 30: octmae_mae_compose_nc, octmae_white_border (+ octmae_white_border_ws_floats): the RGB / raw-level panels and the border blanking of
  *     the 2-D half of the validation pass (csrc/recon2d.hip).
  * 31: octmae_cam_eigen (+ octmae_cam_eigen_ws_floats), octmae_cam_accumulate: the eigen-smoothed Grad-CAM map by matrix-free power
- *     iterations and the normalise-flip-fold of test-time-augmentation smoothing (csrc/saliency.hip). */
-#define OCTMAE_ABI_VERSION 31
+ *     iterations and the normalise-flip-fold of test-time-augmentation smoothing (csrc/saliency.hip).
+ * 32: octmae_retrieval_pair_ranks (+ octmae_retrieval_pair_ws): both directions of up to three square retrieval problems from one walk
+ *     over the tiles of 19 (the six directions of the three-modality COEM validation, csrc/retrieval_pair.hip). */
+#define OCTMAE_ABI_VERSION 32
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -613,6 +615,30 @@ long long int octmae_retrieval_topk_ws(long long n, long long m, int k);
 int octmae_retrieval_topk(const float* a, long long a_stride, const float* b, long long b_stride, const uint8_t* keep,
                           const int* row_group, const int* col_group, int k, int* out_idx, float* out_score, void* ws,
                           long long ws_bytes, long long n, long long m, int d, void* stream);
+
+/* ---- both directions of up to three retrieval problems (csrc/retrieval_pair.hip) -----------------------
+ * retinal-COEM/src/training/train_retclip_3modalities.py:561-604 (get_metrics_3modalities) ranks six directions: three [n][n] products,
+ * each read by row and by column.  This entry point walks the tiles of each product once and counts both directions.
+ *   pairs   P = 1 .. 3; pair p is a_p, b_p, both f32 [n][d] with rows a_p_stride / b_p_stride ELEMENTS apart (>= d); the pointers and
+ *           strides of the pairs at and past P are not read (NULL / 0).  Two pairs may share an operand.
+ *   s_p(i, j) the f32 chain of octmae_retrieval_ranks on a_p, b_p (the same bits);  t_p(i) = s_p(i, i), the tile's own bits
+ *   out     int32 [P][2][n][2], contiguous:
+ *             out[p][0][i] = { #{ j != i : s_p(i, j) > t_p(i) },  #{ j < i : s_p(i, j) == t_p(i) } }
+ *             out[p][1][j] = { #{ i != j : s_p(i, j) > t_p(j) },  #{ i < j : s_p(i, j) == t_p(j) } }
+ *           out[p][0] is columns 0 and 1 of octmae_retrieval_ranks(a_p, b_p) with the diagonal as target and no keep, out[p][1] those of
+ *           octmae_retrieval_ranks(b_p, a_p), bit for bit: a product of two floats commutes, so the chain is the same either way.
+ *   ws      workspace of at least octmae_retrieval_pair_ws(n, pairs) BYTES, 4-byte aligned: the P n diagonal scores, written by a
+ *           pre-pass; the query returns -1 for n <= 0, n above 2^31 - 1 or pairs outside 1 .. 3
+ * IEEE comparisons; the caller keeps non-finite features out (octcubem_amd.ops.retrieval_pair_ranks raises).  Deterministic: integer
+ * counts, combined across workgroups with integer atomics into the zeroed `out`; no float crosses a workgroup but the read-only
+ * diagonal.  The library allocates nothing and does not synchronise.  Same code in the two builds of the library.
+ * -1, before any launch and with nothing written: pairs outside 1 .. 3, n or d <= 0, n above 2^31 - 1, a NULL out / ws, a NULL operand
+ * or a stride below d among the first P pairs, ws not 4-byte aligned or ws_bytes below the query.  (`long long int`: a byte count.) */
+long long int octmae_retrieval_pair_ws(long long n, int pairs);
+int octmae_retrieval_pair_ranks(const float* a0, long long a0_stride, const float* b0, long long b0_stride, const float* a1,
+                                long long a1_stride, const float* b1, long long b1_stride, const float* a2, long long a2_stride,
+                                const float* b2, long long b2_stride, int pairs, int* out, void* ws, long long ws_bytes, long long n,
+                                int d, void* stream);
 
 /* ---- contrastive loss of the COEM training step (csrc/cliploss.hip) ---------------------------------
  * retinal-COEM/src/open_clip/loss.py:148-230 (ClipLoss) and :230-385 (ThreeModalityClipLoss) form logit_scale * a @ b.T, its transpose,

@@ -43,6 +43,8 @@ SIGNATURES = {
     "octmae_retrieval_ranks": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _vp],
     "octmae_retrieval_topk_ws": [_ll, _ll, _i],
     "octmae_retrieval_topk": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],
+    "octmae_retrieval_pair_ws": [_ll, _i],
+    "octmae_retrieval_pair_ranks": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _vp, _vp, _ll, _ll, _i, _vp],
     "octmae_clip_loss_ws_floats": [_ll, _ll],
     "octmae_clip_loss_fwd": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],
     "octmae_clip_loss_bwd": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _ll, _ll, _i, _vp],
@@ -123,7 +125,7 @@ SIGNATURES = {
 }
 
 # ... except a query whose value is a byte count (long long in the header)
-RESTYPES = {"octmae_retrieval_topk_ws": _ll}
+RESTYPES = {"octmae_retrieval_topk_ws": _ll, "octmae_retrieval_pair_ws": _ll}
 
 _lib = None
 _on_load = []       # callbacks run once, right after the library has been loaded and bound (ops: operand-type check)

@@ -947,6 +947,30 @@ def _positions(ranks, pairs):
     return np.split(flat, np.cumsum([c.shape[0] for c in cols])[:-1])
 
 
+def _device_pair_ranks(pairs):
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for p in pairs for t in p):
+        raise RuntimeError("retrieval metrics: the ranks come from the HIP kernel (ops.retrieval_pair_ranks), which has no CPU fallback: "
+                           "pass features on the device, or a pair_ranks function")
+    from . import ops
+    return ops.retrieval_pair_ranks(pairs)
+
+
+def _one_ranks_source(name, ranks, pair_ranks):
+    if ranks is not None and pair_ranks is not None:
+        raise ValueError(f"{name}: pass ranks= or pair_ranks=, not both")
+
+
+def _pair_positions(pair_ranks, pairs):
+    """[(a, b), ...] -> two int64 numpy arrays per pair, in order: the place of sample i's partner among the rows of b (the rows of the
+    product), then among the rows of a (its columns).  One call, one device-to-host copy."""
+    out = torch.as_tensor(pair_ranks(list(pairs)))
+    n = pairs[0][0].shape[0]
+    if tuple(out.shape) != (len(pairs), 2, n, 2):
+        raise ValueError(f"pair_ranks returned {tuple(out.shape)}, expected {(len(pairs), 2, n, 2)}")
+    pos = out.sum(dim=-1).cpu().numpy().astype(np.int64)
+    return [pos[p, k] for p in range(len(pairs)) for k in (0, 1)]
+
+
 def _rank_summary(metrics, name, preds):
     metrics[f"{name}_mean_rank"] = preds.mean() + 1
     metrics[f"{name}_median_rank"] = np.floor(np.median(preds)) + 1
@@ -954,27 +978,34 @@ def _rank_summary(metrics, name, preds):
         metrics[f"{name}_R@{k}"] = np.mean(preds < k)
 
 
-def get_metrics(image_features, text_features, logit_scale, ranks=None):
+def get_metrics(image_features, text_features, logit_scale, ranks=None, pair_ranks=None):
     """train_retclip.get_metrics: ``{image_to_text, text_to_image}_{mean_rank, median_rank, R@1, R@5, R@10}``.  ``logit_scale`` is
-    checked (finite, > 0) and does not enter the ranking: a positive factor changes no order.  Ties resolve by column index."""
+    checked (finite, > 0) and does not enter the ranking: a positive factor changes no order.  Ties resolve by column index.
+    ``pair_ranks=`` (a function of ``ops.retrieval_pair_ranks``' signature; not together with ``ranks=``): both directions from one
+    walk over the product."""
     _check_scale("logit_scale", logit_scale)
+    _one_ranks_source("get_metrics", ranks, pair_ranks)
     ranks = ranks or _device_ranks
     img, txt = _feat(image_features), _feat(text_features)
     if img.dim() != 2 or img.shape != txt.shape:
         raise ValueError(f"get_metrics: expected two [N, D] feature matrices, got {tuple(img.shape)} and {tuple(txt.shape)}")
     metrics = {}
-    for name, preds in zip(("image_to_text", "text_to_image"), _positions(ranks, [(img, txt), (txt, img)])):
+    preds_all = _positions(ranks, [(img, txt), (txt, img)]) if pair_ranks is None else _pair_positions(pair_ranks, [(img, txt)])
+    for name, preds in zip(("image_to_text", "text_to_image"), preds_all):
         _rank_summary(metrics, name, preds)
     return metrics
 
 
 def get_metrics_3modalities(image_features, text1_features, text2_features, logit_scale, logit_scale1, logit_scale2, t_weight1,
-                            t_weight2, ranks=None):
+                            t_weight2, ranks=None, pair_ranks=None):
     """train_retclip_3modalities.get_metrics_3modalities: the six directions among (image, text1, text2); every sample is ranked against
     ALL candidates and the summary is taken over the samples whose modality is present (``t_weight > 0``; ``t_weight1 * t_weight2``
-    for the text1 / text2 pair).  A direction with no sample left raises ValueError."""
+    for the text1 / text2 pair).  A direction with no sample left raises ValueError.  ``pair_ranks=`` (a function of
+    ``ops.retrieval_pair_ranks``' signature; not together with ``ranks=``): the six directions from one launch over the three products
+    instead of six launches."""
     for nm, s in (("logit_scale", logit_scale), ("logit_scale1", logit_scale1), ("logit_scale2", logit_scale2)):
         _check_scale(nm, s)
+    _one_ranks_source("get_metrics_3modalities", ranks, pair_ranks)
     ranks = ranks or _device_ranks
     img, t1, t2 = _feat(image_features), _feat(text1_features), _feat(text2_features)
     if img.dim() != 2 or img.shape != t1.shape or img.shape != t2.shape:
@@ -990,7 +1021,11 @@ def get_metrics_3modalities(image_features, text1_features, text2_features, logi
         if not (w > 0).any():
             raise ValueError(f"get_metrics_3modalities: no sample with t_weight > 0 is left for {name}")
     metrics = {}
-    for (name, _, _, w), preds in zip(directions, _positions(ranks, [(a, b) for _, a, b, _ in directions])):
+    if pair_ranks is None:
+        preds_all = _positions(ranks, [(a, b) for _, a, b, _ in directions])
+    else:                               # the rows and columns of three products, in the order of `directions`
+        preds_all = _pair_positions(pair_ranks, [(img, t1), (img, t2), (t1, t2)])
+    for (name, _, _, w), preds in zip(directions, preds_all):
         _rank_summary(metrics, name, preds[w > 0])
     return metrics
 
@@ -1242,3 +1277,180 @@ def evaluate(model, data, epoch, args, tb_writer=None):
                     arrays[name], arrays[name + "_scores"] = idx.cpu().numpy(), score.cpu().numpy()
             np.savez(os.path.join(args.checkpoint_path, f"retrieval_results_{epoch}.npz"), **arrays)
     return metrics
+
+
+# ---- validation of the other recipes (train_retclip.py:290-300 for 'oct_ir' / 'oct_faf_only', train_retclip_3modalities.py:279-538 for
+# 'oct_faf_ir').  ``evaluate`` above stays the 'default' loop, untouched; the loops below take dict batches as ``_run_epoch`` does and
+# may draw every direction's ranks from one launch of ops.retrieval_pair_ranks (csrc/retrieval_pair.hip).  Whether they do without being
+# asked is PAIR_RANKS_DEFAULT, True only if the one launch is not slower than the launches it replaces at N = 3000: measured on an
+# MI355X at D = 512 (tools/bench_pair_ranks.py, profiles/pair_ranks_bench.txt; DESIGN.md section 4 holds the table, as for
+# FUSED_DEFAULT), one P = 3 launch takes 1.63 ms against 4.65 ms for the six launches.
+PAIR_RANKS_DEFAULT = True
+
+
+def _pair_ranks_arg(pair_ranks):
+    """None: PAIR_RANKS_DEFAULT; True / False: the pair kernel / the per-direction kernel; a function: that function."""
+    if pair_ranks is None:
+        pair_ranks = PAIR_RANKS_DEFAULT
+    if pair_ranks is True:
+        return _device_pair_ranks
+    return None if pair_ranks is False else pair_ranks
+
+
+def _masked_pair_term(loss_rows, w):
+    """sum(loss * w) / sum(w), 0 where sum(w) == 0 -- chosen on the device, without a division by that zero and without a read-back"""
+    den = w.sum()
+    return torch.where(den == 0, torch.zeros_like(den), (loss_rows * w).sum() / torch.where(den == 0, torch.ones_like(den), den))
+
+
+def three_way_val_loss(image_features, text1_features, text2_features, logit_scale, logit_scale1, logit_scale2, w1, w2, correct_label=False):
+    """The per-batch validation loss of train_retclip_3modalities.evaluate (:407-467): six ``cross_entropy(reduction='none')`` terms on
+    the three in-batch logit matrices and their transposes; image / text1 weighted by ``w1`` over ``w1.sum()``, image / text2 by ``w2``
+    over ``w2.sum()`` and text1 / text2 by ``w1`` ALONE over ``w1.sum()`` (:451-463 -- not the ``w1 * w2`` of ThreeModalityClipLoss),
+    a zero weight sum giving 0 for its two terms; the sum over 6.  ``correct_label``: the targets are the 0 / 1 same-feature matrix of
+    text1, which ``cross_entropy`` takes as class probabilities (the reference builds a BCE criterion there and never uses it)."""
+    l0 = logit_scale * image_features @ text1_features.t()
+    l1 = logit_scale1 * image_features @ text2_features.t()
+    l2 = logit_scale2 * text1_features @ text2_features.t()
+    if correct_label:
+        targets = _eval_corrected_label(text1_features)
+    else:
+        targets = torch.arange(image_features.shape[0], device=image_features.device).long()
+    total = 0.0
+    for logits, w in ((l0, w1), (l1, w2), (l2, w1)):
+        total = total + _masked_pair_term(F.cross_entropy(logits, targets, reduction="none"), w)
+        total = total + _masked_pair_term(F.cross_entropy(logits.t(), targets, reduction="none"), w)
+    return total / 6
+
+
+def _evaluate_dict_batches(name, mm, model, data, epoch, args, tb_writer, pair_ranks):
+    """The loop behind ``evaluate_3modalities`` (mm == 'oct_faf_ir') and the two-tower dict-batch types of ``evaluate_multimodal``:
+    ``evaluate``'s gates, device-side accumulation, log line and files around the batch format of ``_run_epoch``."""
+    import json
+    import logging
+    import os
+    from . import misc
+    metrics = {}
+    if not misc.is_main_process():
+        return metrics
+    val_frequency = getattr(args, "val_frequency", 0)
+    if not ("val" in data and (val_frequency and ((epoch % val_frequency) == 0 or epoch == getattr(args, "epochs", None)))):
+        return metrics
+    three = mm == "oct_faf_ir"
+    device = torch.device(getattr(args, "device", "cuda"))
+    model.eval()
+    dataloader = data["val"].dataloader
+    samples_per_val = getattr(dataloader, "num_samples", None)
+    correct_label = bool(getattr(args, "correct_label", 0))
+    pair_ranks = _pair_ranks_arg(pair_ranks)
+    num_samples = 0
+    cumulative_loss = torch.zeros((), dtype=torch.float32, device=device)
+    all_feats, all_scales, all_weights = [], [], []
+    scales = None
+    with torch.no_grad():
+        for i, batch in enumerate(dataloader):
+            images, texts_ir, texts_f2_faf = batch[0]["oct"], batch[0]["ir"], batch[0]["f2_faf"]
+            modalities = batch[1][2]
+            if mm == "oct_ir":
+                inputs = (images, texts_ir)
+            elif mm == "oct_faf_only":
+                assert sum(modalities[2]) == len(modalities[2]), "Only f2_faf is allowed in this setting"
+                inputs = (images, texts_f2_faf)
+            else:
+                inputs = (images, texts_ir, texts_f2_faf)
+                weights = [convert_modalities_idx_to_flag(mod) for mod in modalities[:3]]
+                all_weights.append(weights)
+            inputs = tuple(x.to(device=device, non_blocking=True) for x in inputs)
+            out = model(*inputs)
+            nf = len(inputs)
+            with torch.autocast(device_type=device.type, enabled=False):
+                feats = [f.float() for f in out[:nf]]
+                scales = [s.float().mean() for s in out[nf:]]
+                batch_size = inputs[0].shape[0]
+                if three:
+                    w1, w2 = (w.to(device=device, dtype=torch.float32, non_blocking=True) for w in weights[1:3])
+                    total_loss = three_way_val_loss(*feats, *scales, w1, w2, correct_label)
+                else:
+                    logits_per_image = scales[0] * feats[0] @ feats[1].t()
+                    logits_per_text = logits_per_image.t()
+                    if correct_label:
+                        targets = _eval_corrected_label(feats[1])
+                        total_loss = (F.binary_cross_entropy_with_logits(logits_per_image, targets)
+                                      + F.binary_cross_entropy_with_logits(logits_per_text, targets)) / 2
+                    else:
+                        targets = torch.arange(batch_size, device=device).long()
+                        total_loss = (F.cross_entropy(logits_per_image, targets) + F.cross_entropy(logits_per_text, targets)) / 2
+                cumulative_loss += total_loss * batch_size
+            all_feats.append(feats)
+            all_scales.append(torch.stack(scales))
+            num_samples += batch_size
+            if (i % 100) == 0:
+                logging.info(f"Eval Epoch: {epoch} [{num_samples} / {samples_per_val}]")
+        if num_samples == 0:
+            raise ValueError(f"{name}: the validation loader is empty")
+        feats_all = [torch.cat([f[k] for f in all_feats]) for k in range(len(all_feats[0]))]
+        if three:
+            weights_all = stack_weight_modalities(all_weights)
+            val_metrics = get_metrics_3modalities(*feats_all, *scales, t_weight1=weights_all[1], t_weight2=weights_all[2],
+                                                  pair_ranks=pair_ranks)
+        else:
+            val_metrics = get_metrics(image_features=feats_all[0], text_features=feats_all[1], logit_scale=scales[0], pair_ranks=pair_ranks)
+        loss = cumulative_loss / num_samples
+        metrics.update({**{k: float(v) for k, v in val_metrics.items()}, "val_loss": loss.item(), "epoch": epoch,
+                        "num_samples": num_samples})
+    logging.info(f"Eval Epoch: {epoch} " + "\t".join([f"{k}: {round(v, 4):.4f}" for k, v in metrics.items()]))
+    if getattr(args, "save_logs", False):
+        for key, val in metrics.items():
+            if tb_writer is not None:
+                tb_writer.add_scalar(f"val/{key}", val, epoch)
+        with open(os.path.join(args.checkpoint_path, "results.jsonl"), "a+") as f:
+            f.write(json.dumps(metrics))
+            f.write("\n")
+        if getattr(args, "save_retrieval_results", False):
+            stacked = torch.stack(all_scales).cpu().numpy()                    # [batches, towers - 1 .. 3]
+            if three:
+                arrays = {"image_features": feats_all[0].cpu().numpy(), "text1_features": feats_all[1].cpu().numpy(),
+                          "text2_features": feats_all[2].cpu().numpy(), "t_weight1": weights_all[1].cpu().numpy(),
+                          "t_weight2": weights_all[2].cpu().numpy(), "logit_scale": stacked}
+            else:
+                arrays = {"image_features": feats_all[0].cpu().numpy(), "text_features": feats_all[1].cpu().numpy(),
+                          "logit_scale": stacked[:, 0]}
+            np.savez(os.path.join(args.checkpoint_path, f"retrieval_results_{epoch}.npz"), **arrays)
+    return metrics
+
+
+def evaluate_3modalities(model, data, epoch, args, tb_writer=None, pair_ranks=None):
+    """train_retclip_3modalities.evaluate for ``args.multimodal_type == 'oct_faf_ir'``: ``model(oct, ir, faf)`` on dict batches
+    (``batch[0]['oct' / 'ir' / 'f2_faf']``, presence flags ``batch[1][2]``, as ``train_one_epoch_3modalities`` takes them), the
+    per-batch ``three_way_val_loss`` in f32 outside any autocast, weighted by batch size and summed on the device with one
+    synchronisation at the end, and ``get_metrics_3modalities`` on the concatenated device features with the LAST batch's three
+    temperatures and the concatenated weights.  Gates, log line, ``results.jsonl`` and ``tb_writer`` scalars as ``evaluate``; returns
+    ``{}`` off the main process or when validation is not due, otherwise the 30 metrics plus ``val_loss``, ``epoch``, ``num_samples``.
+    ``pair_ranks``: None = ``PAIR_RANKS_DEFAULT``, True / False = the six directions from one launch of ``ops.retrieval_pair_ranks`` /
+    from six of ``ops.retrieval_ranks`` (the same integers), or a function of the former's signature.
+    With ``args.save_retrieval_results``: ``retrieval_results_{epoch}.npz`` with ``image_features``, ``text1_features``,
+    ``text2_features``, ``t_weight1``, ``t_weight2`` and ``logit_scale`` [batches, 3].  Departures: the reference's own saving block
+    names variables it never defines (it cannot run); zero-shot evaluation and wandb are not part of this package; a direction with no
+    present sample raises ValueError (``get_metrics_3modalities``) where the reference reports the mean of an empty selection."""
+    return _evaluate_dict_batches("evaluate_3modalities", "oct_faf_ir", model, data, epoch, args, tb_writer, pair_ranks)
+
+
+def evaluate_multimodal(model, data, epoch, args, tb_writer=None, pair_ranks=None):
+    """What a driver binds as ``evaluate``: dispatch on ``args.multimodal_type``.  None / 'default': ``evaluate``, unchanged (tuple
+    batches; ``pair_ranks`` plays no part).  'oct_ir' / 'oct_faf_only': the two-tower loop of train_retclip.py:292-300 on
+    ``batch[0]['oct']`` and ``batch[0]['ir']`` / ``batch[0]['f2_faf']`` (the latter with the reference's assertion that every FAF flag
+    is set), with ``evaluate``'s loss, ``correct_label`` BCE included, and the ``get_metrics`` keys; the saved file holds
+    ``image_features``, ``text_features`` and ``logit_scale`` (no labels, no top-k lists).  'oct_faf_ir': ``evaluate_3modalities``.
+    Anything else ('oct_f2_faf_inplace' included, which the reference leaves unfinished) raises NotImplementedError."""
+    from . import misc
+    if not misc.is_main_process():
+        return {}
+    mm = getattr(args, "multimodal_type", "default")
+    if mm in (None, "default"):
+        return evaluate(model, data, epoch, args, tb_writer)
+    if mm == "oct_faf_ir":
+        return evaluate_3modalities(model, data, epoch, args, tb_writer, pair_ranks)
+    if mm in ("oct_ir", "oct_faf_only"):
+        return _evaluate_dict_batches("evaluate_multimodal", mm, model, data, epoch, args, tb_writer, pair_ranks)
+    raise NotImplementedError(f"evaluate_multimodal: multimodal_type {mm!r} is not supported (only 'default', 'oct_ir', 'oct_faf_only', "
+                              "'oct_faf_ir')")

@@ -1249,6 +1249,53 @@ def retrieval_ranks(a: torch.Tensor, b: torch.Tensor, target: Optional[torch.Ten
     return out
 
 
+RETRIEVAL_PAIR_MAX = 3      # RP_MAX_PAIRS of csrc/retrieval_pair.hip
+
+
+def retrieval_pair_ranks(pairs) -> torch.Tensor:
+    """int32 [P, 2, N, 2] for ``pairs`` = P (1 .. 3) tuples (a_p, b_p) of float32 [N, D] features, N and D the same for all: one walk
+    over the f32 MFMA tiles of each product counts BOTH directions (csrc/retrieval_pair.hip), so
+
+      out[p, 0] == retrieval_ranks(a_p, b_p)[:, :2]      out[p, 1] == retrieval_ranks(b_p, a_p)[:, :2]
+
+    bit for bit (the partner of sample i is sample i; ``[..., 0] + [..., 1]`` is its place under a stable descending sort) at half the
+    matrix work of the 2 P launches.  No ``target``, ``keep`` or groups.  Operands may be slices of wider buffers (unit column stride,
+    any row stride >= D) and may be shared between pairs.  Non-finite features raise ValueError before the launch (one flag per
+    operand, read back together).  No autograd; no 16-bit operand, so autocast changes nothing."""
+    name = "retrieval_pair_ranks"
+    pairs = [tuple(p) for p in pairs] if isinstance(pairs, (list, tuple)) else None
+    if pairs is None or not 1 <= len(pairs) <= RETRIEVAL_PAIR_MAX or any(len(p) != 2 for p in pairs):
+        raise ValueError(f"{name}: expected a list of 1 .. {RETRIEVAL_PAIR_MAX} (a, b) pairs")
+    n, _, d = _pair_shapes(name, pairs[0][0], pairs[0][1], ())
+    checked = []
+    for a, b in pairs:
+        shape = _pair_shapes(name, a, b, ())
+        if shape != (n, n, d) or a.device != pairs[0][0].device:
+            raise ValueError(f"{name}: every operand must be [{n}, {d}] on one device, got {tuple(a.shape)} and {tuple(b.shape)} on "
+                             f"{a.device}")
+        a, b = a.detach(), b.detach()
+        checked.append((a, b) + _pair_strides(name, a, b))
+    dev = checked[0][0].device
+    # one flag per operand, one read-back (max |x| is finite iff every x is: a NaN propagates through the maximum)
+    bad = (~torch.isfinite(torch.stack([torch.linalg.vector_norm(t, ord=float("inf")) for a, b, _, _ in checked for t in (a, b)]))).tolist()
+    if any(bad):
+        k = bad.index(True)
+        raise ValueError(f"{name}: {'ab'[k % 2]} of pair {k // 2} contains non-finite values")
+    P = len(checked)
+    nws = int(load().octmae_retrieval_pair_ws(n, P))
+    if nws < 0:
+        raise ValueError(f"{name}: n = {n}, {P} pairs is beyond the kernel's workspace query")
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    out = torch.empty((P, 2, n, 2), dtype=torch.int32, device=dev)
+    args = []
+    for k in range(RETRIEVAL_PAIR_MAX):
+        args += [checked[k][0].data_ptr(), checked[k][2], checked[k][1].data_ptr(), checked[k][3]] if k < P else [None, 0, None, 0]
+    # algorithmic HBM bytes: every operand read once (the re-reads per tile hit the caches), the counts written once
+    _launch(name, 2.0 * P * n * n * d, float(8 * P * n * d + 16 * P * n),
+            lambda: call("octmae_retrieval_pair_ranks", *args, P, out.data_ptr(), ws.data_ptr(), nws, n, d, _stream()))
+    return out
+
+
 RETRIEVAL_TOPK_MAX = 32     # RT_KMAX of csrc/retrieval_topk.hip
 
 
