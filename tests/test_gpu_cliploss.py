@@ -5,14 +5,12 @@ reproducibility; ClipLoss / ThreeModalityClipLoss fused against their ATen compo
 import functools
 import json
 import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+from tests import children
 from tests import cliploss_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -236,12 +234,8 @@ def worker_results():
 def test_half_build_gives_the_same_bits():
     """The entry points have no 16-bit operand: liboctmae_f16.so must return bit-equal results (a child process, one library each)."""
     assert os.path.exists(LIB_F16), "make -C octcubem_amd/csrc both"
-    tmp = tempfile.mkdtemp(prefix="octmae_cliploss_f16_")
-    outp = os.path.join(tmp, "result.npz")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "cliploss_f16_worker.py"), "--out", outp]
-    child = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), capture_output=True, text=True, timeout=300)
-    assert child.returncode == 0 and os.path.exists(outp), f"rc {child.returncode}\n{child.stdout[-2000:]}\n{child.stderr[-2000:]}"
-    theirs = np.load(outp)
+    children.spawn_f16_worker("cliploss_f16", "tests.test_gpu_cliploss:worker_results", ext="npz")
+    theirs = children.f16_worker_result("cliploss_f16")
     meta = json.loads(str(theirs["meta"]))
     assert meta["lib"] == "liboctmae_f16.so" and meta["lp_is_f16"] is True
     mine = worker_results()

@@ -3,62 +3,55 @@
 One GPU is enough for the first group: a ONE-RANK communicator goes through the same ncclCommInitRank / ncclAllReduce /
 stream-and-event path as an 8-rank one (the collective itself degenerates to a copy), so it checks the bootstrap, the stream
 ordering (`after_stream` -> communication stream -> octmae_comm_wait) and the reducer's slice bookkeeping.
-The second group needs >= 2 GPUs on the box and is skipped otherwise: a fresh torchrun child (started at COLLECTION time,
-before this process touches the GPU) runs tests/dp_worker.py on 2 ranks and compares the exchanged gradients with the mean of
-the two ranks' local gradients computed in one process.
+The second group needs >= 2 GPUs on the box and is skipped otherwise: a fresh torchrun child (start_children(), called once the
+collection holds a test of this module and before this process touches the GPU) runs tests/dp_worker.py on 2 ranks and compares
+the exchanged gradients with the mean of the two ranks' local gradients computed in one process.
 """
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import pytest
 import torch
+
+from tests import children
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# ---- 2-rank child, launched before anything in this process initialises the GPU (device_count() does not) -------------------
-_CHILD = None
-_CHILD_OUT = None
-if os.environ.get("OCTMAE_SKIP_2GPU_TEST") is None and torch.cuda.device_count() >= 2:
-    _CHILD_OUT = tempfile.mkdtemp(prefix="octmae_dp_")
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OCTMAE_DP_OUT=_CHILD_OUT)
-    _CHILD = subprocess.Popen(
-        [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-         "--master-port", "29617", os.path.join(ROOT, "tests", "dp_worker.py")],
-        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+# ---- the multi-rank children: tests/conftest.py calls start_children() before anything in this process initialises the GPU
+# (device_count() does not) and only when a test of this module is selected; tests/children.py gates, bounds and reaps them ----------
+TWO_GPUS = torch.cuda.device_count() >= 2
+ONE_GPU = torch.cuda.device_count() >= 1
+RUN_2GPU = os.environ.get("OCTMAE_SKIP_2GPU_TEST") is None and TWO_GPUS
+RUN_GLOO = os.environ.get("OCTMAE_SKIP_2RANK_GLOO_TEST") is None and ONE_GPU
+RUN_BENCH4 = os.environ.get("OCTMAE_SKIP_BENCH4_TEST") is None and ONE_GPU
+RUN_FAIL = os.environ.get("OCTMAE_SKIP_COMM_FAIL_TEST") is None and ONE_GPU
 
-# ---- 2 ranks on ONE GPU, exchange over gloo (every box): the world-size-2 run of the GPU training path -----------------------
-_CHILD_GLOO = None
-_CHILD_GLOO_OUT = None
-if os.environ.get("OCTMAE_SKIP_2RANK_GLOO_TEST") is None and torch.cuda.device_count() >= 1:
-    _CHILD_GLOO_OUT = tempfile.mkdtemp(prefix="octmae_dp_gloo_")
-    env = dict(os.environ, OCTMAE_DP_OUT=_CHILD_GLOO_OUT, OCTMAE_DP_BACKEND="gloo")
-    _CHILD_GLOO = subprocess.Popen(
-        [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-         "--master-port", "29619", os.path.join(ROOT, "tests", "dp_worker.py")],
-        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
 
-# ---- bench.py itself with FOUR ranks on the one GPU (gloo): the multi-rank control flow of the script the driver launches on 8 ----
-_CHILD_BENCH4 = None
-if os.environ.get("OCTMAE_SKIP_BENCH4_TEST") is None and torch.cuda.device_count() >= 1:
-    _CHILD_BENCH4 = subprocess.Popen(
-        [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-         "--master-port", "29623", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--gloo-one-gpu", "--same-data",
-         "--global-batch", "16", "--micro-batch", "4", "--steps", "2", "--warmup", "2"],
-        cwd=ROOT, env=dict(os.environ), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+def _torchrun(ranks, port, *script):
+    return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
+            "--master-port", str(port), *script]
 
-# ---- 2 ranks, native backend, rank 1 fails to create its communicator: every rank must leave with status 3 -------------------------
-_CHILD_FAIL = None
-if os.environ.get("OCTMAE_SKIP_COMM_FAIL_TEST") is None and torch.cuda.device_count() >= 1:
-    _CHILD_FAIL = subprocess.Popen(
-        [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-         "--master-port", "29627", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
-        cwd=ROOT, env=dict(os.environ, OCTMAE_BENCH_FORCE_LOCAL_RANK="0", OCTMAE_BENCH_FAIL_COMM_RANK="1", HSA_ENABLE_IPC_MODE_LEGACY="0"),
-        stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+
+def start_children():
+    dp_worker = os.path.join(ROOT, "tests", "dp_worker.py")
+    if RUN_2GPU:            # 2 ranks, one GPU each, the native backend
+        children.spawn("dp_2gpu", _torchrun(2, 29617, dp_worker), gpu_procs=2, limit_s=900,
+                       env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OCTMAE_DP_OUT=children.tmpdir("dp_2gpu")))
+    if RUN_GLOO:            # 2 ranks on ONE GPU, exchange over gloo (every box): the world-size-2 run of the GPU training path
+        children.spawn("dp_gloo", _torchrun(2, 29619, dp_worker), gpu_procs=2, limit_s=900,
+                       env=dict(os.environ, OCTMAE_DP_OUT=children.tmpdir("dp_gloo"), OCTMAE_DP_BACKEND="gloo"))
+    if RUN_BENCH4:          # bench.py itself with FOUR ranks on the one GPU (gloo): the multi-rank control flow of the script the driver launches on 8
+        children.spawn("bench4", _torchrun(4, 29623, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--gloo-one-gpu", "--same-data",
+                                           "--global-batch", "16", "--micro-batch", "4", "--steps", "2", "--warmup", "2"),
+                       env=dict(os.environ), gpu_procs=4, limit_s=1500, stdout=os.path.join(children.tmpdir("bench4"), "stdout"))
+    if RUN_FAIL:            # 2 ranks, native backend, rank 1 fails to create its communicator: every rank must leave with status 3
+        children.spawn("comm_fail", _torchrun(2, 29627, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"),
+                       env=dict(os.environ, OCTMAE_BENCH_FORCE_LOCAL_RANK="0", OCTMAE_BENCH_FAIL_COMM_RANK="1", HSA_ENABLE_IPC_MODE_LEGACY="0"),
+                       gpu_procs=2, limit_s=240)
+
 
 if torch.cuda.is_available():
     from octcubem_amd import comm as ocomm, models_mae, misc, optim as foptim
@@ -206,27 +199,27 @@ def test_reducer_skips_the_exchange_on_accumulation_micro_steps(comm1):
     assert torch.isfinite(norm)
 
 
-@pytest.mark.skipif(_CHILD is None, reason="needs >= 2 GPUs on the box")
+@pytest.mark.skipif(not RUN_2GPU, reason="needs >= 2 GPUs on the box")
 def test_two_rank_gradients_equal_the_mean_of_the_local_ones():
-    out, _ = _CHILD.communicate(timeout=900)
-    assert _CHILD.returncode == 0, out.decode(errors="replace")[-4000:]
-    res = json.load(open(os.path.join(_CHILD_OUT, "result.json")))
+    start_children()
+    assert children.result("dp_2gpu").rc == 0, children.log_tail("dp_2gpu", 4000)
+    res = json.load(open(os.path.join(children.tmpdir("dp_2gpu"), "result.json")))
     assert res["world"] == 2 and res["backend"].startswith("octmae_comm")
     assert res["params_equal_after_broadcast"]
     assert res["max_rel_err"] <= 1e-5, res
     assert res["ranks_agree"]
 
 
-@pytest.mark.skipif(_CHILD_GLOO is None, reason="needs a GPU")
+@pytest.mark.skipif(not RUN_GLOO, reason="needs a GPU")
 def test_two_ranks_on_one_gpu_gradients_equal_the_mean_of_the_local_ones():
     """World size 2 ON HARDWARE with the box's one GPU: two processes share it, each runs the HIP training path on its own
     volumes, FlatGradReducer exchanges the gradient arena chunk by chunk from inside backward (torch.distributed gloo group on
     the device tensors: RCCL refuses two ranks on one device).  Three steps -- the learning step, then two with the frozen
     readiness layout (cold chunks exchanged at begin_backward) -- and after each the exchanged arena must equal the mean of the
     two ranks' local gradients, recomputed by every rank alone; different initial weights per rank check the broadcast."""
-    out, _ = _CHILD_GLOO.communicate(timeout=900)
-    assert _CHILD_GLOO.returncode == 0, out.decode(errors="replace")[-4000:]
-    res = json.load(open(os.path.join(_CHILD_GLOO_OUT, "result.json")))
+    start_children()
+    assert children.result("dp_gloo").rc == 0, children.log_tail("dp_gloo", 4000)
+    res = json.load(open(os.path.join(children.tmpdir("dp_gloo"), "result.json")))
     assert res["world"] == 2 and res["backend"].startswith("gloo")
     assert res["params_equal_after_broadcast"]
     assert res["max_rel_err"] <= 1e-5, res
@@ -235,7 +228,7 @@ def test_two_ranks_on_one_gpu_gradients_equal_the_mean_of_the_local_ones():
     assert res["reducer"]["launched_in_backward"] > 0
 
 
-@pytest.mark.skipif(_CHILD_BENCH4 is None, reason="needs a GPU")
+@pytest.mark.skipif(not RUN_BENCH4, reason="needs a GPU")
 def test_bench_script_with_four_ranks_prints_one_line_and_ranks_agree():
     """bench.py as the driver launches it (torch.distributed.run, one process per rank), world size 4, every rank on GPU 0 and
     the exchange over gloo (--gloo-one-gpu; RCCL refuses several ranks per device): ViT-L, global batch 16 as 4 volumes per rank.
@@ -243,9 +236,9 @@ def test_bench_script_with_four_ranks_prints_one_line_and_ranks_agree():
     and launch-order agreements, two frozen-layout steps, the max-over-ranks timing and rank 0's single JSON line.  With
     --same-data every rank holds the same weights, volumes and masking noise, so the ranks' losses must be BIT-equal after the
     exchanged optimizer steps."""
-    out, err = _CHILD_BENCH4.communicate(timeout=1500)
-    assert _CHILD_BENCH4.returncode == 0, err.decode(errors="replace")[-4000:]
-    lines = [l for l in out.decode().splitlines() if l.strip()]
+    start_children()
+    assert children.result("bench4").rc == 0, children.log_tail("bench4", 4000)
+    lines = [l for l in open(os.path.join(children.tmpdir("bench4"), "stdout")).read().splitlines() if l.strip()]
     assert len(lines) == 1, lines                                  # ONE line on stdout (banners and logs go to stderr)
     res = json.loads(lines[0])
     assert res["n_gpus"] == 4 and res["config"]["global_batch"] == 16 and res["config"]["micro_batch_per_gpu"] == 4
@@ -263,15 +256,13 @@ def test_every_rank_exits_3_when_one_rank_cannot_create_the_communicator():
     """bench.py --gpus 2 with the native backend: rank 1's communicator creation fails (simulated), rank 0 is then blocked inside the
     collective ncclCommInitRank waiting for it -- its watchdog thread must see the failure key in the control-plane store and end the
     process with status 3 (only the failing rank used to exit)."""
-    if _CHILD_FAIL is None:
+    if not RUN_FAIL:
         pytest.skip("no GPU at collection time")
-    try:
-        out, err = _CHILD_FAIL.communicate(timeout=240)
-    except subprocess.TimeoutExpired:
-        _CHILD_FAIL.kill()
-        raise AssertionError("the ranks did not end: a rank is still blocked in the communicator creation")
-    text = err.decode(errors="replace")
-    assert _CHILD_FAIL.returncode != 0
+    start_children()
+    rc = children.result("comm_fail").rc
+    assert rc != 124, "the ranks did not end: a rank is still blocked in the communicator creation"
+    text = children.log_tail("comm_fail", None)
+    assert rc != 0
     assert "simulated communicator failure" in text
     # (rank 0 ends through its own watchdog -- "a peer could not create ..." -- unless the launcher's SIGTERM, sent because rank 1
     # exited with an error, reaches it first: either way nobody is left blocked, which is what the time limit above checks)

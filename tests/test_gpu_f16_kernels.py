@@ -8,19 +8,18 @@ and activation sweeps of tests/test_gpu_gemm_elements.py and the planted NaN / I
 pytest process with OCTMAE_LIB pointing at the half build (the 16-bit type is chosen per process, before octcubem_amd is imported).
 
 The child is started once the collection is known to contain a test of this module (tests/conftest.py::pytest_collection_finish ->
-start_children()), writes its log to a file and its results to a JUnit XML file, runs under a wall-clock limit, and is reaped at
-exit.  The tests below read the XML: the child passed, every module ran at least as many tests as it holds today (a collection that
+start_children()) through tests/children.py, which logs it to a file, runs it under a wall-clock limit and reaps it at exit; its
+results go to a JUnit XML file.  The tests below read the XML: the child passed, every module ran at least as many tests as it holds today (a collection that
 quietly shrinks fails), and every skip is on the allowlist.
 """
-import atexit
 import os
 import re
-import subprocess
 import sys
-import tempfile
 import xml.etree.ElementTree as ET
 
 import pytest
+
+from tests import children
 
 pytestmark = pytest.mark.gpu
 
@@ -40,59 +39,39 @@ MIN_TESTS = {"tests.test_gpu_kernels": 533, "tests.test_gpu_gemm_small": 20, "te
 # (test id, skip reason) pairs the half build may skip: none today
 ALLOWED_SKIPS = set()
 
-_CHILD = {}
+CHILD = "f16_kernels"
 
 
-def _reap():
-    c = _CHILD.get("proc")
-    if c is not None and c.poll() is None:
-        c.kill()
-        try:
-            c.wait(timeout=10)
-        except subprocess.TimeoutExpired:
-            pass
-    if "logf" in _CHILD:
-        _CHILD["logf"].close()
+def _xml():
+    return os.path.join(children.tmpdir(CHILD), "junit.xml")
 
 
 def start_children():
-    """The half-build child (idempotent; nothing when the library is missing: _result() then fails with the build hint)."""
-    if _CHILD or not os.path.exists(LIB_F16):
-        return
-    tmp = tempfile.mkdtemp(prefix="octmae_f16_kernels_")
-    xml = os.path.join(tmp, "junit.xml")
-    logf = open(os.path.join(tmp, "child.log"), "wb")            # a file, not a pipe: the child never blocks on a full pipe
-    cmd = [sys.executable, "-m", "pytest", "-q", "-s", "-m", "gpu", "-p", "no:cacheprovider", f"--junitxml={xml}", *SUITES]
-    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdout=logf, stderr=subprocess.STDOUT),
-                  xml=xml, logf=logf, tmp=tmp)
-    atexit.register(_reap)
+    """The half-build child: a nested pytest session, one GPU process (nothing when the library is missing: _result() then fails with
+    the build hint)."""
+    if os.path.exists(LIB_F16):
+        cmd = [sys.executable, "-m", "pytest", "-q", "-s", "-m", "gpu", "-p", "no:cacheprovider", f"--junitxml={_xml()}", *SUITES]
+        children.spawn(CHILD, cmd, env=dict(os.environ, OCTMAE_LIB=LIB_F16), limit_s=TIMEOUT_S)
 
 
 _RESULT = {}
 
 
 def _log_tail(n=6000):
-    _CHILD["logf"].flush()
-    with open(_CHILD["logf"].name, "rb") as f:
-        text = f.read().decode(errors="replace")
-    return text if n is None else text[-n:]
+    return children.log_tail(CHILD, n)
 
 
 def _result():
     if _RESULT:
         return _RESULT
     start_children()
-    assert _CHILD, f"{LIB_F16} is missing: build it (python -c 'import __graft_entry__ as g; g.build()' or make -C octcubem_amd/csrc both)"
-    proc = _CHILD["proc"]
-    try:
-        proc.wait(timeout=TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        proc.kill()
-        proc.wait(timeout=30)
+    assert os.path.exists(LIB_F16), f"{LIB_F16} is missing: build it (python -c 'import __graft_entry__ as g; g.build()' or make -C octcubem_amd/csrc both)"
+    rc = children.result(CHILD).rc
+    if rc == 124:
         pytest.fail(f"the half-build kernel suite did not finish in {TIMEOUT_S} s:\n{_log_tail()}")
     cases = []
-    if os.path.exists(_CHILD["xml"]):
-        for tc in ET.parse(_CHILD["xml"]).getroot().iter("testcase"):
+    if os.path.exists(_xml()):
+        for tc in ET.parse(_xml()).getroot().iter("testcase"):
             status, msg = "passed", ""
             for kind in ("failure", "error", "skipped"):
                 el = tc.find(kind)
@@ -100,7 +79,7 @@ def _result():
                     status, msg = kind, el.get("message", "")
                     break
             cases.append((f"{tc.get('classname')}::{tc.get('name')}", status, msg))
-    _RESULT.update(rc=proc.returncode, cases=cases)
+    _RESULT.update(rc=rc, cases=cases)
     # the child's parity ledger (the u-scaled errors on half, printed by its session under -s) joins this session's, which
     # tests/conftest.py writes out at the end: one file holds both builds
     from tests import conftest
@@ -109,7 +88,7 @@ def _result():
         e = re.fullmatch(r"(\S+) (\S+) \(<= (\S+)\)", entry)
         if e:
             conftest._LEDGER.append((e.group(1), float(e.group(2)), float(e.group(3))))
-    print(f"\n[half-build kernel suite] exit code {proc.returncode}: " +
+    print(f"\n[half-build kernel suite] exit code {rc}: " +
           ", ".join(f"{mod} {c}" for mod, c in _counts(cases).items()))
     return _RESULT
 

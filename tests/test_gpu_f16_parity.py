@@ -19,17 +19,17 @@ Which gradient quantities meet 1e-3 on half and which do not, with the measured 
 profiles/r0x_f16_parity.json.
 
 Both children are started once the collection is known to contain a test of this module (tests/conftest.py::pytest_collection_finish
--> start_children(); a deselected module starts nothing), write their logs to files, and are ended with the session.
+-> start_children(); a deselected module starts nothing); tests/children.py releases them, logs them to files and ends them with the
+session.
 """
-import atexit
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import pytest
 import torch
+
+from tests import children
 
 pytestmark = pytest.mark.gpu
 
@@ -37,39 +37,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_BF16 = os.path.join(ROOT, "octcubem_amd", "liboctmae.so")
 LIB_F16 = os.path.join(ROOT, "octcubem_amd", "liboctmae_f16.so")
 
-_CHILDREN = {}
-_STARTED = False
-
-
-def _reap():
-    for child, _, logf in _CHILDREN.values():
-        if child.poll() is None:
-            child.kill()
-            try:
-                child.wait(timeout=10)
-            except subprocess.TimeoutExpired:
-                pass
-        logf.close()
+LIBS = {"bf16": LIB_BF16, "f16": LIB_F16}
 
 
 def start_children():
-    """Both ledgers, each in a process of its own, beside the test session (idempotent).  Called by the collection hook when at least
-    one test of this module is selected -- and by _ledger() itself when the module is driven without that hook."""
-    global _STARTED
-    if _STARTED:
-        return
-    _STARTED = True
+    """Both ledgers, each in a process of its own, beside the test session (tests/children.py).  Called by the collection hook when at
+    least one test of this module is selected -- and by _ledger() itself when the module is driven without that hook."""
     if os.environ.get("OCTMAE_SKIP_F16_TEST") is not None or torch.cuda.device_count() < 1:
         return
-    tmp = tempfile.mkdtemp(prefix="octmae_f16_")
-    for name, lib in (("bf16", LIB_BF16), ("f16", LIB_F16)):
+    for name, lib in LIBS.items():
         if os.path.exists(lib):
-            out = os.path.join(tmp, name + ".json")
-            logf = open(os.path.join(tmp, name + ".log"), "wb")          # a file, not a pipe: a child never blocks on a full pipe
-            _CHILDREN[name] = (subprocess.Popen(
-                [sys.executable, os.path.join(ROOT, "tests", "f16_parity_worker.py"), "--out", out],
-                cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=lib), stdout=logf, stderr=subprocess.STDOUT), out, logf)
-    atexit.register(_reap)
+            children.spawn("parity_" + name, [sys.executable, os.path.join(ROOT, "tests", "f16_parity_worker.py"), "--out",
+                                              os.path.join(children.tmpdir("parity_" + name), "ledger.json")],
+                           env=dict(os.environ, OCTMAE_LIB=lib), limit_s=1800)
 
 
 _RESULTS = {}
@@ -79,18 +59,10 @@ def _ledger(name):
     if name in _RESULTS:
         return _RESULTS[name]
     start_children()
-    assert name in _CHILDREN, (f"{LIB_F16 if name == 'f16' else LIB_BF16} is missing: build it "
-                               "(python -c 'import __graft_entry__ as g; g.build()' or make -C octcubem_amd/csrc both)")
-    child, out, logf = _CHILDREN[name]
-    try:
-        child.wait(timeout=1800)
-    except subprocess.TimeoutExpired:
-        child.kill()
-        raise
-    logf.flush()
-    log = open(logf.name, "rb").read()
-    assert child.returncode == 0, log.decode(errors="replace")[-4000:]
-    res = json.load(open(out))
+    assert os.path.exists(LIBS[name]), (f"{LIBS[name]} is missing: build it "
+                                        "(python -c 'import __graft_entry__ as g; g.build()' or make -C octcubem_amd/csrc both)")
+    assert children.result("parity_" + name).rc == 0, children.log_tail("parity_" + name, 4000)
+    res = json.load(open(os.path.join(children.tmpdir("parity_" + name), "ledger.json")))
     _RESULTS[name] = res
     try:                                        # kept beside the parity ledger of the session (copied to profiles/ per round)
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)

@@ -1,12 +1,9 @@
 """GPU: the join kernels (octcubem_amd/csrc/join.hip through ops.join_fwd / ops.join_bwd / ops.JoinFn) at their dispatch edges, every
 output element against the float64 reference and the derived bounds of tests/join_ref.py (tests/test_cpu_join.py shows what those bounds
 pass and what they catch); determinism and accumulation of the parameter gradients; the refusals; the weight-gradient switch; autocast;
-and the same cases on the half-operand build in a child process (tests/join_f16_worker.py)."""
+and the same cases on the half-operand build in a child process (tests/f16_worker.py)."""
 import json
 import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -16,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from octcubem_amd import _lib, coem, ops
+from tests import children
 from tests import join_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -244,12 +242,8 @@ def test_join_on_the_half_operand_build():
     """the same cases on liboctmae_f16.so in a fresh child process (a process binds one library): y against the bounds for one rounding to
     half; everything that never meets the 16-bit type is the same f32 code in both builds and must come back bit-equal"""
     assert os.path.exists(LIB_F16), f"{LIB_F16} is missing: __graft_entry__.build() makes it"
-    tmp = tempfile.mkdtemp(prefix="octmae_join_f16_")
-    outp = os.path.join(tmp, "result.npz")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "join_f16_worker.py"), "--out", outp]
-    child = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), capture_output=True, text=True, timeout=300)
-    assert child.returncode == 0 and os.path.exists(outp), f"rc {child.returncode}\n{child.stdout[-2000:]}\n{child.stderr[-2000:]}"
-    theirs = np.load(outp)
+    children.spawn_f16_worker("join_f16", "tests.test_gpu_join:worker_results", ext="npz")
+    theirs = children.f16_worker_result("join_f16")
     meta = json.loads(str(theirs["meta"]))
     assert meta["lib"] == "liboctmae_f16.so" and meta["lp_is_f16"] is True
     mine = worker_results()

@@ -1,25 +1,21 @@
 """GPU tests of the fine-tune evaluation: octmae_rank_counts (ops.rank_counts) against the numpy comparison table of
 tests/metrics_ref.py -- EQUAL, as integers -- at every edge of the 256-wide block of i and the 1024-wide LDS tile of j, once more on
-the half-operand build in a child process (tests/metrics_f16_worker.py, started before this process touches the GPU), and
+the half-operand build in a child process (tests/f16_worker.py, started before this process touches the GPU), and
 engine_finetune.evaluate_report end to end on a small ST ViT.
 
 End to end: ``loss`` and ``acc1`` against the existing ``evaluate`` on the same loader to 1e-6 (the same per-batch fp32 losses, summed in
 float64 on the device instead of on the host), ``auc_roc`` / ``auc_pr`` against the sort-based float64 references applied to the
 logits ``evaluate`` returns to 1e-12 (a few float64 divisions and sums of at most 13 terms: a few ulp), the CSV row parsed back."""
-import atexit
 import csv
 import functools
-import json
 import os
-import subprocess
-import sys
-import tempfile
 from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
+from tests import children
 from tests import metrics_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -264,40 +260,24 @@ def test_evaluate_report_raises_when_a_class_is_missing(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- the half build
-_CHILD = {}
-
-
-def _reap():
-    c = _CHILD.get("proc")
-    if c is not None and c.poll() is None:
-        c.kill()
-        try:
-            c.wait(timeout=10)
-        except subprocess.TimeoutExpired:
-            pass
-    if "logf" in _CHILD:
-        _CHILD["logf"].close()
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build."""
+    for case in COUNT_CASES:
+        check_counts(*case)
+    return {"passed": [list(c) for c in COUNT_CASES]}
 
 
 def start_children():
-    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU."""
-    if _CHILD or not os.path.exists(LIB_F16):
-        return
-    tmp = tempfile.mkdtemp(prefix="octmae_metrics_f16_")
-    logf = open(os.path.join(tmp, "child.log"), "wb")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "metrics_f16_worker.py"), "--out", os.path.join(tmp, "result.json")]
-    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdout=logf, stderr=subprocess.STDOUT),
-                  out=os.path.join(tmp, "result.json"), log=os.path.join(tmp, "child.log"), logf=logf)
-    atexit.register(_reap)
+    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU;
+    tests/children.py releases the worker when the GPU has room for it."""
+    if os.path.exists(LIB_F16):
+        children.spawn_f16_worker("metrics_f16", "tests.test_gpu_metrics:half_build_cases")
 
 
 def test_half_build_runs_the_same_rank_count_kernel():
     """The entry point has no 16-bit operand: liboctmae_f16.so must give the same counts on every count case."""
     assert os.path.exists(LIB_F16), "make -C octcubem_amd/csrc both"
     start_children()
-    rc = _CHILD["proc"].wait(timeout=300)
-    log = open(_CHILD["log"], errors="replace").read()[-3000:]
-    assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
-    res = json.load(open(_CHILD["out"]))
+    res = children.f16_worker_result("metrics_f16")
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
     assert res["passed"] == [list(c) for c in COUNT_CASES], res

@@ -1,26 +1,22 @@
 """GPU tests of the multi-task and regression fine-tune modes: octmae_rank_counts_masked (ops.rank_counts_masked) against the numpy
 restatement of tests/multitask_ref.py (compress, count, scatter) -- EQUAL, as integers -- at every edge of the 256-wide block of i
 and the 1024-wide LDS tile of j, for four score families and seven mask families, once more on the half-operand build in a child
-process (tests/multitask_f16_worker.py, started before this process touches the GPU and released when its test runs), and engine_finetune.evaluate_task_report /
+process (tests/f16_worker.py, started gated before this process touches the GPU: tests/children.py), and engine_finetune.evaluate_task_report /
 train_one_epoch end to end on the small ST ViT of tests/test_gpu_metrics.py.
 
 End to end the report is recomputed by metrics.misc_measures_multi_task with the numpy stand-in on the logits THE RUN produced (a
 forward hook keeps them: a repeated forward is not promised bit for bit) to the 1e-12 of the goldens (tests/test_cpu_metrics.py: TOL),
 and the loss is held against the float64 loop within (k + 8) * 2^-24 * sum|term| (tests/test_cpu_multitask.py)."""
-import atexit
 import csv
 import functools
-import json
 import os
-import subprocess
-import sys
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+from tests import children
 from tests import multitask_ref as M
 from tests.test_cpu_metrics import TOL
 from tests.test_gpu_metrics import FAMILIES, NS, SPECIAL, small_vit
@@ -421,33 +417,18 @@ def test_the_new_loss_functions_ignore_autocast():
 
 
 # ---------------------------------------------------------------------------------------------- the half build
-_CHILD = {}
-
-
-def _reap():
-    c = _CHILD.get("proc")
-    if c is not None and c.poll() is None:
-        c.kill()
-        try:
-            c.wait(timeout=10)
-        except subprocess.TimeoutExpired:
-            pass
-    if "logf" in _CHILD:
-        _CHILD["logf"].close()
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build."""
+    for case in MASKED_CASES:
+        check_masked(*case)
+    return {"passed": [list(c) for c in MASKED_CASES]}
 
 
 def start_children():
-    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU.  The
-    child does not open the GPU yet: it waits for a line on its stdin (tests/multitask_f16_worker.py says why)."""
-    if _CHILD or not os.path.exists(LIB_F16):
-        return
-    tmp = tempfile.mkdtemp(prefix="octmae_multitask_f16_")
-    logf = open(os.path.join(tmp, "child.log"), "wb")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "multitask_f16_worker.py"), "--out", os.path.join(tmp, "result.json")]
-    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdin=subprocess.PIPE, stdout=logf,
-                                        stderr=subprocess.STDOUT),
-                  out=os.path.join(tmp, "result.json"), log=os.path.join(tmp, "child.log"), logf=logf)
-    atexit.register(_reap)
+    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU;
+    tests/children.py releases the worker when the GPU has room for it."""
+    if os.path.exists(LIB_F16):
+        children.spawn_f16_worker("multitask_f16", "tests.test_gpu_multitask:half_build_cases", limit_s=240)
 
 
 def test_half_build_runs_the_same_masked_kernel():
@@ -455,13 +436,6 @@ def test_half_build_runs_the_same_masked_kernel():
     before this process touched the GPU; it is released here and then runs under its own time limit."""
     assert os.path.exists(LIB_F16), "make -C octcubem_amd/csrc both"
     start_children()
-    proc = _CHILD["proc"]
-    assert proc.poll() is None, "the child ended before it was asked to run"
-    proc.stdin.write(b"go\n")
-    proc.stdin.close()
-    rc = proc.wait(timeout=300)
-    log = open(_CHILD["log"], errors="replace").read()[-3000:]
-    assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
-    res = json.load(open(_CHILD["out"]))
+    res = children.f16_worker_result("multitask_f16")
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
     assert res["passed"] == [list(c) for c in MASKED_CASES], res

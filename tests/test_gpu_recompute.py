@@ -4,16 +4,15 @@ The contract is bit equality throughout: ``ops.ln_apply`` against the ``y`` of `
 ``act`` of the fc1 epilogue, and -- every launch being deterministic -- outputs, input gradients and accumulated parameter gradients of
 a Block and of whole models at levels light and full against level none.  What each level keeps is counted in bytes through
 ``torch.autograd.graph.saved_tensors_hooks``.  The kernel checks run again on the half-operand build in a child process
-(tests/recompute_f16_worker.py)."""
-import json
+(tests/f16_worker.py)."""
 import os
-import subprocess
-import sys
-import tempfile
+import traceback
 from functools import partial
 
 import pytest
 import torch
+
+from tests import children
 
 pytestmark = pytest.mark.gpu
 
@@ -170,13 +169,23 @@ def test_kernels(name):
     KERNEL_CHECKS[name]()
 
 
+def half_build_kernel_checks():
+    """What tests/f16_worker.py runs on the half-operand build: every check, a failed one recorded with its traceback."""
+    ran, failed = [], {}
+    for name, fn in KERNEL_CHECKS.items():
+        ran.append(name)
+        try:
+            fn()
+            torch.cuda.synchronize()
+        except AssertionError:
+            failed[name] = traceback.format_exc()[-1500:]
+    return {"ran": ran, "failed": failed}
+
+
 def test_kernels_on_the_half_build():
     assert os.path.exists(LIB_F16), f"{LIB_F16} is missing: __graft_entry__.build() makes it"
-    outp = os.path.join(tempfile.mkdtemp(prefix="octmae_recompute_f16_"), "result.json")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "recompute_f16_worker.py"), "--out", outp]
-    child = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), capture_output=True, text=True, timeout=300)
-    assert child.returncode == 0 and os.path.exists(outp), f"rc {child.returncode}\n{child.stdout[-2000:]}\n{child.stderr[-2000:]}"
-    res = json.load(open(outp))
+    children.spawn_f16_worker("recompute_f16", "tests.test_gpu_recompute:half_build_kernel_checks")
+    res = children.f16_worker_result("recompute_f16")
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
     assert res["ran"] == list(KERNEL_CHECKS) and res["failed"] == {}, res["failed"]
 

@@ -1,24 +1,20 @@
 """GPU tests of the reconstruction volumes: octmae_mae_compose called directly (ops.mae_compose) against the torch restatement of the
 reference's chain (tests/recon_ref.py; cases (a) and (b) are tests/golden/recon_small.npz, which the reference's own functions wrote),
 ``MaskedAutoencoderViT.reconstruct`` on a model, ``engine_pretrain.eval_one_epoch`` with its dump, and the direct cases once more on the
-half-operand build in a child process (tests/recon_f16_worker.py, started before this process touches the GPU).
+half-operand build in a child process (tests/f16_worker.py, started before this process touches the GPU).
 
 Without ``denorm`` every voxel of all four panels must be EQUAL: the kernel rounds where the reference's tensor ops round.  With it the
 reference is the fp64 restatement: every voxel within one grey level, and equal wherever the fp64 value before truncation is farther
 than 1e-3 from an integer -- the fp32 chain (mean and variance of at most 768 values, one sqrt, one fma, g) is off by a few ulp of 255,
 about 1e-4, and 1e-3 is ten times that; at least 95 % of the voxels are in that class (tests/test_cpu_recon.py shows it for these inputs)."""
-import atexit
-import json
 import os
-import subprocess
-import sys
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+from tests import children
 from tests import recon_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -230,40 +226,32 @@ def test_eval_one_epoch_on_a_two_batch_loader(golden_dir, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- the half build
-_CHILD = {}
-
-
-def _reap():
-    c = _CHILD.get("proc")
-    if c is not None and c.poll() is None:
-        c.kill()
-        try:
-            c.wait(timeout=10)
-        except subprocess.TimeoutExpired:
-            pass
-    if "logf" in _CHILD:
-        _CHILD["logf"].close()
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build."""
+    golden, passed = os.path.join(ROOT, "tests", "golden"), []
+    for name in DIRECT:
+        check_direct(name, golden)
+        passed.append(name)
+    for name in ("a", "d"):
+        check_denorm(name, golden)
+        passed.append("denorm " + name)
+    for denorm in (False, True):
+        check_past_the_grid_cap(denorm)
+        passed.append("past the cap denorm" if denorm else "past the cap")
+    return {"passed": passed}
 
 
 def start_children():
-    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU."""
-    if _CHILD or not os.path.exists(LIB_F16):
-        return
-    tmp = tempfile.mkdtemp(prefix="octmae_recon_f16_")
-    logf = open(os.path.join(tmp, "child.log"), "wb")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "recon_f16_worker.py"), "--out", os.path.join(tmp, "result.json")]
-    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdout=logf, stderr=subprocess.STDOUT),
-                  out=os.path.join(tmp, "result.json"), log=os.path.join(tmp, "child.log"), logf=logf)
-    atexit.register(_reap)
+    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU;
+    tests/children.py releases the worker when the GPU has room for it."""
+    if os.path.exists(LIB_F16):
+        children.spawn_f16_worker("recon_f16", "tests.test_gpu_recon:half_build_cases")
 
 
 def test_half_build_runs_the_same_compose_kernel():
     """The entry point has no 16-bit operand: liboctmae_f16.so must give the same panels on every direct case and both denorm cases."""
     assert os.path.exists(LIB_F16), "make -C octcubem_amd/csrc both"
     start_children()
-    rc = _CHILD["proc"].wait(timeout=300)
-    log = open(_CHILD["log"], errors="replace").read()[-3000:]
-    assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
-    res = json.load(open(_CHILD["out"]))
+    res = children.f16_worker_result("recon_f16")
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
     assert res["passed"] == [*DIRECT, "denorm a", "denorm d", "past the cap", "past the cap denorm"], res

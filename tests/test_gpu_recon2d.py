@@ -2,19 +2,15 @@
 buffers that sit between guard bytes, against the restatements of tests/recon2d_ref.py and the fixture the reference's own functions
 wrote (tests/golden/recon2d_small.npz); then ``reconstruct`` on the 2-D MAE and on the joint model's B-scan branch,
 ``engine_pretrain.eval_one_epoch`` with its 2-D loader, and the direct cases once more on the half-operand build in a child process
-(tests/recon2d_f16_worker.py, started before this process touches the GPU).
+(tests/f16_worker.py, started before this process touches the GPU).
 
 Without ``denorm`` every byte of all four panels must be EQUAL: the kernel rounds where the reference's tensor ops round.  With it the
 reference is the fp64 restatement, under the rule of tests/test_gpu_recon.py: every value within one level, and equal wherever the fp64
 value before truncation is farther than 1e-3 from an integer (the fp32 chain -- mean and variance of at most 768 values, one sqrt, one
 fma, the level -- is off by a few ulp of 255, about 1e-4); at least 95 % of the values are in that class
 (tests/test_cpu_recon2d.py shows it for these inputs).  The blanked images and the regions must be EQUAL to the fixture."""
-import atexit
 import json
 import os
-import subprocess
-import sys
-import tempfile
 import types
 from functools import partial
 
@@ -22,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import children
 from tests import recon2d_ref as R
 from tests import recon_ref as R0
 
@@ -359,40 +356,34 @@ def test_eval_one_epoch_writes_the_3d_and_the_2d_files(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- the half build
-_CHILD = {}
-
-
-def _reap():
-    c = _CHILD.get("proc")
-    if c is not None and c.poll() is None:
-        c.kill()
-        try:
-            c.wait(timeout=10)
-        except subprocess.TimeoutExpired:
-            pass
-    if "logf" in _CHILD:
-        _CHILD["logf"].close()
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build."""
+    golden, passed = os.path.join(ROOT, "tests", "golden"), []
+    for name in DIRECT:
+        check_direct(name, golden)
+        passed.append(name)
+    for name in DENORM:
+        check_denorm(name)
+        passed.append("denorm " + name)
+    check_past_the_grid_cap()
+    passed.append("past the cap")
+    for name in BLANK:
+        check_blank(name)
+        passed.append("blank " + name)
+    return {"passed": passed}
 
 
 def start_children():
-    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU."""
-    if _CHILD or not os.path.exists(LIB_F16):
-        return
-    tmp = tempfile.mkdtemp(prefix="octmae_recon2d_f16_")
-    logf = open(os.path.join(tmp, "child.log"), "wb")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "recon2d_f16_worker.py"), "--out", os.path.join(tmp, "result.json")]
-    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdout=logf, stderr=subprocess.STDOUT),
-                  out=os.path.join(tmp, "result.json"), log=os.path.join(tmp, "child.log"), logf=logf)
-    atexit.register(_reap)
+    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU;
+    tests/children.py releases the worker when the GPU has room for it."""
+    if os.path.exists(LIB_F16):
+        children.spawn_f16_worker("recon2d_f16", "tests.test_gpu_recon2d:half_build_cases")
 
 
 def test_half_build_runs_the_same_kernels():
     """Neither entry point has a 16-bit operand: liboctmae_f16.so must pass every direct compose and blanking case."""
     assert os.path.exists(LIB_F16), "make -C octcubem_amd/csrc both"
     start_children()
-    rc = _CHILD["proc"].wait(timeout=300)
-    log = open(_CHILD["log"], errors="replace").read()[-3000:]
-    assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
-    res = json.load(open(_CHILD["out"]))
+    res = children.f16_worker_result("recon2d_f16")
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
     assert res["passed"] == [*DIRECT, *("denorm " + n for n in DENORM), "past the cap", *("blank " + n for n in BLANK)], res

@@ -13,13 +13,9 @@ features with a tenth of b's rows bit copies of other rows: a copy of the target
 fails when t_i is not the tile's own value.  ``continuous``: with float64 scores and beta_ij = d 2^-23 sum_k |a_ik b_jk| (twice the
 gamma_d bound of an f32 chain of d terms, unit roundoff 2^-24) the position must lie in [lo_i, hi_i]; at most 5 % of the rows may have
 lo != hi and R@1 must be neither 0 nor 1, both asserted, so the case cannot be hollow."""
-import atexit
 import functools
 import json
 import os
-import subprocess
-import sys
-import tempfile
 import types
 from functools import partial
 
@@ -27,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import children
 from tests import retrieval_ref as R
 from tests import test_cpu_retrieval as G
 
@@ -405,40 +402,24 @@ def test_evaluate_end_to_end(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- the half build
-_CHILD = {}
-
-
-def _reap():
-    c = _CHILD.get("proc")
-    if c is not None and c.poll() is None:
-        c.kill()
-        try:
-            c.wait(timeout=10)
-        except subprocess.TimeoutExpired:
-            pass
-    if "logf" in _CHILD:
-        _CHILD["logf"].close()
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build."""
+    for case in DYADIC_CASES:
+        check_dyadic(*case)
+    return {"passed": [list(c) for c in DYADIC_CASES]}
 
 
 def start_children():
-    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU."""
-    if _CHILD or not os.path.exists(LIB_F16):
-        return
-    tmp = tempfile.mkdtemp(prefix="octmae_retrieval_f16_")
-    logf = open(os.path.join(tmp, "child.log"), "wb")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "retrieval_f16_worker.py"), "--out", os.path.join(tmp, "result.json")]
-    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdout=logf, stderr=subprocess.STDOUT),
-                  out=os.path.join(tmp, "result.json"), log=os.path.join(tmp, "child.log"), logf=logf)
-    atexit.register(_reap)
+    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU;
+    tests/children.py releases the worker when the GPU has room for it."""
+    if os.path.exists(LIB_F16):
+        children.spawn_f16_worker("retrieval_f16", "tests.test_gpu_retrieval:half_build_cases")
 
 
 def test_half_build_runs_the_same_retrieval_kernel():
     """The entry point has no 16-bit operand: liboctmae_f16.so must give the same counts on every dyadic case."""
     assert os.path.exists(LIB_F16), "make -C octcubem_amd/csrc both"
     start_children()
-    rc = _CHILD["proc"].wait(timeout=300)
-    log = open(_CHILD["log"], errors="replace").read()[-3000:]
-    assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
-    res = json.load(open(_CHILD["out"]))
+    res = children.f16_worker_result("retrieval_f16")
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
     assert res["passed"] == [list(c) for c in DYADIC_CASES], res

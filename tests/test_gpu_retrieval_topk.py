@@ -8,19 +8,15 @@ chain is exact, retrieval_ref.chain_scores IS the kernel's score and indices and
 tests/retrieval_topk_ref.py -- ties in every row pin the tie rule, keep, the groups and the padding.  ``continuous``: unit-norm rows,
 four conditions per element against the float64 score S and the standard bound of an f32 chain of d terms,
 e(i, j) = gamma_d sum_k |a_ik b_jk|, gamma_d = d u / (1 - d u), u = 2^-24."""
-import atexit
 import functools
-import json
 import os
-import subprocess
-import sys
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+from tests import children
 from tests import retrieval_ref as R
 from tests import retrieval_topk_ref as T
 
@@ -445,33 +441,18 @@ def test_evaluate_saves_the_lists_and_the_report_reads_them(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- the half build
-_CHILD = {}
-
-
-def _reap():
-    c = _CHILD.get("proc")
-    if c is not None and c.poll() is None:
-        c.kill()
-        try:
-            c.wait(timeout=10)
-        except subprocess.TimeoutExpired:
-            pass
-    if "logf" in _CHILD:
-        _CHILD["logf"].close()
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build."""
+    for case in DYADIC_CASES:
+        check_dyadic(*case)
+    return {"passed": [list(c) for c in DYADIC_CASES]}
 
 
 def start_children():
-    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU.  The
-    child does not open the GPU yet: it waits for a line on its stdin (tests/retrieval_topk_f16_worker.py says why)."""
-    if _CHILD or not os.path.exists(LIB_F16):
-        return
-    tmp = tempfile.mkdtemp(prefix="octmae_retrieval_topk_f16_")
-    logf = open(os.path.join(tmp, "child.log"), "wb")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "retrieval_topk_f16_worker.py"), "--out", os.path.join(tmp, "result.json")]
-    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdin=subprocess.PIPE, stdout=logf,
-                                        stderr=subprocess.STDOUT),
-                  out=os.path.join(tmp, "result.json"), log=os.path.join(tmp, "child.log"), logf=logf)
-    atexit.register(_reap)
+    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU;
+    tests/children.py releases the worker when the GPU has room for it."""
+    if os.path.exists(LIB_F16):
+        children.spawn_f16_worker("retrieval_topk_f16", "tests.test_gpu_retrieval_topk:half_build_cases", limit_s=240)
 
 
 def test_half_build_runs_the_same_topk_kernel():
@@ -479,13 +460,6 @@ def test_half_build_runs_the_same_topk_kernel():
     before this process touched the GPU; it is released here and then runs under its own time limit."""
     assert os.path.exists(LIB_F16), "make -C octcubem_amd/csrc both"
     start_children()
-    proc = _CHILD["proc"]
-    assert proc.poll() is None, "the child ended before it was asked to run"
-    proc.stdin.write(b"go\n")
-    proc.stdin.close()
-    rc = proc.wait(timeout=300)
-    log = open(_CHILD["log"], errors="replace").read()[-3000:]
-    assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
-    res = json.load(open(_CHILD["out"]))
+    res = children.f16_worker_result("retrieval_topk_f16")
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
     assert res["passed"] == [list(c) for c in DYADIC_CASES], res

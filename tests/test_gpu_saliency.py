@@ -1,13 +1,9 @@
 """GPU tests of the saliency path: the four kernels of csrc/saliency.hip against the restatements of tests/saliency_ref.py, the image
 gradient of PatchEmbedFn against a float64 GEMM, ops.weight_grads, octcubem_amd.saliency on small models against autograd through the CPU
-oracle, and scatter / patch-embed / model parity once more on the half-operand build in a child process (tests/saliency_f16_worker.py,
-started before this process touches the GPU; it opens the GPU only once the first test of this module runs)."""
-import atexit
+oracle, and scatter / patch-embed / model parity once more on the half-operand build in a child process (tests/f16_worker.py,
+started before this process touches the GPU; tests/children.py releases it when the GPU has room)."""
 import json
 import os
-import subprocess
-import sys
-import tempfile
 import types
 from functools import lru_cache, partial
 
@@ -23,6 +19,7 @@ LIB_F16 = os.path.join(ROOT, "octcubem_amd", "liboctmae_f16.so")
 if torch.cuda.is_available():
     from octcubem_amd import _lib, models_mae, models_vit, models_vit_3dhead, models_vit_flash_attn, models_vit_st, ops, saliency, video_vit
 from oracle import vit_ref as V
+from tests import children
 from tests import saliency_ref as R
 from tests.conftest import parity
 from tests.gemm_elem import LP_U, acc_bound, lp_round_bound, worst
@@ -669,49 +666,20 @@ def test_mae_backward_with_an_image_gradient_fails_loudly():
 
 
 # ---- 12: the half-operand build, in a child process ------------------------------------------------------------------------------------
-_CHILD = {}
-
-
-def _reap():
-    c = _CHILD.get("proc")
-    if c is not None and c.poll() is None:
-        c.kill()
-        try:
-            c.wait(timeout=10)
-        except subprocess.TimeoutExpired:
-            pass
-    if "logf" in _CHILD:
-        _CHILD["logf"].close()
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build."""
+    ops.ATTN_BWD_FUSED_MIN_FILL = 0.0                    # as tests/conftest.py sets it for every GPU test
+    res = {"scatter_cases": sum(check_scatter(*geom) for geom in SCATTER_GEOM) + check_scatter_past_the_grid_cap()}
+    res["patch_embed"] = {f"{kind} {ids}": check_patch_embed(kind, ids) for kind in ("3d", "2d") for ids in (False, True)}
+    res["parity"] = {v: measure_model_parity(v)[0] for v in ("native", "flash_compat", "flash_blocks", "vit2d")}
+    return res
 
 
 def start_children():
-    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU.  The
-    child does not open the GPU yet: it waits for a line on its stdin (tests/saliency_f16_worker.py says why)."""
-    if _CHILD or not os.path.exists(LIB_F16):
-        return
-    tmp = tempfile.mkdtemp(prefix="octmae_saliency_f16_")
-    logf = open(os.path.join(tmp, "child.log"), "wb")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "saliency_f16_worker.py"), "--out", os.path.join(tmp, "result.json")]
-    _CHILD.update(proc=subprocess.Popen(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), stdin=subprocess.PIPE, stdout=logf,
-                                        stderr=subprocess.STDOUT),
-                  out=os.path.join(tmp, "result.json"), log=os.path.join(tmp, "child.log"), logf=logf)
-    atexit.register(_reap)
-
-
-def release_child():
-    """Lets the child open the GPU.  Once only: the pipe is closed after the line."""
-    proc = _CHILD.get("proc")
-    if proc is not None and proc.stdin is not None and not proc.stdin.closed and proc.poll() is None:
-        proc.stdin.write(b"go\n")
-        proc.stdin.close()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _half_build_child_runs_beside_this_module():
-    """The helper processes of the modules that ran before this one have ended by now, so the child shares the GPU with this process
-    alone and its checks overlap the tests above instead of adding their time to the last one."""
-    release_child()
-    yield
+    """tests/conftest.py calls this once the collection holds a test of this module, before this process has touched the GPU;
+    tests/children.py releases the worker when the GPU has room for it."""
+    if os.path.exists(LIB_F16):
+        children.spawn_f16_worker("saliency_f16", "tests.test_gpu_saliency:half_build_cases", limit_s=240)
 
 
 # 1.5 x the value measured on MI355X with the half build; measured values beside them
@@ -726,11 +694,7 @@ PARITY_BOUND_F16 = {
 def test_half_build_scatter_patch_embed_and_model_parity():
     assert os.path.exists(LIB_F16), "make -C octcubem_amd/csrc both"
     start_children()
-    release_child()
-    rc = _CHILD["proc"].wait(timeout=300)
-    log = open(_CHILD["log"], errors="replace").read()[-3000:]
-    assert rc == 0 and os.path.exists(_CHILD["out"]), f"rc {rc}\n{log}"
-    res = json.load(open(_CHILD["out"]))
+    res = children.f16_worker_result("saliency_f16")
     assert res["lib"] == "liboctmae_f16.so" and res["lp_is_f16"] is True
     assert res["scatter_cases"] == 20 * len(SCATTER_GEOM) + 1 and len(res["patch_embed"]) == 4 and max(res["patch_embed"].values()) <= 1.0
     for variant in PARITY_BOUND_F16:

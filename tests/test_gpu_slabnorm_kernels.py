@@ -11,12 +11,8 @@ both store paths (L % 8 == 0: 16-byte pieces; otherwise element by element); a r
 Every output and the workspace sit between guard elements that must keep their value; the workspace is handed over filled with the
 guard value (it needs no initialisation); prefix rows of dx are exact zeros; dgamma / dbeta accumulate onto a non-zero start; NULL
 pointers change nothing else; two runs are bit-equal.  The same checks run on the half-operand build in a child process
-(tests/slabnorm_f16_worker.py)."""
-import json
+(tests/f16_worker.py)."""
 import os
-import subprocess
-import sys
-import tempfile
 
 import pytest
 import torch
@@ -25,10 +21,9 @@ pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from octcubem_amd import _lib, ops
+from tests import children
 from tests import slabnorm_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_F16 = os.path.join(ROOT, "octcubem_amd", "liboctmae_f16.so")
 DEV = "cuda"
 EPS = 1e-5
 GUARD = 256            # elements in front of and behind every output (a multiple of 8: the 16-byte alignment survives in both widths)
@@ -163,10 +158,12 @@ def test_wrappers_refuse_before_launching():
     check_wrappers()
 
 
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build; a failed check ends it with a traceback and a non-zero status."""
+    return {"cases": len(run_all_checks())}
+
+
 def test_same_checks_on_the_half_operand_build():
-    outp = os.path.join(tempfile.mkdtemp(prefix="slabnorm_f16_"), "result.json")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "slabnorm_f16_worker.py"), "--out", outp]
-    child = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), capture_output=True, text=True, timeout=300)
-    assert child.returncode == 0 and os.path.exists(outp), f"rc {child.returncode}\n{child.stdout[-3000:]}\n{child.stderr[-3000:]}"
-    meta = json.load(open(outp))
+    children.spawn_f16_worker("slabnorm_f16", "tests.test_gpu_slabnorm_kernels:half_build_cases")
+    meta = children.f16_worker_result("slabnorm_f16")
     assert meta["lib"] == "liboctmae_f16.so" and meta["lp_is_f16"] is True and meta["cases"] == len(CASES)

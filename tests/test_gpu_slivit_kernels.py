@@ -13,13 +13,9 @@ they catch), no measured constant in any of them:
 Shapes: maps narrower than the halo, equal to the filter, one past the 8 x 16 tile in each direction, several tiles; channel counts
 below a wave's 64 lanes x 4, a non-power-of-two, and a tail after the 32-channel blocks; and the shapes of slivit_ref.DW_TRIP_SHAPES /
 LS_TRIP_SHAPE, where the workgroups of the weight gradient and of the layer-scale backward outnumber their cap.  The same checks run on the half-operand build
-in a child process (tests/slivit_f16_worker.py)."""
+in a child process (tests/f16_worker.py)."""
 import ctypes
-import json
 import os
-import subprocess
-import sys
-import tempfile
 
 import pytest
 import torch
@@ -29,10 +25,9 @@ pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
     from octcubem_amd import _lib, ops
+from tests import children
 from tests import slivit_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_F16 = os.path.join(ROOT, "octcubem_amd", "liboctmae_f16.so")
 DEV = "cuda"
 HW = [(1, 1), (2, 3), (3, 7), (7, 7), (8, 9), (17, 5), (33, 40)]
 CS = [8, 32, 96, 136]
@@ -309,10 +304,12 @@ def test_argument_checks_return_without_launching():
     check_argument_checks()
 
 
+def half_build_cases():
+    """What tests/f16_worker.py runs on the half-operand build; a failed check ends it with a traceback and a non-zero status."""
+    return {"cases": len(run_all_checks())}
+
+
 def test_same_checks_on_the_half_operand_build():
-    outp = os.path.join(tempfile.mkdtemp(prefix="slivit_f16_"), "result.json")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "slivit_f16_worker.py"), "--out", outp]
-    child = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, OCTMAE_LIB=LIB_F16), capture_output=True, text=True, timeout=300)
-    assert child.returncode == 0 and os.path.exists(outp), f"rc {child.returncode}\n{child.stdout[-3000:]}\n{child.stderr[-3000:]}"
-    meta = json.load(open(outp))
+    children.spawn_f16_worker("slivit_f16", "tests.test_gpu_slivit_kernels:half_build_cases")
+    meta = children.f16_worker_result("slivit_f16")
     assert meta["lib"] == "liboctmae_f16.so" and meta["lp_is_f16"] is True and meta["cases"] > 0
