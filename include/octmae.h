@@ -63,8 +63,10 @@ extern "C" {
  * 31: octmae_cam_eigen (+ octmae_cam_eigen_ws_floats), octmae_cam_accumulate: the eigen-smoothed Grad-CAM map by matrix-free power
  *     iterations and the normalise-flip-fold of test-time-augmentation smoothing (csrc/saliency.hip).
  * 32: octmae_retrieval_pair_ranks (+ octmae_retrieval_pair_ws): both directions of up to three square retrieval problems from one walk
- *     over the tiles of 19 (the six directions of the three-modality COEM validation, csrc/retrieval_pair.hip). */
-#define OCTMAE_ABI_VERSION 32
+ *     over the tiles of 19 (the six directions of the three-modality COEM validation, csrc/retrieval_pair.hip).
+ * 33: octmae_bootstrap_rank_metrics (bootstrap resamples of AUROC / average precision / AUPRC / best F1 from one sort and a weighted
+ *     prefix walk per resample, csrc/bootstrap.hip). */
+#define OCTMAE_ABI_VERSION 33
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -566,6 +568,27 @@ int octmae_rank_counts(const float* scores, long long score_stride, const uint8_
  * octmae_rank_counts.  -2, before any launch: the conditions of octmae_rank_counts, a NULL valid, valid_stride below C. */
 int octmae_rank_counts_masked(const float* scores, long long score_stride, const uint8_t* labels, long long label_stride,
                               const uint8_t* valid, long long valid_stride, int* counts, long long n, int C, void* stream);
+
+/* ---- bootstrap resamples of the ranking metrics (csrc/bootstrap.hip) ----------------------------------
+ * R resamples of AUROC, average precision, trapezoid AUPRC and best F1 from one sort: a resample gives every resampling unit (a
+ * sample, or a patient with all its samples) a multiplicity, and each metric is a function of the weighted cumulative counts along
+ * the descending score order.  The caller sorts every class column once (octcubem_amd.ops.bootstrap_rank_metrics) and passes
+ *   unit_sorted int32 [C][n]   the unit of the sample at position p of class c's descending order
+ *   flags       uint8 [C][n]   bit 0 label, bit 1 last position of a tie group (s[p] != s[p+1] under IEEE comparison, or p == n - 1),
+ *                              bit 2 valid (the sample belongs to class c's population)
+ *   mult        int32 [R][U]   how often unit u is drawn in resample r; the weight of p is valid ? mult[r][unit] : 0
+ * all contiguous.  Outputs, contiguous [R][C]: p / n_neg int64 (weighted positives / negatives), u2 int64 (twice the Mann-Whitney
+ * statistic, sum over tie groups of posw (2 (N - FP) + negw)), ap_sum f64 (sum of posw TP / ALL: average precision times P), auprc f64
+ * (the trapezoid rule over the points (TP / P, TP / ALL), one per tie-group end, from (0, 1); ALL == 0 reads as precision 1) and max_f1
+ * f64 (max of 2 p r / (p + r + 1e-8) over those points, at least 0).  A pair (r, c) with p == 0 or n_neg == 0 is undefined for the
+ * caller; with p == 0 the three floats are 0.  Deterministic: integers, and float sums folded in a fixed order.
+ * The caller guarantees: every multiplicity >= 0, and the weights of a column sum to less than 2^31 (largest cluster x largest row sum
+ * of mult); the running sums are 32-bit.  A unit id outside [0, U) weighs 0 (no read outside mult).  Same code in the two builds.
+ * -2, before any launch: a NULL pointer, n <= 0, C <= 0, R <= 0, U <= 0, n or U above 2^31 - 1, C above 65535, R above 2^24 - 1 (one
+ * workgroup of 256 threads per resample). */
+int octmae_bootstrap_rank_metrics(const int* unit_sorted, const uint8_t* flags, const int* mult, long long* p, long long* n_neg,
+                                  long long* u2, double* ap_sum, double* auprc, double* max_f1, long long n, int C, long long R,
+                                  long long U, void* stream);
 
 /* ---- retrieval ranks of the COEM validation (csrc/retrieval.hip) -------------------------------------
  * retinal-COEM/src/training/train_retclip.py:409-469 ranks every sample's partner among all candidates by sorting the rows of the

@@ -40,6 +40,7 @@ SIGNATURES = {
     "octmae_image_augment": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "octmae_rank_counts": [_vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
     "octmae_rank_counts_masked": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
+    "octmae_bootstrap_rank_metrics": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _vp],
     "octmae_retrieval_ranks": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _vp],
     "octmae_retrieval_topk_ws": [_ll, _ll, _i],
     "octmae_retrieval_topk": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],

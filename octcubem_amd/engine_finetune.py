@@ -139,6 +139,31 @@ def _write_int_matrix(path: str, m):
         csv.writer(f).writerows([[int(v) for v in r] for r in np.asarray(m)])
 
 
+CI_HEADER = ["epoch", "metric", "class", "point", "low", "high", "n_defined", "resamples", "alpha", "seed", "level"]
+
+
+def _bootstrap_report(task, epoch, mode, scores, labels, names, args):
+    """The opt-in bootstrap of ``evaluate_report`` (``args.bootstrap`` = R > 0): percentile intervals of roc_auc / AP / auprc / max_f1
+    of the scores the report has just ranked, appended to ``metrics_ci_<mode>.csv`` (CI_HEADER): per metric one row for ``macro`` and
+    one per class, named through ``names``.  ``args.bootstrap_seed`` (0), ``args.bootstrap_alpha`` (0.05), ``args.bootstrap_groups``
+    (None; one id per sample in the loader's order: patients are drawn instead of samples, ``level`` = group)."""
+    R = int(args.bootstrap)
+    seed, alpha = int(getattr(args, "bootstrap_seed", 0) or 0), float(getattr(args, "bootstrap_alpha", 0.05) or 0.05)
+    groups = getattr(args, "bootstrap_groups", None)
+    res = metrics.bootstrap_rank_metrics(scores, labels, resamples=R, seed=seed, alpha=alpha, groups=groups)
+    with open(os.path.join(task, f"metrics_ci_{mode}.csv"), mode="a", newline="", encoding="utf8") as f:
+        w = csv.writer(f)
+        if f.tell() == 0:
+            w.writerow(CI_HEADER)
+        tail = [res["resamples"], alpha, seed, res["level"]]
+        for key in metrics.RANK_KEYS:
+            m = res["macro"][key]
+            w.writerow([epoch, key, "macro", float(m["point"]), float(m["low"]), float(m["high"]), int(m["n_defined"])] + tail)
+            for i, name in enumerate(names):
+                c = res[key]
+                w.writerow([epoch, key, name, float(c["point"][i]), float(c["low"][i]), float(c["high"][i]), int(c["n_defined"][i])] + tail)
+
+
 @torch.no_grad()
 def evaluate_report(data_loader, model, device, task, epoch, mode, num_class, criterion=torch.nn.CrossEntropyLoss(),
                     task_mode="binary_cls", disease_list=None, return_bal_acc=False, args=None):
@@ -161,7 +186,12 @@ def evaluate_report(data_loader, model, device, task, epoch, mode, num_class, cr
     per step, one synchronisation at the end.  The metrics cover what THIS rank's loader yields, as in the reference.
     ``regression`` and ``multi_task*`` raise NotImplementedError here: ``evaluate_task_report`` below serves them and hands the three
     modes of this function on unchanged, so a driver binds that one as ``evaluate``.  ``args.frame_inference_all`` /
-    ``return_embeddings`` / ``variable_joint`` must be unset or falsy."""
+    ``return_embeddings`` / ``variable_joint`` must be unset or falsy.
+
+    Opt-in: ``args.bootstrap`` = R > 0 appends bootstrap percentile intervals of roc_auc / AP / auprc / max_f1 of the same scores
+    (softmax one-vs-rest against the one-hot targets, or sigmoid against the multi-label targets) to ``metrics_ci_<mode>.csv``
+    (``_bootstrap_report``; ``args.bootstrap_seed``, ``args.bootstrap_alpha``, ``args.bootstrap_groups``).  Absent, None or 0: nothing
+    changes, neither a file nor the return value; set, the return value is still the one above."""
     if task_mode not in _REPORT_MODES:
         if task_mode == "regression" or str(task_mode).startswith("multi_task"):
             raise NotImplementedError(f"evaluate_report: task_mode {task_mode!r} is not built (built: {', '.join(_REPORT_MODES)})")
@@ -217,6 +247,8 @@ def evaluate_report(data_loader, model, device, task, epoch, mode, num_class, cr
         print("Metrics - Acc: {:.4f} AUC-roc: {:.4f}, AP: {:4f}, AUC-pr: {:.4f} F1-score: {:.4f}, Max F1: {:.4f}, Balanced Acc: {:.4f}, "
               "Kappa: {:.4f}, MCC: {:.4f}".format(macro["accuracy"], macro["roc_auc"], macro["AP"], macro["auprc"], macro["f1"],
                                                   macro["max_f1"], macro["balanced_acc"], macro["kappa"], macro["mcc"]))
+        if getattr(args, "bootstrap", None):
+            _bootstrap_report(task, epoch, mode, scores, targets != 0, [disease_list.get(i, str(i)) for i in range(num_class)], args)
         if return_bal_acc:
             return stats, macro["roc_auc"], (macro["auprc"], macro["balanced_acc"])
         return stats, macro["roc_auc"], macro["auprc"]
@@ -237,6 +269,9 @@ def evaluate_report(data_loader, model, device, task, epoch, mode, num_class, cr
                 [acc, balanced_acc, sensitivity, specificity, precision, auc_roc, auc_pr, F1, mcc, stats["loss"]])
     if mode.startswith("test") and not getattr(args, "not_save_figs", False):
         _write_int_matrix(os.path.join(task, f"confusion_matrix_{mode}_epoch_{epoch}.csv"), confusion)
+    if getattr(args, "bootstrap", None):
+        named = {} if disease_list is None else disease_list if isinstance(disease_list, dict) else dict(enumerate(disease_list))
+        _bootstrap_report(task, epoch, mode, scores, onehot, [named.get(i, str(i)) for i in range(num_class)], args)
     if return_bal_acc:
         return stats, auc_roc, (auc_pr, balanced_acc)
     return stats, auc_roc, auc_pr
@@ -251,7 +286,8 @@ def evaluate_task_report(data_loader, model, device, task, epoch, mode, num_clas
                          task_mode="binary_cls", disease_list=None, return_bal_acc=False, args=None):
     """The reference's ``evaluate`` (engine_finetune.py:498-813) for all five task modes, the function a driver binds as ``evaluate``.
     ``binary_cls``, ``multi_cls`` and ``multi_label`` go to ``evaluate_report`` unchanged; an unknown mode raises ValueError;
-    ``args.frame_inference_all`` / ``return_embeddings`` / ``variable_joint`` must be unset or falsy.
+    ``args.frame_inference_all`` / ``return_embeddings`` / ``variable_joint`` must be unset or falsy.  ``args.bootstrap`` (the
+    bootstrap intervals of ``evaluate_report``) is not wired for ``multi_task*`` and ``regression``: set, it raises NotImplementedError.
 
     ``multi_task*`` (targets [n, T + 1], column 0 the shared "normal" label; ``num_class`` model outputs: 2T for
     'multi_task_default', T + 1 otherwise): returns ``({"loss", "acc1"}, macro roc_auc, macro auprc)`` of
@@ -279,6 +315,9 @@ def evaluate_task_report(data_loader, model, device, task, epoch, mode, num_clas
         raise ValueError(f"evaluate_task_report: unknown task_mode {task_mode!r}")
     for name in _UNBUILT_ARGS:
         assert not getattr(args, name, False), f"evaluate_task_report: args.{name} is not built"
+    if getattr(args, "bootstrap", None):
+        raise NotImplementedError(f"evaluate_task_report: args.bootstrap is not built for task_mode {task_mode!r} (built: "
+                                  f"{', '.join(_REPORT_MODES)})")
     os.makedirs(task, exist_ok=True)
     device = torch.device(device)
     whole_set_loss = multi_task and isinstance(criterion, losses.WeightedLabelSmoothingCrossEntropy)

@@ -14,7 +14,9 @@ For one class with P positives and N negatives, and per sample the counts {gt_al
                             smaller F1, so neither number depends on the version.)
 The reference's own ``1e-8`` deltas stand exactly where it has them.  Provenance: a RESTATEMENT of the reference's formulas, call-compatible
 with its functions; nothing here is on a hot path.  ``misc_measures_multi_task`` (:86-242) ranks every task over its own population
-from the masked counts of ``ops.rank_counts_masked``; ``regression_measures`` restates the scipy / scikit-learn values of :642-660."""
+from the masked counts of ``ops.rank_counts_masked``; ``regression_measures`` restates the scipy / scikit-learn values of :642-660.
+``bootstrap_rank_metrics`` / ``bootstrap_compare`` (no counterpart in the reference) put percentile intervals on the four ranking
+metrics and compare two score sets on the same resamples, from the weighted-rank kernel of ``ops.bootstrap_rank_metrics``."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Optional
@@ -278,6 +280,180 @@ def misc_measures_multi_task(y_true, y_pred, threshold: float = 0.5, multi_task_
     macro = {"micro_AP": float(micro["AP"][0])}
     macro.update({k: float(np.mean(cw[k])) for k in _TASK_KEYS})
     return {"macro": macro, "classwise": {k: [float(x) for x in cw[k]] for k in _TASK_KEYS}}
+
+
+# ---- bootstrap intervals of the ranking metrics.  A resample draws U resampling units with replacement (the samples themselves, or
+# with ``groups`` the patients, each with all its samples: a cluster bootstrap) and is held as one int32 multiplicity per unit; the
+# kernel of ops.bootstrap_rank_metrics (csrc/bootstrap.hip) sorts once and walks every resample over the sorted columns.  The host
+# divides, drops the resamples in which a class has no positive or no negative (counted in ``n_defined``, not redrawn) and reads
+# percentile intervals off the rest.  ``kernel=`` replaces the device op by any function of its signature (tests/bootstrap_ref.py:
+# numpy), ``rank_counts=`` the counter behind the point estimates, as elsewhere in this file.
+RANK_KEYS = ("roc_auc", "AP", "auprc", "max_f1")
+
+
+def bootstrap_multiplicities(R: int, U: int, seed: int, device) -> torch.Tensor:
+    """int32 [R, U]: row r counts how often each of U units is drawn when U units are drawn with replacement.  The draws are
+    ``torch.randint(U, (R, U))`` from a ``torch.Generator`` of ``device`` seeded with ``seed``, counted by an integer ``scatter_add_``
+    (integer atomics: the same tensor on every run).  The stream is torch's for that device: the CPU and the GPU differ, and numpy's
+    resamples for the same seed differ from both."""
+    if R < 1 or U < 1:
+        raise ValueError(f"bootstrap_multiplicities: needs R >= 1 and U >= 1, got {R} and {U}")
+    device = torch.device(device)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    draws = torch.randint(U, (R, U), generator=gen, device=device)
+    return torch.zeros((R, U), dtype=torch.int32, device=device).scatter_add_(1, draws, torch.ones((R, U), dtype=torch.int32, device=device))
+
+
+def _device_bootstrap(scores, labels, mult, unit=None, valid=None):
+    if not all(isinstance(t, torch.Tensor) for t in (scores, labels, mult)):
+        raise TypeError("the resamples come from the HIP kernel, which takes GPU tensors (there is no CPU path): pass tensors on the "
+                        "device, or a kernel function")
+    from . import ops
+    return ops.bootstrap_rank_metrics(scores, labels, mult, unit, valid)
+
+
+def _dense_ids(groups):
+    """ids of any hashable type -> (int64 ids in order of first occurrence [n], how many distinct ones), as coem._label_ids."""
+    if isinstance(groups, (torch.Tensor, np.ndarray)):
+        groups = groups.tolist()
+    ids: dict = {}
+    out = [ids.setdefault(g, len(ids)) for g in groups]
+    return np.asarray(out, dtype=np.int64), len(ids)
+
+
+def _bootstrap_problem(scores, labels, valid, resamples, seed, groups, mult):
+    """The operands every score set of one call shares: ``(scores float32, labels uint8, valid uint8 or None, unit or None, mult)``,
+    torch tensors where ``scores`` lives when it is a tensor and numpy arrays otherwise."""
+    as_tensor = isinstance(scores, torch.Tensor)
+    if as_tensor:
+        s = scores.detach().float()
+        lab = (torch.as_tensor(labels).detach().to(s.device) != 0).to(torch.uint8)
+        val = None if valid is None else (torch.as_tensor(valid).detach().to(s.device) != 0).to(torch.uint8)
+    else:
+        s = np.ascontiguousarray(scores, dtype=np.float32)
+        lab = (_host(labels) != 0).astype(np.uint8)
+        val = None if valid is None else (_host(valid) != 0).astype(np.uint8)
+    if s.ndim != 2 or tuple(lab.shape) != tuple(s.shape) or (val is not None and tuple(val.shape) != tuple(s.shape)):
+        raise ValueError(f"bootstrap_rank_metrics: expected scores, labels and valid [n, C], got {tuple(s.shape)}, {tuple(lab.shape)}"
+                         + ("" if val is None else f", {tuple(val.shape)}"))
+    n = s.shape[0]
+    unit, U = None, n
+    if groups is not None:
+        ids, U = _dense_ids(groups)
+        if ids.shape[0] != n:
+            raise ValueError(f"bootstrap_rank_metrics: {n} samples but {ids.shape[0]} group ids")
+        unit = torch.from_numpy(ids).to(s.device) if as_tensor else ids
+    if mult is None:
+        mult = bootstrap_multiplicities(int(resamples), U, seed, s.device if as_tensor else "cpu")
+        mult = mult if as_tensor else mult.numpy()
+    elif tuple(mult.shape)[1:] != (U,) or len(mult.shape) != 2 or mult.shape[0] < 1:
+        raise ValueError(f"bootstrap_rank_metrics: expected mult [R, {U}], got {tuple(mult.shape)}")
+    return s, lab, val, unit, mult
+
+
+def _bootstrap_samples(s, lab, val, unit, mult, kernel, rank_counts):
+    """``(point {key: [C]}, samples {key: float64 [R, C], NaN where P == 0 or N == 0})`` of one score set."""
+    if rank_counts is None:
+        counts = _device_rank_counts_masked(s, lab, val)
+    else:
+        counts = rank_counts(s, lab) if val is None else rank_counts(s, lab, val)
+    point = binary_rank_metrics(counts, lab, valid=val)
+    raw = {k: _host(v) for k, v in (kernel or _device_bootstrap)(s, lab, mult, unit, val).items()}
+    P, N = raw["P"].astype(np.int64), raw["N"].astype(np.int64)
+    defined = (P > 0) & (N > 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        samples = {"roc_auc": raw["U2"].astype(np.float64) / (2.0 * P * N), "AP": raw["ap_sum"].astype(np.float64) / P,
+                   "auprc": raw["auprc"].astype(np.float64), "max_f1": raw["max_f1"].astype(np.float64)}
+    return point, {k: np.where(defined, v, np.nan) for k, v in samples.items()}
+
+
+def _macro_samples(samples: np.ndarray) -> np.ndarray:
+    """[R, C] -> [R]: the mean over the classes, NaN unless every class is defined in the resample."""
+    return samples.mean(axis=1)           # a NaN propagates through the mean
+
+
+def _interval(samples: np.ndarray, alpha: float, what: str):
+    """Percentile interval of the columns of ``samples`` [R, K] over their defined (non-NaN) rows: ``(low [K], high [K], n_defined
+    [K])``; ValueError for a column that is never defined."""
+    K = samples.shape[1]
+    low, high, cnt = np.empty(K), np.empty(K), np.empty(K, dtype=np.int64)
+    for k in range(K):
+        col = samples[:, k]
+        col = col[~np.isnan(col)]
+        cnt[k] = col.size
+        if col.size == 0:
+            raise ValueError(f"{what} {k}: no resample holds both a positive and a negative: the interval is not defined")
+        low[k], high[k] = np.quantile(col, alpha / 2), np.quantile(col, 1 - alpha / 2)
+    return low, high, cnt
+
+
+def bootstrap_rank_metrics(scores, labels, *, resamples: int = 1000, seed: int = 0, alpha: float = 0.05, groups=None, valid=None,
+                           mult=None, kernel: Optional[Callable] = None, rank_counts: Optional[Callable] = None) -> dict:
+    """Bootstrap percentile intervals of the four ranking metrics of ``binary_rank_metrics``: ``scores`` [n, C], ``labels`` [n, C]
+    (!= 0 = positive), ``valid`` [n, C] or None (!= 0 = the sample belongs to the class's population).
+
+    Returns, for each of ``roc_auc``, ``AP``, ``auprc``, ``max_f1``, a dict of ``point`` [C] (``binary_rank_metrics`` on the rank counts,
+    unchanged), ``samples`` float64 [R, C] (NaN where the resample has no positive or no negative of the class), ``low`` / ``high`` [C]
+    (``np.quantile`` at ``alpha / 2`` and ``1 - alpha / 2`` over the class's defined resamples, linear interpolation) and ``n_defined``
+    [C]; under ``macro`` the same four keys for the mean over the classes (a float ``point``, ``samples`` [R], a resample counting only
+    where every class is defined); and ``resamples`` (R) and ``level`` ("sample" or "group").  ValueError for a class without any
+    defined resample.
+
+    ``groups``: one hashable id per sample (a patient): units are drawn, and all their samples come with them.  ``mult`` int32 [R, U]
+    overrides the draw of ``bootstrap_multiplicities(resamples, U, seed, device)``.  By default the resamples come from
+    ops.bootstrap_rank_metrics and the point estimates from ops.rank_counts[_masked], for which the inputs must be GPU tensors (there
+    is no CPU path); ``kernel`` / ``rank_counts`` replace them by functions of the same signatures."""
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"bootstrap_rank_metrics: alpha must lie in (0, 1), got {alpha}")
+    s, lab, val, unit, mult = _bootstrap_problem(scores, labels, valid, resamples, seed, groups, mult)
+    point, samples = _bootstrap_samples(s, lab, val, unit, mult, kernel, rank_counts)
+    out: dict = {"macro": {}, "resamples": int(mult.shape[0]), "level": "sample" if groups is None else "group"}
+    for key in RANK_KEYS:
+        low, high, cnt = _interval(samples[key], alpha, "class")
+        out[key] = {"point": point[key], "samples": samples[key], "low": low, "high": high, "n_defined": cnt}
+        macro = _macro_samples(samples[key])
+        low, high, cnt = _interval(macro[:, None], alpha, "macro over the classes: column")
+        out["macro"][key] = {"point": float(np.mean(point[key])), "samples": macro, "low": float(low[0]), "high": float(high[0]),
+                             "n_defined": int(cnt[0])}
+    return out
+
+
+def _delta_summary(delta: np.ndarray, alpha: float, what: str):
+    """[R, K] differences (NaN where either side is undefined) -> (low [K], high [K], p [K], n_defined [K]): the percentile interval
+    and the two-sided p = 2 min(share(delta <= 0), share(delta >= 0)) clipped to [1 / n_defined, 1]."""
+    low, high, cnt = _interval(delta, alpha, what)
+    p = np.empty(delta.shape[1])
+    for k in range(delta.shape[1]):
+        col = delta[:, k]
+        col = col[~np.isnan(col)]
+        p[k] = min(1.0, max(1.0 / col.size, 2.0 * min(np.mean(col <= 0), np.mean(col >= 0))))
+    return low, high, p, cnt
+
+
+def bootstrap_compare(scores_a, scores_b, labels, *, resamples: int = 1000, seed: int = 0, alpha: float = 0.05, groups=None, valid=None,
+                      mult=None, kernel: Optional[Callable] = None, rank_counts: Optional[Callable] = None) -> dict:
+    """Paired comparison of two score sets on one test set: both are walked with the SAME multiplicities, and per metric and class
+    (and under ``macro`` for the mean over the classes) the result holds ``delta_point`` (a - b on the full set), ``delta_low`` /
+    ``delta_high`` (the percentile interval of the resampled differences), ``p`` (two-sided: 2 min(share(delta <= 0), share(delta >=
+    0)), clipped to [1 / n_defined, 1]) and ``n_defined`` (resamples defined for both).  Keywords as ``bootstrap_rank_metrics``."""
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"bootstrap_compare: alpha must lie in (0, 1), got {alpha}")
+    sa, lab, val, unit, mult = _bootstrap_problem(scores_a, labels, valid, resamples, seed, groups, mult)
+    sb = _bootstrap_problem(scores_b, labels, valid, resamples, seed, groups, mult)[0]
+    if tuple(sa.shape) != tuple(sb.shape):
+        raise ValueError(f"bootstrap_compare: the two score sets differ in shape: {tuple(sa.shape)} and {tuple(sb.shape)}")
+    pa, xa = _bootstrap_samples(sa, lab, val, unit, mult, kernel, rank_counts)
+    pb, xb = _bootstrap_samples(sb, lab, val, unit, mult, kernel, rank_counts)
+    out: dict = {"macro": {}, "resamples": int(mult.shape[0]), "level": "sample" if groups is None else "group"}
+    for key in RANK_KEYS:
+        low, high, p, cnt = _delta_summary(xa[key] - xb[key], alpha, "class")
+        out[key] = {"delta_point": pa[key] - pb[key], "delta_low": low, "delta_high": high, "p": p, "n_defined": cnt}
+        macro = _macro_samples(xa[key]) - _macro_samples(xb[key])
+        low, high, p, cnt = _delta_summary(macro[:, None], alpha, "macro over the classes: column")
+        out["macro"][key] = {"delta_point": float(np.mean(pa[key]) - np.mean(pb[key])), "delta_low": float(low[0]),
+                             "delta_high": float(high[0]), "p": float(p[0]), "n_defined": int(cnt[0])}
+    return out
 
 
 def regression_measures(pred, target) -> Dict[str, float]:

@@ -1148,6 +1148,95 @@ def rank_counts_masked(scores: torch.Tensor, labels: torch.Tensor, valid: torch.
     return _rank_counts("rank_counts_masked", scores, labels, valid)
 
 
+def bootstrap_rank_metrics(scores: torch.Tensor, labels: torch.Tensor, mult: torch.Tensor, unit: Optional[torch.Tensor] = None,
+                           valid: Optional[torch.Tensor] = None) -> dict:
+    """The ranking metrics of R bootstrap resamples of one evaluation set, from one sort (csrc/bootstrap.hip).  ``scores`` float32
+    [n, C], ``labels`` and ``valid`` bool or uint8 [n, C] (column slices of wider buffers pass, as in ``rank_counts``); ``mult`` int32
+    [R, U]: how often resampling unit u is drawn in resample r; ``unit`` int32 or int64 [n]: the unit of every sample (None: the sample
+    itself, ``U == n``).  Returns device tensors ``P``, ``N``, ``U2`` (int64 [R, C]: weighted positives, negatives, twice the
+    Mann-Whitney statistic) and ``ap_sum``, ``auprc``, ``max_f1`` (float64 [R, C]: average precision times P, the trapezoid area under
+    the precision-recall points, the reference's best F1); ``octcubem_amd.metrics.bootstrap_rank_metrics`` divides and marks the pairs
+    with ``P == 0`` or ``N == 0`` undefined.
+
+    Every column is sorted once (``torch.sort``, descending, stable) and the unit ids and flag bytes of the kernel are built with ATen
+    ops; the kernel then walks every resample over them.  ValueError before the launch, from four device reductions read back
+    together: a unit id outside [0, U), a negative multiplicity, largest cluster x largest row sum of ``mult`` >= 2^31 (the running sums
+    are 32-bit), a NaN score at a valid position.  +-inf are ordinary scores, -0.0 ties with 0.0.  No autograd, no CPU path."""
+    name = "bootstrap_rank_metrics"
+    flags = (("labels", labels),) if valid is None else (("labels", labels), ("valid", valid))
+    others = (("mult", mult),) if unit is None else (("mult", mult), ("unit", unit))
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (scores,) + tuple(t for _, t in flags + others)):
+        raise RuntimeError(f"{name}: expected GPU tensors (the HIP path has no CPU fallback)")
+    if scores.dtype != F32:
+        raise TypeError(f"{name}: scores must be float32, got {scores.dtype}")
+    for what, t in flags:
+        if t.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{name}: {what} must be bool or uint8, got {t.dtype}")
+    if mult.dtype != torch.int32:
+        raise TypeError(f"{name}: mult must be int32, got {mult.dtype}")
+    if unit is not None and unit.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: unit must be int32 or int64, got {unit.dtype}")
+    if scores.dim() != 2 or any(t.shape != scores.shape for _, t in flags) or any(t.device != scores.device for _, t in flags + others):
+        raise ValueError(f"{name}: expected scores and {' and '.join(w for w, _ in flags)} [n, C] on one device, got "
+                         f"{tuple(scores.shape)} and {' and '.join(str(tuple(t.shape)) for _, t in flags)}")
+    n, C = scores.shape
+    if n < 1 or C < 1:
+        raise ValueError(f"{name}: empty input {tuple(scores.shape)}")
+    if mult.dim() != 2 or mult.shape[0] < 1 or mult.shape[1] < 1:
+        raise ValueError(f"{name}: expected mult [R, U], got {tuple(mult.shape)}")
+    R, U = mult.shape
+    if unit is None and U != n:
+        raise ValueError(f"{name}: without unit every sample is its own unit: mult must be [R, {n}], got {tuple(mult.shape)}")
+    if unit is not None and unit.shape != (n,):
+        raise ValueError(f"{name}: expected unit [{n}], got {tuple(unit.shape)}")
+    scores = scores.detach()
+    flags = tuple((what, t.detach().view(torch.uint8) if t.dtype == torch.bool else t.detach()) for what, t in flags)
+    for what, t in (("scores", scores),) + flags:
+        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
+            raise ValueError(f"{name}: {what} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
+    mult = mult.detach().contiguous()
+    lab = flags[0][1] != 0
+    val = None if valid is None else flags[1][1] != 0
+    nan = torch.isnan(scores)
+    if val is not None:
+        nan = nan & val
+    row_sum = mult.sum(dim=1, dtype=torch.int64).max()
+    if unit is None:
+        bad_unit, cluster = torch.zeros((), dtype=torch.bool, device=scores.device), torch.ones((), dtype=torch.int64, device=scores.device)
+    else:
+        unit = unit.detach().long()
+        bad_unit = ((unit < 0) | (unit >= U)).any()
+        cluster = torch.bincount(unit.clamp(0, U - 1), minlength=U).max()
+    # the four checks as one readback: [bad unit, negative multiplicity, NaN, largest cluster, largest row sum]
+    bad_u, neg, has_nan, cl, rs = torch.stack([bad_unit.long(), (mult < 0).any().long(), nan.any().long(), cluster, row_sum]).tolist()
+    if bad_u:
+        raise ValueError(f"{name}: unit ids must lie in [0, {U})")
+    if neg:
+        raise ValueError(f"{name}: mult holds a negative multiplicity")
+    if has_nan:
+        raise ValueError(f"{name}: scores contain NaN" + ("" if valid is None else " at a valid position"))
+    if cl * rs >= 2 ** 31:
+        raise ValueError(f"{name}: a resample can weigh {cl} x {rs} >= 2^31 (largest cluster x largest row sum of mult): the running "
+                         "sums of the kernel are 32-bit")
+    vals, order = torch.sort(scores, dim=0, descending=True, stable=True)
+    end = torch.ones((n, C), dtype=torch.bool, device=scores.device)
+    if n > 1:
+        end[:-1] = vals[:-1] != vals[1:]
+    fl = torch.gather(lab, 0, order).to(torch.uint8) | (end.to(torch.uint8) << 1)
+    fl |= 4 if val is None else torch.gather(val, 0, order).to(torch.uint8) << 2
+    flag_bytes = fl.t().contiguous()
+    unit_sorted = (order if unit is None else unit[order]).to(torch.int32).t().contiguous()
+    dev = scores.device
+    out = {k: torch.empty((R, C), dtype=torch.int64, device=dev) for k in ("P", "N", "U2")}
+    out.update({k: torch.empty((R, C), dtype=torch.float64, device=dev) for k in ("ap_sum", "auprc", "max_f1")})
+    # algorithmic HBM bytes: the unit ids and flag bytes once (every resample re-reads them from the caches), mult once, the outputs
+    _launch(name, 0.0, float(C * n * 5 + R * U * 4 + R * C * 48),
+            lambda: call("octmae_bootstrap_rank_metrics", unit_sorted.data_ptr(), flag_bytes.data_ptr(), mult.data_ptr(),
+                         out["P"].data_ptr(), out["N"].data_ptr(), out["U2"].data_ptr(), out["ap_sum"].data_ptr(),
+                         out["auprc"].data_ptr(), out["max_f1"].data_ptr(), n, C, R, U, _stream()))
+    return out
+
+
 def _pair_shapes(name: str, a, b, others, fits: Optional[str] = None, f32_others: bool = False):
     """The operand contract of the ops on the f32 similarity tile (csrc/simtile.hpp): ``a`` float32 [n, d] and ``b`` float32 [m, d]
     on one GPU, none empty, row counts in int32.  ``others``: (tensor or None, name) pairs that must be GPU tensors too, and float32
