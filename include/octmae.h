@@ -65,8 +65,10 @@ extern "C" {
  * 32: octmae_retrieval_pair_ranks (+ octmae_retrieval_pair_ws): both directions of up to three square retrieval problems from one walk
  *     over the tiles of 19 (the six directions of the three-modality COEM validation, csrc/retrieval_pair.hip).
  * 33: octmae_bootstrap_rank_metrics (bootstrap resamples of AUROC / average precision / AUPRC / best F1 from one sort and a weighted
- *     prefix walk per resample, csrc/bootstrap.hip). */
-#define OCTMAE_ABI_VERSION 33
+ *     prefix walk per resample, csrc/bootstrap.hip).
+ * 34: octmae_unit_moments, octmae_bootstrap_moments (+ octmae_bootstrap_moments_ws): bootstrap resamples of the regression metrics as
+ *     one int32 x f64 matrix product on v_mfma_f64_16x16x4_f64, in a fixed summation order (csrc/bootmoments.hip). */
+#define OCTMAE_ABI_VERSION 34
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -589,6 +591,37 @@ int octmae_rank_counts_masked(const float* scores, long long score_stride, const
 int octmae_bootstrap_rank_metrics(const int* unit_sorted, const uint8_t* flags, const int* mult, long long* p, long long* n_neg,
                                   long long* u2, double* ap_sum, double* auprc, double* max_f1, long long n, int C, long long R,
                                   long long U, void* stream);
+
+/* ---- bootstrap resamples of the regression metrics (csrc/bootmoments.hip) ------------------------------
+ * Pearson r, R^2, explained variance, MSE and MAE of one resample are functions of eight weighted sums over the samples, and a
+ * resample is a row of multiplicities: all R resamples are the product mult [R][U] x F [U][Cpad8], Cpad8 = 8 C rounded up to a
+ * multiple of 16.  The caller (octcubem_amd.ops.bootstrap_moments) finishes the sums in float64 on the host.
+ *
+ * octmae_unit_moments fills F f64 [U][Cpad8], contiguous.  With a = (double)x - centre[0][c], b = (double)y - centre[1][c] and
+ * e = (double)y - (double)x, entry 8 c + k of row u is, over the valid samples of unit u:
+ *   k = 0 count, 1 sum a, 2 sum b, 3 sum a^2, 4 sum b^2, 5 sum a b, 6 sum e^2, 7 sum |e|;
+ * columns 8 C .. Cpad8 - 1 are written as zero, a unit without samples gives zeros (every byte of F is written).
+ *   pred, target  f32 [n][C], unit column stride, rows pred_stride / target_stride ELEMENTS apart (>= C)
+ *   valid         uint8 [n][C] (!= 0: the sample counts for the column), rows valid_stride bytes apart (>= C), or NULL: all valid
+ *   centre        f64 [2][C]: a shift only, any finite value is mathematically correct
+ *   order         int32 [n]: the sample indices sorted stably by unit;  start int32 [U + 1]: unit u owns order[start[u] .. start[u+1])
+ * Each (unit, column) is summed sequentially in ascending position, i.e. ascending sample index.  An order[] entry outside [0, n) is
+ * skipped and start[] is clamped to [0, n]: nothing past an operand's edge is read.
+ *
+ * octmae_bootstrap_moments computes D[r][j] = sum_u (double)mult[r][u] * F[u][j], f64 [R][Cpad8] contiguous, mult int32 [R][U]
+ * contiguous, on v_mfma_f64_16x16x4_f64.  Units are walked in ascending steps of 4; rows past R, units past U and columns at or past
+ * 8 C enter as literal zeros (selected, not multiplied: F's pad columns are not read).  The units are split in parts of 1024, a
+ * function of U alone; with more than one part each part is stored to ws (octmae_bootstrap_moments_ws(R, U, C) doubles; 0 for one
+ * part, then ws may be NULL) and the parts are added in ascending order by a second launch: no floating-point atomic, the same bits
+ * on every run, and row r does not depend on R or on the other rows.  The caller keeps F finite (0 * NaN is NaN).
+ * Same code in the two builds.  -2, before any launch: a NULL pointer (valid excepted; ws excepted for one part), n, C, R or U <= 0,
+ * n above 2^31 - 1, C above 4096, R above 2^20, U above 2^24, R * Cpad8 >= 2^32 (the product and its _ws query: one thread of the
+ * second launch per element of D), a stride below C; the _ws query returns -2 for the same sizes.  It counts DOUBLES, not bytes. */
+int octmae_unit_moments(const float* pred, long long pred_stride, const float* target, long long target_stride, const uint8_t* valid,
+                        long long valid_stride, const double* centre, const int* order, const int* start, double* F, long long n, int C,
+                        long long U, void* stream);
+long long int octmae_bootstrap_moments_ws(long long R, long long U, int C);
+int octmae_bootstrap_moments(const int* mult, const double* F, double* D, double* ws, long long R, long long U, int C, void* stream);
 
 /* ---- retrieval ranks of the COEM validation (csrc/retrieval.hip) -------------------------------------
  * retinal-COEM/src/training/train_retclip.py:409-469 ranks every sample's partner among all candidates by sorting the rows of the

@@ -41,6 +41,9 @@ SIGNATURES = {
     "octmae_rank_counts": [_vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
     "octmae_rank_counts_masked": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
     "octmae_bootstrap_rank_metrics": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _vp],
+    "octmae_unit_moments": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _i, _ll, _vp],
+    "octmae_bootstrap_moments_ws": [_ll, _ll, _i],
+    "octmae_bootstrap_moments": [_vp, _vp, _vp, _vp, _ll, _ll, _i, _vp],
     "octmae_retrieval_ranks": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _vp],
     "octmae_retrieval_topk_ws": [_ll, _ll, _i],
     "octmae_retrieval_topk": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],
@@ -125,8 +128,9 @@ SIGNATURES = {
     "octmae_probe_trread": [_vp, _vp, _vp],
 }
 
-# ... except a query whose value is a byte count (long long in the header)
-RESTYPES = {"octmae_retrieval_topk_ws": _ll, "octmae_retrieval_pair_ws": _ll}
+# ... except a workspace query whose value is long long in the header: a byte count for the two retrieval queries, a count of
+# DOUBLES for octmae_bootstrap_moments_ws
+RESTYPES = {"octmae_retrieval_topk_ws": _ll, "octmae_retrieval_pair_ws": _ll, "octmae_bootstrap_moments_ws": _ll}
 
 _lib = None
 _on_load = []       # callbacks run once, right after the library has been loaded and bound (ops: operand-type check)

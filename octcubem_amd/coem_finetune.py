@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import coem
-from .metrics import regression_measures
+from .metrics import bootstrap_regression_measures, regression_measures
 
 CLS_TYPES = ("oct3d_paired_faf_cls", "oct3d_paired_ir_cls", "oct3d_paired_faf_ir_cls")
 METRIC_KEYS = ("pearsonr", "r2", "mse", "mae", "PearsonR", "R2")
@@ -68,6 +68,30 @@ def column_metrics(logits, labels) -> dict:
                 raise
             r, mse, mae = float("nan"), float(np.mean(d * d)), float(np.mean(np.abs(d)))
         out.update({f"pearsonr_{j}": r, f"r2_{j}": r * r, f"mse_{j}": mse, f"mae_{j}": mae, f"PearsonR_{j}": r, f"R2_{j}": r * r})
+    return out
+
+
+def bootstrap_column_metrics(logits, labels, point: dict, args) -> dict:
+    """The opt-in bootstrap of ``evaluate`` (``args.bootstrap`` = R > 0): for every target column j the percentile bounds
+    ``pearsonr_j_low`` / ``_high``, ``r2_j_low`` / ``_high`` (of r squared, which is what ``r2_j`` is here), ``mse_j_low`` / ``_high``,
+    ``mae_j_low`` / ``_high`` and ``bootstrap_n_defined_j`` (the resamples with a defined correlation), from
+    ``metrics.bootstrap_regression_measures`` on the same normalised ``logits`` and ``labels`` [N, C] as the point values ``point`` of
+    ``column_metrics``.  ``args.bootstrap_seed`` (0), ``args.bootstrap_alpha`` (0.05), ``args.bootstrap_groups`` (None; one id per
+    sample in the loader's order: patients are drawn instead of samples).  A column whose point correlation is NaN (constant
+    predictions or targets) gets NaN bounds and ``bootstrap_n_defined_j`` 0."""
+    R = int(args.bootstrap)
+    seed, alpha = int(getattr(args, "bootstrap_seed", 0) or 0), float(getattr(args, "bootstrap_alpha", 0.05) or 0.05)
+    groups = getattr(args, "bootstrap_groups", None)
+    C = logits.shape[1]
+    good = [j for j in range(C) if not math.isnan(point[f"pearsonr_{j}"])]
+    res = bootstrap_regression_measures(logits[:, good], labels[:, good], resamples=R, seed=seed, alpha=alpha, groups=groups) if good else None
+    out = {}
+    for j in range(C):
+        k = good.index(j) if j in good else None
+        for name, key in (("pearsonr", "pearsonr"), ("r2", "R2"), ("mse", "mse"), ("mae", "mae")):
+            out[f"{name}_{j}_low"] = float("nan") if k is None else float(res[key]["low"][k])
+            out[f"{name}_{j}_high"] = float("nan") if k is None else float(res[key]["high"][k])
+        out[f"bootstrap_n_defined_{j}"] = 0 if k is None else int(res["pearsonr"]["n_defined"][k])
     return out
 
 
@@ -211,7 +235,8 @@ def evaluate(model, data, epoch, args, tb_writer=None, setting="val", dinfo_idx=
     """The regression branch of the reference's ``evaluate``: on the main process, when ``args.val_frequency`` says validation is due,
     run ``data[setting].dataloader`` (or ``data.dataloader``) without gradients; the loss is ``regression_loss`` per batch, weighted by
     batch size and summed on the device; logits and labels stay on the device until the loader is exhausted.  Returns ``{}`` off the
-    main process or when validation is not due (also with ``return_prediction``, as the reference); otherwise ``column_metrics`` plus ``val_loss``, ``epoch``, ``num_samples`` -- and, with
+    main process or when validation is not due (also with ``return_prediction``, as the reference); otherwise ``column_metrics`` plus ``val_loss``, ``epoch``, ``num_samples`` -- with
+    ``args.bootstrap`` = R > 0 also the keys of ``bootstrap_column_metrics`` (absent, None or 0: nothing changes) -- and, with
     ``return_prediction``, a second dict of the de-normalised ``original_labels`` / ``original_logits`` (float32: value * std + mean,
     with the dataset's ``preset_label_mean`` / ``preset_label_std``, else its ``label_mean`` / ``label_std``) and ``original_true_idx``.
     ``args.save_logs``: the scalars go to ``tb_writer`` under the reference's names, one line to
@@ -253,8 +278,11 @@ def evaluate(model, data, epoch, args, tb_writer=None, setting="val", dinfo_idx=
                 logging.info(f"Eval {setting}-{dinfo_idx} Epoch: {epoch} [{num_samples} / {samples_per_val}]")
     if num_samples == 0:
         raise ValueError("evaluate: the loader is empty")
-    logits, labels = torch.cat(all_logits).cpu().numpy(), torch.cat(all_labels).cpu().numpy()
+    dev_logits, dev_labels = torch.cat(all_logits), torch.cat(all_labels)
+    logits, labels = dev_logits.cpu().numpy(), dev_labels.cpu().numpy()
     metrics.update(column_metrics(logits, labels))
+    if getattr(args, "bootstrap", None):
+        metrics.update(bootstrap_column_metrics(dev_logits, dev_labels, metrics, args))
     metrics.update({"val_loss": float(cumulative_loss / num_samples), "epoch": epoch, "num_samples": num_samples})
     original_labels = labels.astype(np.float32) * label_std + label_mean
     original_logits = logits.astype(np.float32) * label_std + label_mean

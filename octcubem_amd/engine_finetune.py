@@ -287,7 +287,9 @@ def evaluate_task_report(data_loader, model, device, task, epoch, mode, num_clas
     """The reference's ``evaluate`` (engine_finetune.py:498-813) for all five task modes, the function a driver binds as ``evaluate``.
     ``binary_cls``, ``multi_cls`` and ``multi_label`` go to ``evaluate_report`` unchanged; an unknown mode raises ValueError;
     ``args.frame_inference_all`` / ``return_embeddings`` / ``variable_joint`` must be unset or falsy.  ``args.bootstrap`` (the
-    bootstrap intervals of ``evaluate_report``) is not wired for ``multi_task*`` and ``regression``: set, it raises NotImplementedError.
+    bootstrap intervals of ``evaluate_report``) is refused here for ``multi_task*`` and ``regression``: set, it raises
+    NotImplementedError.  Their intervals are a call of their own, ``bootstrap_task_report`` on the logits and targets that ``evaluate``
+    returns; this function writes the same files with and without them.
 
     ``multi_task*`` (targets [n, T + 1], column 0 the shared "normal" label; ``num_class`` model outputs: 2T for
     'multi_task_default', T + 1 otherwise): returns ``({"loss", "acc1"}, macro roc_auc, macro auprc)`` of
@@ -383,3 +385,68 @@ def evaluate_task_report(data_loader, model, device, task, epoch, mode, num_clas
     if return_bal_acc:
         return stats, macro["roc_auc"], (macro["auprc"], macro["balanced_acc"])
     return stats, macro["roc_auc"], macro["auprc"]
+
+
+def bootstrap_task_report(task, epoch, mode, logits, targets, task_mode, disease_list=None, args=None):
+    """Bootstrap intervals for the two task modes whose report ``evaluate_task_report`` writes without them, from the ``logits`` and
+    ``targets`` that ``evaluate`` returns (a driver calls it after the report).  Appends to ``metrics_ci_<mode>.csv`` under CI_HEADER,
+    with ``args.bootstrap`` = R > 0 resamples and ``args.bootstrap_seed`` / ``bootstrap_alpha`` / ``bootstrap_groups`` as
+    ``_bootstrap_report``; with ``args.bootstrap`` absent, None or 0 it writes nothing and returns None.  ``logits`` and ``targets``
+    may live on the host, as ``evaluate`` returns them (tensors or numpy arrays): they are moved to ``args.device`` (default "cuda"),
+    where the kernels run.
+
+    ``regression``: ``logits[:, 0]`` against column 0 of ``targets`` (as the report), one row per key of
+    ``metrics.regression_measures``, class "target", from ``metrics.bootstrap_regression_measures``.
+    ``multi_task*``: ``metrics.multi_task_problem(targets, logits, task_mode)`` with its ``valid`` handed to
+    ``metrics.bootstrap_rank_metrics``; a task's value in a resample is the mean over its two columns (as
+    ``misc_measures_multi_task``), undefined unless both are defined; per ranking metric one row ``macro`` (the mean over the tasks)
+    and one per task, named as ``evaluate_task_report`` names them.  Returns the result dict of the metrics call."""
+    if not getattr(args, "bootstrap", None):
+        return None
+    multi_task = str(task_mode).startswith("multi_task")
+    if not multi_task and task_mode != "regression":
+        raise ValueError(f"bootstrap_task_report: task_mode {task_mode!r} is reported by evaluate_report (built here: regression, multi_task*)")
+    R = int(args.bootstrap)
+    seed, alpha = int(getattr(args, "bootstrap_seed", 0) or 0), float(getattr(args, "bootstrap_alpha", 0.05) or 0.05)
+    groups = getattr(args, "bootstrap_groups", None)
+    # ``evaluate`` returns host tensors; the kernels take device tensors and have no CPU path
+    device = torch.device(getattr(args, "device", None) or "cuda")
+    logits = torch.as_tensor(np.asarray(logits) if not isinstance(logits, torch.Tensor) else logits).detach().to(device)
+    targets = torch.as_tensor(np.asarray(targets) if not isinstance(targets, torch.Tensor) else targets).detach().to(device)
+    os.makedirs(task, exist_ok=True)
+    rows = []
+    if multi_task:
+        scores, labels, valid = metrics.multi_task_problem(targets, logits, task_mode)
+        res = metrics.bootstrap_rank_metrics(scores, labels, resamples=R, seed=seed, alpha=alpha, groups=groups, valid=valid)
+        T = scores.shape[1] // 2
+        idx = getattr(args, "multi_task_idx", None)
+        if disease_list is None:
+            names = [str(i + 1) for i in range(T)]
+        else:
+            names = [disease_list[idx[i]] if idx is not None else disease_list[i + 1] for i in range(T)]
+        res["tasks"] = {}
+        for key in metrics.RANK_KEYS:
+            samples = res[key]["samples"].reshape(-1, T, 2).mean(axis=2)          # a NaN propagates through the mean
+            point = np.asarray(res[key]["point"], dtype=np.float64).reshape(T, 2).mean(axis=1)
+            low, high, cnt = metrics._interval(samples, alpha, "task")
+            mlow, mhigh, mcnt = metrics._interval(samples.mean(axis=1)[:, None], alpha, "macro over the tasks: column")
+            res["tasks"][key] = {"point": point, "samples": samples, "low": low, "high": high, "n_defined": cnt}
+            rows.append([key, "macro", float(point.mean()), float(mlow[0]), float(mhigh[0]), int(mcnt[0])])
+            rows += [[key, name, float(point[i]), float(low[i]), float(high[i]), int(cnt[i])] for i, name in enumerate(names)]
+    else:
+        out, tgt = logits, targets
+        if tgt.dim() > 1:
+            tgt = tgt[:, 0]
+        if out.dim() > 1:
+            out = out[:, 0]
+        res = metrics.bootstrap_regression_measures(out.reshape(-1).float(), tgt.reshape(-1).float(), resamples=R, seed=seed, alpha=alpha,
+                                                    groups=groups)
+        rows = [[key, "target", float(res[key]["point"][0]), float(res[key]["low"][0]), float(res[key]["high"][0]),
+                 int(res[key]["n_defined"][0])] for key in metrics.REGRESSION_KEYS]
+    with open(os.path.join(task, f"metrics_ci_{mode}.csv"), mode="a", newline="", encoding="utf8") as f:
+        w = csv.writer(f)
+        if f.tell() == 0:
+            w.writerow(CI_HEADER)
+        for row in rows:
+            w.writerow([epoch] + row + [res["resamples"], alpha, seed, res["level"]])
+    return res

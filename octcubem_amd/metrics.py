@@ -479,3 +479,161 @@ def regression_measures(pred, target) -> Dict[str, float]:
     dc = d - d.mean()
     return {"pearsonr": r, "r2": 1.0 - float(np.sum(d * d)) / syy, "explained_variance": 1.0 - float(np.sum(dc * dc)) / syy,
             "mse": float(np.mean(d * d)), "mae": float(np.mean(np.abs(d))), "R2": r * r}
+
+
+# ---- bootstrap intervals of the regression metrics.  Every entry of ``regression_measures`` of one resample is a function of eight
+# weighted sums over the samples (count, sum a, sum b, sum a^2, sum b^2, sum a b, sum e^2, sum |e| with a = x - cx, b = y - cy,
+# e = y - x), and a resample is a row of multiplicities: ops.bootstrap_moments (csrc/bootmoments.hip) forms all R rows of sums as one
+# int32 x f64 matrix product in a fixed order, and the host finishes them here in float64.  The draws are those of the ranking
+# metrics (``bootstrap_multiplicities``); ``kernel=`` replaces the device op by any function of its signature
+# (tests/bootmoments_ref.py: numpy and exact rationals).
+REGRESSION_KEYS = ("pearsonr", "r2", "explained_variance", "mse", "mae", "R2")
+
+
+def _device_bootmoments(pred, target, mult, unit=None, valid=None, centre=None):
+    if not all(isinstance(t, torch.Tensor) for t in (pred, target, mult)):
+        raise TypeError("the resamples come from the HIP kernel, which takes GPU tensors (there is no CPU path): pass tensors on the "
+                        "device, or a kernel function")
+    from . import ops
+    return ops.bootstrap_moments(pred, target, mult, unit, valid, centre)
+
+
+def regression_variance_threshold(n: int) -> float:
+    """tau(n) = (n + 8) 2^-50: a resample whose centred sum of squares Sxx = D3 - D1^2 / W is at most tau D3 has no variance that the
+    sums can tell from zero, and counts as constant.
+
+    Derivation, u = 2^-53, n the larger of the sample and the unit count.  D3 = sum w a^2 reaches the host with a relative error of at
+    most (s + 6) u from the sums of a unit of s samples plus (U + 2) u from the product over U units, together below (2 n + 8) u of
+    D3 (every term is positive, so the sum of the magnitudes is D3 itself).  D1 = sum w a carries the same share of sum w |a|, and by
+    Cauchy-Schwarz (sum w |a|)^2 <= W D3, so D1^2 / W is off by at most (2 (2 n + 8) + 2) u of D3 (the square doubles the share; one
+    rounding each for the product and the quotient).  The difference adds one rounding: in all (6 n + 27) u D3 <= (6 n + 30) 2^-53 D3.
+    tau = (n + 8) 2^-50 = (8 n + 64) 2^-53 lies above that, so a resample of one sample drawn n times, whose exact Sxx is 0, computes
+    an Sxx within its own error of zero and is caught, whatever the shift of the centre; a resample with two distinct values x1 != x2
+    has Sxx / D3 of the order (x1 - x2)^2 / (n max a^2), far above tau unless the values agree to about 2^-25 of their distance from
+    the centre -- float32 inputs centred near their mean do not."""
+    return (n + 8) * 2.0 ** -50
+
+
+def finish_regression_moments(moments, centre, n: int) -> dict:
+    """``moments`` float64 [R, C, 8] and ``centre`` float64 [2, C] of ``ops.bootstrap_moments`` -> the six entries of
+    ``regression_measures`` as float64 [R, C] each.  With W = D0:
+    Sxx = D3 - D1^2 / W, Syy = D4 - D2^2 / W, Sxy = D5 - D1 D2 / W, sum e = D2 - D1 + (cy - cx) W,
+    pearsonr = clip(Sxy / sqrt(Sxx Syy)), r2 = 1 - D6 / Syy, explained_variance = 1 - (D6 - (sum e)^2 / W) / Syy, mse = D6 / W,
+    mae = D7 / W, R2 = pearsonr^2.  NaN (undefined): mse / mae only where W == 0; the four other keys where W < 2, Sxx <= tau D3 or
+    Syy <= tau D4 with tau = ``regression_variance_threshold(n)``."""
+    D = np.asarray(_host(moments), dtype=np.float64)
+    c = np.asarray(_host(centre), dtype=np.float64)
+    W, D1, D2, D3, D4, D5, D6, D7 = (D[:, :, k] for k in range(8))
+    tau = regression_variance_threshold(n)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sxx, syy, sxy = D3 - D1 * D1 / W, D4 - D2 * D2 / W, D5 - D1 * D2 / W
+        se = D2 - D1 + (c[1] - c[0])[None, :] * W
+        bad = ~((W >= 2) & (sxx > tau * D3) & (syy > tau * D4))
+        empty = ~(W > 0)
+        r = np.clip(sxy / np.sqrt(sxx * syy), -1.0, 1.0)
+        out = {"pearsonr": r, "r2": 1.0 - D6 / syy, "explained_variance": 1.0 - (D6 - se * se / W) / syy, "mse": D6 / W, "mae": D7 / W,
+               "R2": r * r}
+    return {k: np.where(empty if k in ("mse", "mae") else bad, np.nan, v) for k, v in out.items()}
+
+
+def _regression_problem(pred, target, valid, resamples, seed, groups, mult, name):
+    """``(pred float32 [n, C], target float32 [n, C], valid uint8 [n, C] or None, unit or None, mult)``: torch tensors where ``pred``
+    lives when it is a tensor, numpy arrays otherwise; 1-D inputs become one column."""
+    as_tensor = isinstance(pred, torch.Tensor)
+    if as_tensor:
+        x = pred.detach().float()
+        y = torch.as_tensor(target).detach().to(x.device).float()
+        val = None if valid is None else (torch.as_tensor(valid).detach().to(x.device) != 0).to(torch.uint8)
+    else:
+        x, y = np.asarray(_host(pred), dtype=np.float32), np.asarray(_host(target), dtype=np.float32)
+        val = None if valid is None else (_host(valid) != 0).astype(np.uint8)
+    if x.ndim == 1:
+        x, y, val = x.reshape(-1, 1), y.reshape(-1, 1), None if val is None else val.reshape(-1, 1)
+    if x.ndim != 2 or tuple(y.shape) != tuple(x.shape) or (val is not None and tuple(val.shape) != tuple(x.shape)) or x.shape[0] < 1:
+        raise ValueError(f"{name}: expected pred, target and valid [n] or [n, C], got {tuple(x.shape)}, {tuple(y.shape)}"
+                         + ("" if val is None else f", {tuple(val.shape)}"))
+    n = x.shape[0]
+    unit, U = None, n
+    if groups is not None:
+        ids, U = _dense_ids(groups)
+        if ids.shape[0] != n:
+            raise ValueError(f"{name}: {n} samples but {ids.shape[0]} group ids")
+        unit = torch.from_numpy(ids).to(x.device) if as_tensor else ids
+    if mult is None:
+        mult = bootstrap_multiplicities(int(resamples), U, seed, x.device if as_tensor else "cpu")
+        mult = mult if as_tensor else mult.numpy()
+    elif len(mult.shape) != 2 or tuple(mult.shape)[1:] != (U,) or mult.shape[0] < 1:
+        raise ValueError(f"{name}: expected mult [R, {U}], got {tuple(mult.shape)}")
+    return x, y, val, unit, mult
+
+
+def _regression_point(x, y, val) -> dict:
+    """``regression_measures`` per column over the column's valid rows: key -> float64 [C]."""
+    xh, yh = _host(x), _host(y)
+    vh = None if val is None else _host(val) != 0
+    cols = [regression_measures(xh[:, j] if vh is None else xh[vh[:, j], j], yh[:, j] if vh is None else yh[vh[:, j], j])
+            for j in range(xh.shape[1])]
+    return {k: np.asarray([m[k] for m in cols], dtype=np.float64) for k in REGRESSION_KEYS}
+
+
+def _regression_samples(x, y, val, unit, mult, kernel) -> dict:
+    raw = (kernel or _device_bootmoments)(x, y, mult, unit, val, None)
+    return finish_regression_moments(raw["moments"], raw["centre"], max(int(x.shape[0]), int(mult.shape[1])))
+
+
+def _require_defined(samples: np.ndarray, name: str, key: str):
+    for j in range(samples.shape[1]):
+        if np.isnan(samples[:, j]).all():
+            raise ValueError(f"{name}: column {j}: no resample has a defined {key} (fewer than two distinct predictions or targets in "
+                             "every one): the interval is not defined")
+
+
+def bootstrap_regression_measures(pred, target, *, resamples: int = 1000, seed: int = 0, alpha: float = 0.05, groups=None, valid=None,
+                                  mult=None, kernel: Optional[Callable] = None) -> dict:
+    """Bootstrap percentile intervals of the six entries of ``regression_measures``: ``pred`` and ``target`` [n] or [n, C], ``valid``
+    of the same shape or None (!= 0: the sample counts for the column).
+
+    Returns, for each of ``pearsonr``, ``r2``, ``explained_variance``, ``mse``, ``mae``, ``R2``, a dict of ``point`` [C]
+    (``regression_measures`` per column over its valid rows, unchanged: ValueError for a constant column), ``samples`` float64 [R, C]
+    (NaN where the resample is undefined, see ``finish_regression_moments``), ``low`` / ``high`` [C] (``np.quantile`` at ``alpha / 2``
+    and ``1 - alpha / 2`` over the column's defined resamples) and ``n_defined`` [C]; and ``resamples`` (R) and ``level`` ("sample" or
+    "group").  Undefined resamples are dropped and counted, not redrawn; ValueError for a column without a defined resample.
+
+    ``groups``, ``mult``, ``seed`` as in ``bootstrap_rank_metrics``: the same draws.  By default the sums come from
+    ops.bootstrap_moments, for which the inputs must be GPU tensors (there is no CPU path); ``kernel`` replaces it by a function of the
+    same signature."""
+    name = "bootstrap_regression_measures"
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"{name}: alpha must lie in (0, 1), got {alpha}")
+    x, y, val, unit, mult = _regression_problem(pred, target, valid, resamples, seed, groups, mult, name)
+    point = _regression_point(x, y, val)
+    samples = _regression_samples(x, y, val, unit, mult, kernel)
+    out: dict = {"resamples": int(mult.shape[0]), "level": "sample" if groups is None else "group"}
+    for key in REGRESSION_KEYS:
+        _require_defined(samples[key], name, key)
+        low, high, cnt = _interval(samples[key], alpha, "column")
+        out[key] = {"point": point[key], "samples": samples[key], "low": low, "high": high, "n_defined": cnt}
+    return out
+
+
+def bootstrap_compare_regression(pred_a, pred_b, target, *, resamples: int = 1000, seed: int = 0, alpha: float = 0.05, groups=None,
+                                 valid=None, mult=None, kernel: Optional[Callable] = None) -> dict:
+    """Paired comparison of two prediction sets against one target set: both meet the SAME multiplicities, and per key of
+    ``regression_measures`` the result holds ``delta_point`` (a - b on the full set), ``delta_low`` / ``delta_high``, ``p`` and
+    ``n_defined`` as ``bootstrap_compare`` defines them, [C] each; plus ``resamples`` and ``level``."""
+    name = "bootstrap_compare_regression"
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"{name}: alpha must lie in (0, 1), got {alpha}")
+    xa, y, val, unit, mult = _regression_problem(pred_a, target, valid, resamples, seed, groups, mult, name)
+    xb = _regression_problem(pred_b, target, valid, resamples, seed, groups, mult, name)[0]
+    if tuple(xa.shape) != tuple(xb.shape):
+        raise ValueError(f"{name}: the two prediction sets differ in shape: {tuple(xa.shape)} and {tuple(xb.shape)}")
+    pa, pb = _regression_point(xa, y, val), _regression_point(xb, y, val)
+    sa, sb = _regression_samples(xa, y, val, unit, mult, kernel), _regression_samples(xb, y, val, unit, mult, kernel)
+    out: dict = {"resamples": int(mult.shape[0]), "level": "sample" if groups is None else "group"}
+    for key in REGRESSION_KEYS:
+        delta = sa[key] - sb[key]
+        _require_defined(delta, name, key)
+        low, high, p, cnt = _delta_summary(delta, alpha, "column")
+        out[key] = {"delta_point": pa[key] - pb[key], "delta_low": low, "delta_high": high, "p": p, "n_defined": cnt}
+    return out

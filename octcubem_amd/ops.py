@@ -1237,6 +1237,113 @@ def bootstrap_rank_metrics(scores: torch.Tensor, labels: torch.Tensor, mult: tor
     return out
 
 
+def bootstrap_moments(pred: torch.Tensor, target: torch.Tensor, mult: torch.Tensor, unit: Optional[torch.Tensor] = None,
+                      valid: Optional[torch.Tensor] = None, centre: Optional[torch.Tensor] = None) -> dict:
+    """The eight weighted sums behind the regression metrics of R bootstrap resamples, as one int32 x f64 matrix product on the f64
+    MFMA (csrc/bootmoments.hip).  ``pred`` and ``target`` float32 [n, C] and ``valid`` bool or uint8 [n, C] (column slices of wider
+    buffers pass: unit column stride, any row stride >= C); ``mult`` int32 [R, U]; ``unit`` int32 or int64 [n] (None: the sample
+    itself, ``U == n``); ``centre`` float64 [2, C], the shift of the predictions and of the targets (None: the float64 mean of the
+    valid entries of each column, 0 for a column without one; a shift only, any value is mathematically correct).
+
+    Returns device tensors ``moments`` float64 [R, C, 8] (per resample and column: count, sum a, sum b, sum a^2, sum b^2, sum a b,
+    sum e^2, sum |e| with a = x - centre[0], b = y - centre[1], e = y - x), ``centre`` float64 [2, C] as used, and ``unit_moments``
+    float64 [U, C, 8], the same sums per unit.  ``octcubem_amd.metrics.bootstrap_regression_measures`` finishes them.  Fixed summation
+    order: the same bits on every run, and a resample's row does not depend on the other rows.
+
+    ValueError before any launch, from one readback: a unit id outside [0, U), a negative multiplicity, a non-finite prediction or
+    target at a valid position, a non-finite ``centre``.  No autograd, no CPU path."""
+    name = "bootstrap_moments"
+    tensors = [("pred", pred), ("target", target), ("mult", mult)] + [(w, t) for w, t in (("unit", unit), ("valid", valid), ("centre", centre))
+                                                                      if t is not None]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for _, t in tensors):
+        raise RuntimeError(f"{name}: expected GPU tensors (the HIP path has no CPU fallback)")
+    for what, t in tensors[:2]:
+        if t.dtype != F32:
+            raise TypeError(f"{name}: {what} must be float32, got {t.dtype}")
+    if valid is not None and valid.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{name}: valid must be bool or uint8, got {valid.dtype}")
+    if mult.dtype != torch.int32:
+        raise TypeError(f"{name}: mult must be int32, got {mult.dtype}")
+    if unit is not None and unit.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: unit must be int32 or int64, got {unit.dtype}")
+    if centre is not None and centre.dtype != torch.float64:
+        raise TypeError(f"{name}: centre must be float64, got {centre.dtype}")
+    planes = tensors[:2] + ([("valid", valid)] if valid is not None else [])
+    if pred.dim() != 2 or any(t.shape != pred.shape for _, t in planes) or any(t.device != pred.device for _, t in tensors):
+        raise ValueError(f"{name}: expected {', '.join(w for w, _ in planes)} [n, C] on one device, got "
+                         f"{' and '.join(str(tuple(t.shape)) for _, t in planes)}")
+    n, C = pred.shape
+    if n < 1 or C < 1:
+        raise ValueError(f"{name}: empty input {tuple(pred.shape)}")
+    if mult.dim() != 2 or mult.shape[0] < 1 or mult.shape[1] < 1:
+        raise ValueError(f"{name}: expected mult [R, U], got {tuple(mult.shape)}")
+    R, U = mult.shape
+    if unit is None and U != n:
+        raise ValueError(f"{name}: without unit every sample is its own unit: mult must be [R, {n}], got {tuple(mult.shape)}")
+    if unit is not None and unit.shape != (n,):
+        raise ValueError(f"{name}: expected unit [{n}], got {tuple(unit.shape)}")
+    if centre is not None and centre.shape != (2, C):
+        raise ValueError(f"{name}: expected centre [2, {C}], got {tuple(centre.shape)}")
+    planes = [(what, t.detach().view(torch.uint8) if t.dtype == torch.bool else t.detach()) for what, t in planes]
+    for what, t in planes:
+        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
+            raise ValueError(f"{name}: {what} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
+    pred, target = planes[0][1], planes[1][1]
+    val_bytes = planes[2][1] if valid is not None else None
+    mult = mult.detach().contiguous()
+    dev = pred.device
+    val = None if val_bytes is None else val_bytes != 0
+    bad_value = ~(torch.isfinite(pred) & torch.isfinite(target))
+    if val is not None:
+        bad_value = bad_value & val
+    if unit is None:
+        bad_unit = torch.zeros((), dtype=torch.bool, device=dev)
+    else:
+        unit = unit.detach().long()
+        bad_unit = ((unit < 0) | (unit >= U)).any()
+    bad_centre = torch.zeros((), dtype=torch.bool, device=dev) if centre is None else ~torch.isfinite(centre).all()
+    # the four checks as one readback: [bad unit, negative multiplicity, non-finite value, non-finite centre]
+    bad_u, neg, bad_v, bad_c = torch.stack([bad_unit, (mult < 0).any(), bad_value.any(), bad_centre]).tolist()
+    if bad_u:
+        raise ValueError(f"{name}: unit ids must lie in [0, {U})")
+    if neg:
+        raise ValueError(f"{name}: mult holds a negative multiplicity")
+    if bad_v:
+        raise ValueError(f"{name}: pred or target is not finite" + ("" if valid is None else " at a valid position"))
+    if bad_c:
+        raise ValueError(f"{name}: centre is not finite")
+    if centre is None:
+        # float64 sums over dim 0 of a fixed shape: torch reduces them without atomics, the same bits on every run
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        keep = torch.ones_like(pred, dtype=torch.bool) if val is None else val
+        cnt = keep.sum(dim=0).clamp(min=1).double()
+        centre = torch.stack([torch.where(keep, pred.double(), zero).sum(dim=0) / cnt, torch.where(keep, target.double(), zero).sum(dim=0) / cnt])
+    centre = centre.detach().contiguous()
+    if unit is None:
+        order = torch.arange(n, dtype=torch.int32, device=dev)
+        start = torch.arange(U + 1, dtype=torch.int32, device=dev)
+    else:
+        order = torch.sort(unit, stable=True).indices.to(torch.int32)
+        start = torch.zeros(U + 1, dtype=torch.int32, device=dev)
+        start[1:] = torch.cumsum(torch.bincount(unit, minlength=U), dim=0)
+    cpad8 = (8 * C + 15) // 16 * 16
+    F = torch.empty((U, cpad8), dtype=torch.float64, device=dev)
+    D = torch.empty((R, cpad8), dtype=torch.float64, device=dev)
+    nws = int(load().octmae_bootstrap_moments_ws(R, U, C))
+    if nws < 0:
+        raise ValueError(f"{name}: R = {R}, U = {U}, C = {C} exceed the kernel's limits (R <= 2^20, U <= 2^24, C <= 4096, R x padded columns < 2^32)")
+    ws = torch.empty(max(nws, 1), dtype=torch.float64, device=dev)
+    _launch("unit_moments", 0.0, float(n * C * 9 + U * cpad8 * 8),
+            lambda: call("octmae_unit_moments", pred.data_ptr(), pred.stride(0) if n > 1 else C, target.data_ptr(),
+                         target.stride(0) if n > 1 else C, 0 if val_bytes is None else val_bytes.data_ptr(),
+                         C if val_bytes is None or n == 1 else val_bytes.stride(0), centre.data_ptr(), order.data_ptr(), start.data_ptr(),
+                         F.data_ptr(), n, C, U, _stream()))
+    # algorithmic HBM bytes: mult once, F once (every block of resamples re-reads it from the caches), the output
+    _launch(name, 2.0 * R * U * cpad8, float(R * U * 4 + U * cpad8 * 8 + R * cpad8 * 8),
+            lambda: call("octmae_bootstrap_moments", mult.data_ptr(), F.data_ptr(), D.data_ptr(), ws.data_ptr(), R, U, C, _stream()))
+    return {"moments": D[:, :8 * C].reshape(R, C, 8), "centre": centre, "unit_moments": F[:, :8 * C].reshape(U, C, 8)}
+
+
 def _pair_shapes(name: str, a, b, others, fits: Optional[str] = None, f32_others: bool = False):
     """The operand contract of the ops on the f32 similarity tile (csrc/simtile.hpp): ``a`` float32 [n, d] and ``b`` float32 [m, d]
     on one GPU, none empty, row counts in int32.  ``others``: (tensor or None, name) pairs that must be GPU tensors too, and float32
