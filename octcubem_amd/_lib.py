@@ -7,147 +7,83 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OCTMAE_LIB", os.path.join(_HERE, "liboctmae.so"))   # OCTMAE_LIB: A/B a variant build
 
 _vp, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
-
-# name -> argtypes ; every function returns int (0 ok, <0 bad argument, >0 hipError_t)
-SIGNATURES = {
-    "octmae_abi_version": [],
-    "octmae_lp_dtype": [],
-    "octmae_set_option": [C.c_char_p, _i],
-    "octmae_gemm_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_gemm_bf16_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp],
-    "octmae_gemm_split_ws_kib": [],
-    "octmae_gemm_small_plan": [_i, _i, _i, _i, _i, _i, _vp, _vp],
-    "octmae_gemm_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_wgrad_pair_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
-    "octmae_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "octmae_layernorm_bwd_ws_floats": [_i, _i],
-    "octmae_ln_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "octmae_gelu_apply": [_vp, _vp, _ll, _vp],
-    "octmae_slice_pool_ws_floats": [_i, _i, _i],
-    "octmae_slice_pool_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
-    "octmae_slice_pool_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "octmae_volume_box": [_vp, _i, _i, _i, _i, _vp, _vp],
-    "octmae_volume_resample": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp],
-    "octmae_image_resample": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    "octmae_image_resample_plan": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    "octmae_image_stats": [_vp, _i, _i, _i, _vp, _vp, _vp],
-    "octmae_image_augment": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "octmae_rank_counts": [_vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
-    "octmae_rank_counts_masked": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _vp],
-    "octmae_bootstrap_rank_metrics": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _ll, _ll, _vp],
-    "octmae_unit_moments": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _i, _ll, _vp],
-    "octmae_bootstrap_moments_ws": [_ll, _ll, _i],
-    "octmae_bootstrap_moments": [_vp, _vp, _vp, _vp, _ll, _ll, _i, _vp],
-    "octmae_retrieval_ranks": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _i, _vp],
-    "octmae_retrieval_topk_ws": [_ll, _ll, _i],
-    "octmae_retrieval_topk": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],
-    "octmae_retrieval_pair_ws": [_ll, _i],
-    "octmae_retrieval_pair_ranks": [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _vp, _vp, _ll, _ll, _i, _vp],
-    "octmae_clip_loss_ws_floats": [_ll, _ll],
-    "octmae_clip_loss_fwd": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _i, _vp],
-    "octmae_clip_loss_bwd": [_vp, _ll, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _ll, _ll, _i, _vp],
-    "octmae_join_ws_floats": [_i, _i, _i],
-    "octmae_join_fwd": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    "octmae_join_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "octmae_slabnorm_ws_floats": [_i, _i, _i, _i],
-    "octmae_slab_norm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
-    "octmae_slab_norm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "octmae_dwconv7_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "octmae_dwconv7_bwd_input": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "octmae_dwconv7_bwd_weight_ws_floats": [_i, _i, _i, _i],
-    "octmae_dwconv7_bwd_weight": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "octmae_layer_scale_fwd": [_vp, _vp, _vp, _vp, _i, _i, _vp],
-    "octmae_layer_scale_bwd_ws_floats": [_i, _i],
-    "octmae_layer_scale_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "octmae_mix_batch": [_vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp],
-    "octmae_attn_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "octmae_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "octmae_attn_bwd_fused_ws_kib": [_i, _i, _i, _i],
-    "octmae_attn_bwd_fused": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "octmae_attn_bwd_fused_delta": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "octmae_attn_bwd_rowconst": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "octmae_attn_bwd_dq_rowconst": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "octmae_attn_bwd_dq": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "octmae_attn_bwd_dkv": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "octmae_random_masking_ids": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "octmae_cast_f32_bf16": [_vp, _vp, _ll, _vp],
-    "octmae_cast_rowscale_f32_bf16": [_vp, _vp, _vp, _ll, _i, _i, _vp],
-    "octmae_linear_resid_rowscale": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp],
-    "octmae_colsum_accum": [_vp, _i, _vp, _i, _i, _i, _vp],
-    "octmae_colsum_ws_rows": [_i],
-    "octmae_colsum_accum_ws": [_vp, _i, _vp, _vp, _i, _i, _i, _vp],
-    "octmae_dgelu_colsum_ws_rows": [_i],
-    "octmae_linear_dgrad_dgelu": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp],
-    "octmae_linear_dgrad_delta": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp],
-    "octmae_wgrad_split_plan": [_i, _i, _i, _vp, _vp],
-    "octmae_wgrad_accum_pair": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_patch_gather": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_enc_assemble": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "octmae_dec_assemble": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "octmae_gather_rows_cast": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "octmae_scatter_add_rows": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_dec_assemble_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "octmae_mse_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_mse_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_mae_compose": [_vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_mae_compose_nc": [_vp, _ll, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _vp],
-    "octmae_white_border_ws_floats": [_i, _i, _i, _i],
-    "octmae_white_border": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_patch_scatter": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_cam_ws_floats": [_i, _i, _i],
-    "octmae_cam_weights": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "octmae_cam_tokens": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "octmae_cam_eigen_ws_floats": [_i, _i, _i],
-    "octmae_cam_eigen": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_cam_accumulate": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "octmae_heatmap": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "octmae_mt_chunk_elems": [],
-    "octmae_mt_sumsq": [_vp, _vp, _vp, _i, _vp, _vp],
-    "octmae_mt_finish_norm": [_vp, _i, _f, _vp, _vp, _vp],
-    "octmae_mt_adamw": [_vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _i, _vp],
-    "octmae_mt_adamw_fused": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _vp],
-    "octmae_comm_available": [],
-    "octmae_comm_unique_id": [_vp],
-    "octmae_comm_init": [_vp, _vp, _i, _i, _i],
-    "octmae_comm_destroy": [_vp],
-    "octmae_comm_rank": [_vp],
-    "octmae_comm_world": [_vp],
-    "octmae_comm_allreduce_async": [_vp, _vp, _ll, _i, _i, _vp],
-    "octmae_comm_broadcast_async": [_vp, _vp, _ll, _i, _i, _vp],
-    "octmae_comm_allgather_async": [_vp, _vp, _vp, _ll, _i, _vp],
-    "octmae_comm_reduce_scatter_async": [_vp, _vp, _vp, _ll, _i, _i, _vp],
-    "octmae_comm_wait": [_vp, _vp],
-    "octmae_comm_stream": [_vp, _vp],
-    "octmae_probe_mfma32": [_vp, _vp, _vp, _vp],
-    "octmae_probe_trread": [_vp, _vp, _vp],
-}
-
-# ... except a workspace query whose value is long long in the header: a byte count for the two retrieval queries, a count of
-# DOUBLES for octmae_bootstrap_moments_ws
-RESTYPES = {"octmae_retrieval_topk_ws": _ll, "octmae_retrieval_pair_ws": _ll, "octmae_bootstrap_moments_ws": _ll}
-
-_lib = None
-_on_load = []       # callbacks run once, right after the library has been loaded and bound (ops: operand-type check)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "octmae.h")
-
-
-def expected_abi_version() -> int:
-    """OCTMAE_ABI_VERSION as include/octmae.h defines it -- the single place the number is written."""
-    import re
-    m = re.search(r"^#define\s+OCTMAE_ABI_VERSION\s+(\d+)", open(HEADER_PATH).read(), re.M)
-    if m is None:
-        raise OctmaeError(f"{HEADER_PATH} does not define OCTMAE_ABI_VERSION")
-    return int(m.group(1))
 
 
 class OctmaeError(RuntimeError):
     pass
+
+
+# the C spellings include/octmae.h uses, and nothing else: a declaration outside them is refused, never guessed
+_PARAM = {"int": _i, "float": _f, "long long": _ll}                     # by value; anything with a * is a pointer
+_RETURN = {"int": _i, "long long": _ll, "long long int": _ll}
+_COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(OCTMAE_\w+)[ \t]+(-?\d+)[ \t]*$", re.M)
+_ENUM = re.compile(r"\benum\s*\{([^}]*)\}")
+_PROTOTYPE = re.compile(r"(?:^|(?<=[;{}]))\s*([^;{}()]*?)\b(octmae_\w+)\s*\(([^)]*)\)\s*;", re.M)
+
+
+def _argtype(fn: str, param: str):
+    words = param.replace("*", " * ").split()
+    if "*" in words:
+        return C.c_char_p if words[:3] == ["const", "char", "*"] and words.count("*") == 1 else _vp
+    for spelling in (" ".join(words), " ".join(words[:-1])):            # unnamed, or followed by the parameter's name
+        if spelling in _PARAM:
+            return _PARAM[spelling]
+    raise OctmaeError(f"{fn}: no ctypes binding for the parameter {param.strip()!r}")
+
+
+def parse_header(text: str):
+    """(signatures, restypes, constants) of a C header in the style of include/octmae.h: every prototype
+    ``int | long long [int]  octmae_<name>(...);`` as name -> ctypes argument list, the returns that are not ``int`` as name -> ctype, and
+    the integer ``#define OCTMAE_*`` values and anonymous ``enum { OCTMAE_* = n }`` members as name -> int.  Comments are ignored."""
+    text = _COMMENT.sub(" ", text)
+    constants = {name: int(value) for name, value in _DEFINE.findall(text)}
+    for body in _ENUM.findall(text):
+        for member in filter(None, (m.strip() for m in body.split(","))):
+            m = re.fullmatch(r"(OCTMAE_\w+)\s*=\s*(-?\d+)", member)
+            if m is None:
+                raise OctmaeError(f"enum member {member!r}: expected OCTMAE_<NAME> = <integer>")
+            constants[m.group(1)] = int(m.group(2))
+    signatures, restypes = {}, {}
+    for ret, fn, params in _PROTOTYPE.findall(re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)):
+        ret = " ".join(ret.split())
+        if ret not in _RETURN:
+            raise OctmaeError(f"{fn}: no ctypes binding for the return type {ret!r}")
+        signatures[fn] = [] if params.strip() == "void" else [_argtype(fn, p) for p in params.split(",")]
+        if _RETURN[ret] is not _i:
+            restypes[fn] = _RETURN[ret]
+    return signatures, restypes, constants
+
+
+def _parse_header_file():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise OctmaeError(f"{HEADER_PATH} cannot be read ({e.strerror}): the ctypes bindings are derived from it") from e
+
+
+# SIGNATURES: name -> argtypes; every function returns int (0 ok, <0 bad argument, >0 hipError_t) ...
+# RESTYPES: ... except a workspace query whose value is long long in the header: a byte count for the two retrieval queries, a count of
+# DOUBLES for octmae_bootstrap_moments_ws.  CONSTANTS: the header's integer #defines and enum members.
+SIGNATURES, RESTYPES, CONSTANTS = _parse_header_file()
+
+_lib = None
+_on_load = []       # callbacks run once, right after the library has been loaded and bound (ops: operand-type check)
+
+
+def expected_abi_version() -> int:
+    """OCTMAE_ABI_VERSION as include/octmae.h defines it -- the single place the number is written."""
+    if "OCTMAE_ABI_VERSION" not in CONSTANTS:
+        raise OctmaeError(f"{HEADER_PATH} does not define OCTMAE_ABI_VERSION")
+    return CONSTANTS["OCTMAE_ABI_VERSION"]
 
 
 def load():
@@ -170,7 +106,7 @@ def load():
             raise OctmaeError(f"liboctmae.so does not export {name}") from e
         fn.argtypes = argtypes
         fn.restype = RESTYPES.get(name, C.c_int)
-    if os.path.exists(HEADER_PATH) and lib.octmae_abi_version() != expected_abi_version():
+    if lib.octmae_abi_version() != expected_abi_version():
         raise OctmaeError(f"{LIB_PATH} reports ABI {lib.octmae_abi_version()}, include/octmae.h declares "
                           f"{expected_abi_version()}: rebuild (make -C octcubem_amd/csrc)")
     _lib = lib

@@ -15,12 +15,13 @@ from typing import Optional
 
 import torch
 
-from ._lib import call, load
+from ._lib import CONSTANTS, call, load
 
-F32, BF16, F64, F16 = 0, 1, 2, 3
-SUM, AVG, MAX = 0, 1, 2
+# the OCTMAE_COMM_* values of include/octmae.h
+F32, BF16, F64, F16 = (CONSTANTS[f"OCTMAE_COMM_{n}"] for n in ("F32", "BF16", "F64", "F16"))
+SUM, AVG, MAX = (CONSTANTS[f"OCTMAE_COMM_{n}"] for n in ("SUM", "AVG", "MAX"))
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float64: F64, torch.float16: F16}      # F16: collectives of the half-operand build
-ID_BYTES = 128
+ID_BYTES = CONSTANTS["OCTMAE_COMM_ID_BYTES"]
 
 _default: Optional["NativeComm"] = None
 

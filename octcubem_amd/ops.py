@@ -1089,41 +1089,23 @@ def white_border(imgs: torch.Tensor):
 
 def _rank_counts(name: str, scores: torch.Tensor, labels: torch.Tensor, valid: Optional[torch.Tensor]) -> torch.Tensor:
     """The checks and the launch that ``rank_counts`` (valid None) and ``rank_counts_masked`` share."""
-    flags = (("labels", labels),) if valid is None else (("labels", labels), ("valid", valid))
-    if not scores.is_cuda or not all(t.is_cuda for _, t in flags):
-        raise RuntimeError(f"{name}: expected GPU tensors (the HIP path has no CPU fallback)")
-    if scores.dtype != F32:
-        raise TypeError(f"{name}: scores must be float32, got {scores.dtype}")
-    for what, t in flags:
-        if t.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"{name}: {what} must be bool or uint8, got {t.dtype}")
-    if scores.dim() != 2 or any(t.shape != scores.shape or t.device != scores.device for _, t in flags):
-        raise ValueError(f"{name}: expected scores and {' and '.join(w for w, _ in flags)} [n, C] on one device, got "
-                         f"{tuple(scores.shape)} and {' and '.join(str(tuple(t.shape)) for _, t in flags)}")
-    n, C = scores.shape
-    if n < 1 or C < 1:
-        raise ValueError(f"{name}: empty input {tuple(scores.shape)}")
-    scores = scores.detach()
-    # a bool is stored as 0 / 1: the same bytes
-    flags = tuple((what, t.detach().view(torch.uint8) if t.dtype == torch.bool else t.detach()) for what, t in flags)
-    for what, t in (("scores", scores),) + flags:
-        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
-            raise ValueError(f"{name}: {what} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
+    flags = {"labels": labels} if valid is None else {"labels": labels, "valid": valid}
+    n, C, planes = _plane_contract(name, {"scores": scores}, flags)
+    ss, ls, *vs = _plane_strides(name, n, C, planes)
+    scores, labels, mask = planes["scores"], planes["labels"], planes.get("valid")
     nan = torch.isnan(scores)
-    if valid is not None:
-        nan = nan & (flags[1][1] != 0)
+    if mask is not None:
+        nan = nan & (mask != 0)
     if bool(nan.any()):
         raise ValueError(f"{name}: scores contain NaN" + ("" if valid is None else " at a valid position"))
-    ss, ls = (t.stride(0) if n > 1 else C for t in (scores, flags[0][1]))
     counts = torch.empty((n, C, 4), dtype=torch.int32, device=scores.device)
     # algorithmic HBM bytes: scores, labels (and the mask) read once (the re-reads of the j stream hit the caches), the counts written once
-    if valid is None:
+    if mask is None:
         _launch(name, 0.0, float(n * C * (4 + 1 + 16)),
-                lambda: call("octmae_rank_counts", scores.data_ptr(), ss, flags[0][1].data_ptr(), ls, counts.data_ptr(), n, C, _stream()))
+                lambda: call("octmae_rank_counts", scores.data_ptr(), ss, labels.data_ptr(), ls, counts.data_ptr(), n, C, _stream()))
     else:
-        vs = flags[1][1].stride(0) if n > 1 else C
         _launch(name, 0.0, float(n * C * (4 + 1 + 1 + 16)),
-                lambda: call("octmae_rank_counts_masked", scores.data_ptr(), ss, flags[0][1].data_ptr(), ls, flags[1][1].data_ptr(), vs,
+                lambda: call("octmae_rank_counts_masked", scores.data_ptr(), ss, labels.data_ptr(), ls, mask.data_ptr(), vs[0],
                              counts.data_ptr(), n, C, _stream()))
     return counts
 
@@ -1163,52 +1145,22 @@ def bootstrap_rank_metrics(scores: torch.Tensor, labels: torch.Tensor, mult: tor
     together: a unit id outside [0, U), a negative multiplicity, largest cluster x largest row sum of ``mult`` >= 2^31 (the running sums
     are 32-bit), a NaN score at a valid position.  +-inf are ordinary scores, -0.0 ties with 0.0.  No autograd, no CPU path."""
     name = "bootstrap_rank_metrics"
-    flags = (("labels", labels),) if valid is None else (("labels", labels), ("valid", valid))
-    others = (("mult", mult),) if unit is None else (("mult", mult), ("unit", unit))
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (scores,) + tuple(t for _, t in flags + others)):
-        raise RuntimeError(f"{name}: expected GPU tensors (the HIP path has no CPU fallback)")
-    if scores.dtype != F32:
-        raise TypeError(f"{name}: scores must be float32, got {scores.dtype}")
-    for what, t in flags:
-        if t.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"{name}: {what} must be bool or uint8, got {t.dtype}")
-    if mult.dtype != torch.int32:
-        raise TypeError(f"{name}: mult must be int32, got {mult.dtype}")
-    if unit is not None and unit.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{name}: unit must be int32 or int64, got {unit.dtype}")
-    if scores.dim() != 2 or any(t.shape != scores.shape for _, t in flags) or any(t.device != scores.device for _, t in flags + others):
-        raise ValueError(f"{name}: expected scores and {' and '.join(w for w, _ in flags)} [n, C] on one device, got "
-                         f"{tuple(scores.shape)} and {' and '.join(str(tuple(t.shape)) for _, t in flags)}")
-    n, C = scores.shape
-    if n < 1 or C < 1:
-        raise ValueError(f"{name}: empty input {tuple(scores.shape)}")
-    if mult.dim() != 2 or mult.shape[0] < 1 or mult.shape[1] < 1:
-        raise ValueError(f"{name}: expected mult [R, U], got {tuple(mult.shape)}")
-    R, U = mult.shape
-    if unit is None and U != n:
-        raise ValueError(f"{name}: without unit every sample is its own unit: mult must be [R, {n}], got {tuple(mult.shape)}")
-    if unit is not None and unit.shape != (n,):
-        raise ValueError(f"{name}: expected unit [{n}], got {tuple(unit.shape)}")
-    scores = scores.detach()
-    flags = tuple((what, t.detach().view(torch.uint8) if t.dtype == torch.bool else t.detach()) for what, t in flags)
-    for what, t in (("scores", scores),) + flags:
-        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
-            raise ValueError(f"{name}: {what} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
-    mult = mult.detach().contiguous()
-    lab = flags[0][1] != 0
-    val = None if valid is None else flags[1][1] != 0
+    flags = {"labels": labels} if valid is None else {"labels": labels, "valid": valid}
+    n, C, planes = _plane_contract(name, {"scores": scores}, flags, _resample_tables(mult, unit))
+    R, U, mult, unit, bad_unit, negative = _resample_contract(name, mult, unit, n)
+    _plane_strides(name, n, C, planes)
+    scores, lab = planes["scores"], planes["labels"] != 0
+    val = None if valid is None else planes["valid"] != 0
     nan = torch.isnan(scores)
     if val is not None:
         nan = nan & val
     row_sum = mult.sum(dim=1, dtype=torch.int64).max()
     if unit is None:
-        bad_unit, cluster = torch.zeros((), dtype=torch.bool, device=scores.device), torch.ones((), dtype=torch.int64, device=scores.device)
+        cluster = torch.ones((), dtype=torch.int64, device=scores.device)
     else:
-        unit = unit.detach().long()
-        bad_unit = ((unit < 0) | (unit >= U)).any()
         cluster = torch.bincount(unit.clamp(0, U - 1), minlength=U).max()
     # the four checks as one readback: [bad unit, negative multiplicity, NaN, largest cluster, largest row sum]
-    bad_u, neg, has_nan, cl, rs = torch.stack([bad_unit.long(), (mult < 0).any().long(), nan.any().long(), cluster, row_sum]).tolist()
+    bad_u, neg, has_nan, cl, rs = torch.stack([bad_unit.long(), negative.long(), nan.any().long(), cluster, row_sum]).tolist()
     if bad_u:
         raise ValueError(f"{name}: unit ids must lie in [0, {U})")
     if neg:
@@ -1253,57 +1205,21 @@ def bootstrap_moments(pred: torch.Tensor, target: torch.Tensor, mult: torch.Tens
     ValueError before any launch, from one readback: a unit id outside [0, U), a negative multiplicity, a non-finite prediction or
     target at a valid position, a non-finite ``centre``.  No autograd, no CPU path."""
     name = "bootstrap_moments"
-    tensors = [("pred", pred), ("target", target), ("mult", mult)] + [(w, t) for w, t in (("unit", unit), ("valid", valid), ("centre", centre))
-                                                                      if t is not None]
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda for _, t in tensors):
-        raise RuntimeError(f"{name}: expected GPU tensors (the HIP path has no CPU fallback)")
-    for what, t in tensors[:2]:
-        if t.dtype != F32:
-            raise TypeError(f"{name}: {what} must be float32, got {t.dtype}")
-    if valid is not None and valid.dtype not in (torch.bool, torch.uint8):
-        raise TypeError(f"{name}: valid must be bool or uint8, got {valid.dtype}")
-    if mult.dtype != torch.int32:
-        raise TypeError(f"{name}: mult must be int32, got {mult.dtype}")
-    if unit is not None and unit.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{name}: unit must be int32 or int64, got {unit.dtype}")
-    if centre is not None and centre.dtype != torch.float64:
-        raise TypeError(f"{name}: centre must be float64, got {centre.dtype}")
-    planes = tensors[:2] + ([("valid", valid)] if valid is not None else [])
-    if pred.dim() != 2 or any(t.shape != pred.shape for _, t in planes) or any(t.device != pred.device for _, t in tensors):
-        raise ValueError(f"{name}: expected {', '.join(w for w, _ in planes)} [n, C] on one device, got "
-                         f"{' and '.join(str(tuple(t.shape)) for _, t in planes)}")
-    n, C = pred.shape
-    if n < 1 or C < 1:
-        raise ValueError(f"{name}: empty input {tuple(pred.shape)}")
-    if mult.dim() != 2 or mult.shape[0] < 1 or mult.shape[1] < 1:
-        raise ValueError(f"{name}: expected mult [R, U], got {tuple(mult.shape)}")
-    R, U = mult.shape
-    if unit is None and U != n:
-        raise ValueError(f"{name}: without unit every sample is its own unit: mult must be [R, {n}], got {tuple(mult.shape)}")
-    if unit is not None and unit.shape != (n,):
-        raise ValueError(f"{name}: expected unit [{n}], got {tuple(unit.shape)}")
+    n, C, planes = _plane_contract(name, {"pred": pred, "target": target}, {} if valid is None else {"valid": valid},
+                                   _resample_tables(mult, unit) + ([] if centre is None else [("centre", centre, (torch.float64,))]))
+    R, U, mult, unit, bad_unit, negative = _resample_contract(name, mult, unit, n)
     if centre is not None and centre.shape != (2, C):
         raise ValueError(f"{name}: expected centre [2, {C}], got {tuple(centre.shape)}")
-    planes = [(what, t.detach().view(torch.uint8) if t.dtype == torch.bool else t.detach()) for what, t in planes]
-    for what, t in planes:
-        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
-            raise ValueError(f"{name}: {what} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
-    pred, target = planes[0][1], planes[1][1]
-    val_bytes = planes[2][1] if valid is not None else None
-    mult = mult.detach().contiguous()
+    ps, ts, *vs = _plane_strides(name, n, C, planes)
+    pred, target, val_bytes = planes["pred"], planes["target"], planes.get("valid")
     dev = pred.device
     val = None if val_bytes is None else val_bytes != 0
     bad_value = ~(torch.isfinite(pred) & torch.isfinite(target))
     if val is not None:
         bad_value = bad_value & val
-    if unit is None:
-        bad_unit = torch.zeros((), dtype=torch.bool, device=dev)
-    else:
-        unit = unit.detach().long()
-        bad_unit = ((unit < 0) | (unit >= U)).any()
     bad_centre = torch.zeros((), dtype=torch.bool, device=dev) if centre is None else ~torch.isfinite(centre).all()
     # the four checks as one readback: [bad unit, negative multiplicity, non-finite value, non-finite centre]
-    bad_u, neg, bad_v, bad_c = torch.stack([bad_unit, (mult < 0).any(), bad_value.any(), bad_centre]).tolist()
+    bad_u, neg, bad_v, bad_c = torch.stack([bad_unit, negative, bad_value.any(), bad_centre]).tolist()
     if bad_u:
         raise ValueError(f"{name}: unit ids must lie in [0, {U})")
     if neg:
@@ -1334,14 +1250,69 @@ def bootstrap_moments(pred: torch.Tensor, target: torch.Tensor, mult: torch.Tens
         raise ValueError(f"{name}: R = {R}, U = {U}, C = {C} exceed the kernel's limits (R <= 2^20, U <= 2^24, C <= 4096, R x padded columns < 2^32)")
     ws = torch.empty(max(nws, 1), dtype=torch.float64, device=dev)
     _launch("unit_moments", 0.0, float(n * C * 9 + U * cpad8 * 8),
-            lambda: call("octmae_unit_moments", pred.data_ptr(), pred.stride(0) if n > 1 else C, target.data_ptr(),
-                         target.stride(0) if n > 1 else C, 0 if val_bytes is None else val_bytes.data_ptr(),
-                         C if val_bytes is None or n == 1 else val_bytes.stride(0), centre.data_ptr(), order.data_ptr(), start.data_ptr(),
-                         F.data_ptr(), n, C, U, _stream()))
+            lambda: call("octmae_unit_moments", pred.data_ptr(), ps, target.data_ptr(), ts, 0 if val_bytes is None else val_bytes.data_ptr(),
+                         vs[0] if vs else C, centre.data_ptr(), order.data_ptr(), start.data_ptr(), F.data_ptr(), n, C, U, _stream()))
     # algorithmic HBM bytes: mult once, F once (every block of resamples re-reads it from the caches), the output
     _launch(name, 2.0 * R * U * cpad8, float(R * U * 4 + U * cpad8 * 8 + R * cpad8 * 8),
             lambda: call("octmae_bootstrap_moments", mult.data_ptr(), F.data_ptr(), D.data_ptr(), ws.data_ptr(), R, U, C, _stream()))
     return {"moments": D[:, :8 * C].reshape(R, C, 8), "centre": centre, "unit_moments": F[:, :8 * C].reshape(U, C, 8)}
+
+
+def _plane_contract(name: str, values: dict, flags: dict, tables=None):
+    """The operand contract of the evaluation ops over [n, C] planes: ``values`` (float32) and ``flags`` (bool or uint8) by name, GPU
+    tensors of one shape on one device, not empty.  ``tables``: a list of (name, tensor, dtypes) for the op's further operands, which must be GPU tensors of one of ``dtypes`` on that device; their shapes are the op's business.  Returns
+    (n, C, planes): every plane by name, values first, detached, a flag plane as uint8 (a bool is stored as 0 / 1: the same bytes)."""
+    operands = [(what, t, (F32,)) for what, t in values.items()] + [(what, t, (torch.bool, torch.uint8)) for what, t in flags.items()]
+    operands += tables or []
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for _, t, _ in operands):
+        raise RuntimeError(f"{name}: expected GPU tensors (the HIP path has no CPU fallback)")
+    for what, t, dtypes in operands:
+        if t.dtype not in dtypes:
+            raise TypeError(f"{name}: {what} must be {' or '.join(str(d).split('.')[-1] for d in dtypes)}, got {t.dtype}")
+    planes = {**values, **flags}
+    first = next(iter(planes.values()))
+    if first.dim() != 2 or any(t.shape != first.shape for t in planes.values()) or any(t.device != first.device for _, t, _ in operands):
+        raise ValueError(f"{name}: expected {' and '.join(planes)} [n, C] on one device, got "
+                         f"{' and '.join(str(tuple(t.shape)) for t in planes.values())}")
+    n, C = first.shape
+    if n < 1 or C < 1:
+        raise ValueError(f"{name}: empty input {tuple(first.shape)}")
+    return n, C, {what: t.detach().view(torch.uint8) if t.dtype == torch.bool else t.detach() for what, t in planes.items()}
+
+
+def _plane_strides(name: str, n: int, C: int, planes: dict):
+    """The row strides the kernels take for the planes of ``_plane_contract``, in their order: unit column stride, any row stride >= C
+    (column slices of wider buffers); a single row has no stride to speak of and passes C.  Apart from ``_plane_contract`` because
+    the bootstrap ops refuse a misshapen resampling table between the two."""
+    for what, t in planes.items():
+        if (C > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < C):
+            raise ValueError(f"{name}: {what} needs unit column stride and a row stride >= {C}, got strides {tuple(t.stride())}")
+    return [t.stride(0) if n > 1 else C for t in planes.values()]
+
+
+def _resample_tables(mult, unit):
+    """The resampling operands as ``tables`` of ``_plane_contract``, which refuses a wrong dtype ahead of every shape."""
+    return [("mult", mult, (torch.int32,))] + ([] if unit is None else [("unit", unit, (torch.int32, torch.int64))])
+
+
+def _resample_contract(name: str, mult: torch.Tensor, unit: Optional[torch.Tensor], n: int):
+    """The resampling contract of the bootstrap ops, after ``_plane_contract``: ``mult`` [R, U], not empty; ``unit`` [n], or None: every
+    sample is its own unit and ``U == n``.  Returns (R, U, mult contiguous, unit as int64 or None) and two DEVICE flags for the
+    caller's one readback: a unit id outside [0, U), a negative multiplicity.  Nothing here waits for the device."""
+    if mult.dim() != 2 or mult.shape[0] < 1 or mult.shape[1] < 1:
+        raise ValueError(f"{name}: expected mult [R, U], got {tuple(mult.shape)}")
+    R, U = mult.shape
+    if unit is None and U != n:
+        raise ValueError(f"{name}: without unit every sample is its own unit: mult must be [R, {n}], got {tuple(mult.shape)}")
+    if unit is not None and unit.shape != (n,):
+        raise ValueError(f"{name}: expected unit [{n}], got {tuple(unit.shape)}")
+    mult = mult.detach().contiguous()
+    if unit is None:
+        bad_unit = torch.zeros((), dtype=torch.bool, device=mult.device)
+    else:
+        unit = unit.detach().long()
+        bad_unit = ((unit < 0) | (unit >= U)).any()
+    return R, U, mult, unit, bad_unit, (mult < 0).any()
 
 
 def _pair_shapes(name: str, a, b, others, fits: Optional[str] = None, f32_others: bool = False):

@@ -14,21 +14,70 @@ from oracle import mae3d_ref as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def declared_symbols():
-    txt = open(os.path.join(ROOT, "include", "octmae.h")).read()
-    return sorted(set(re.findall(r"\bint\s+(octmae_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_library_exports_every_declared_symbol():
+    """_lib binds what include/octmae.h declares, by parsing it: both builds of the library export every parsed name."""
     from octcubem_amd import _lib
     lib = _lib.load()
-    syms = declared_symbols()
-    assert len(syms) >= 20
-    for s in syms:
-        assert hasattr(lib, s), s
-        assert s in _lib.SIGNATURES, f"{s} declared in octmae.h but not bound in _lib.SIGNATURES"
-    assert set(_lib.SIGNATURES) == set(syms)
-    assert lib.octmae_abi_version() == _lib.expected_abi_version() and lib.octmae_mt_chunk_elems() == 65536
+    f16 = ctypes.CDLL(os.path.join(ROOT, "octcubem_amd", "liboctmae_f16.so"))
+    assert len(_lib.SIGNATURES) >= 111
+    for s in _lib.SIGNATURES:
+        assert hasattr(lib, s) and hasattr(f16, s), s
+    assert set(_lib.RESTYPES) <= set(_lib.SIGNATURES)
+    assert lib.octmae_abi_version() == _lib.expected_abi_version() == _lib.CONSTANTS["OCTMAE_ABI_VERSION"] and lib.octmae_mt_chunk_elems() == 65536
+
+
+def test_header_parser_on_literal_declarations():
+    """_lib.parse_header is a pure function of the header text: declarations over several lines, comments stripped first, the pointer
+    rule with its one exception, both spellings of a 64-bit return, integer #defines and enum members; a spelling outside the
+    header's vocabulary is an error that names the function, never a guess."""
+    from octcubem_amd import _lib
+    vp, i, f, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
+    sigs, res, consts = _lib.parse_header("""
+        #define OCTMAE_ABI_VERSION 7
+        #define OCTMAE_H_
+        enum { OCTMAE_X_A = 0, OCTMAE_X_B = 3 /* the last */ };
+        /* int octmae_in_a_comment(int a); */
+        // int octmae_in_a_line_comment(void);
+        typedef struct { int kind, mode; } octmae_desc;
+        int octmae_first(void);
+        int octmae_second(const float* x, long long x_stride,
+                          const octmae_desc* desc, void** out,
+                          int n, float eps,   /* between two parameters */
+                          void* stream);
+        int octmae_option(const char* key, int value);  long long octmae_bytes(long long n, int k);
+        long long int octmae_doubles(long long);
+    """)
+    assert sigs == {"octmae_first": [], "octmae_second": [vp, ll, vp, vp, i, f, vp], "octmae_option": [ctypes.c_char_p, i],
+                    "octmae_bytes": [ll, i], "octmae_doubles": [ll]}
+    assert res == {"octmae_bytes": ll, "octmae_doubles": ll}
+    assert consts == {"OCTMAE_ABI_VERSION": 7, "OCTMAE_X_A": 0, "OCTMAE_X_B": 3}
+    for bad, what in (("int octmae_sized(const float* x, size_t n);", "size_t n"), ("int octmae_wide(double x);", "double x"),
+                      ("unsigned octmae_count(void);", "unsigned"), ("void* octmae_handle(int a);", "void*")):
+        with pytest.raises(_lib.OctmaeError) as e:
+            _lib.parse_header("int octmae_fine(int a);\n" + bad)
+        assert re.search(r"octmae_(sized|wide|count|handle)", str(e.value)) and what in str(e.value), str(e.value)
+
+
+def test_header_mapping_pins():
+    """A few argument lists of the real header written out by hand: they guard the parser's mapping (a long long read as int would
+    truncate a stride without an error), not a second table."""
+    from octcubem_amd import _lib
+    vp, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    sig = _lib.SIGNATURES
+    assert sig["octmae_set_option"] == [ctypes.c_char_p, i]
+    assert sig["octmae_gemm_bf16_ws"] == [vp] * 6 + [i] * 11 + [vp, ll, vp] and _lib._ll is ll
+    assert sig["octmae_linear_dgrad_dgelu"][-3:] == [vp, ll, vp]
+    assert sig["octmae_rank_counts"] == [vp, ll, vp, ll, vp, ll, i, vp]                      # the two row strides and n
+    assert sig["octmae_retrieval_pair_ranks"] == [vp, ll] * 6 + [i, vp, vp, ll, ll, i, vp]   # six strides, ws_bytes, n
+    assert sig["octmae_image_augment"] == [vp, i, i, i] + [vp] * 6                           # struct pointers
+    assert _lib.RESTYPES == {n: ll for n in ("octmae_retrieval_topk_ws", "octmae_retrieval_pair_ws", "octmae_bootstrap_moments_ws")}
+
+
+def test_comm_constants_are_the_headers():
+    from octcubem_amd import _lib, comm
+    assert (comm.F32, comm.BF16, comm.F64, comm.F16) == (0, 1, 2, 3) == tuple(_lib.CONSTANTS[f"OCTMAE_COMM_{n}"] for n in ("F32", "BF16", "F64", "F16"))
+    assert (comm.SUM, comm.AVG, comm.MAX) == (0, 1, 2) == tuple(_lib.CONSTANTS[f"OCTMAE_COMM_{n}"] for n in ("SUM", "AVG", "MAX"))
+    assert comm.ID_BYTES == 128 == _lib.CONSTANTS["OCTMAE_COMM_ID_BYTES"]
 
 
 def test_half_build_exports_the_same_abi_and_reports_its_operand_type():
@@ -40,7 +89,7 @@ def test_half_build_exports_the_same_abi_and_reports_its_operand_type():
     path = os.path.join(ROOT, "octcubem_amd", "liboctmae_f16.so")
     assert os.path.exists(path), "make -C octcubem_amd/csrc both"
     lib = ctypes.CDLL(path)
-    for s in declared_symbols():
+    for s in _lib.SIGNATURES:
         assert hasattr(lib, s), s
     assert lib.octmae_abi_version() == _lib.expected_abi_version()
     assert lib.octmae_lp_dtype() == 1 and _lib.load().octmae_lp_dtype() == 0
