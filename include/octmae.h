@@ -116,7 +116,9 @@ int octmae_set_option(const char* key, int value);
  *                         auto_wgrad_split)       weight gradients (autograd of nn.Linear)
  *                         a non-NULL C2 is an fp32 [NA] vector that receives += sum_k A[a][k]: with A = dY this is the
  *                         bias gradient of the same Linear, taken from the operand tiles the kernel stages anyway
- * bias may be NULL.  Requirements: lda, ldb multiples of 8; NA multiple of 4 (epilogues 0-4). */
+ * bias may be NULL.  Requirements: lda, ldb multiples of 8; NA multiple of 4 (epilogues 0-4); epilogue 5: NA * ldc * 4 < 2^32 bytes.
+ * Operands of up to 0xFFF00000 bytes run on the LDS-DMA kernels (32-bit buffer offsets), larger ones on the register-staged kernel
+ * with 64-bit pointers; outputs and aux of any size (docs/OFFSET_RANGES.md). */
 int octmae_gemm_bf16(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
                      int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided, int b_kstrided,
                      int epilogue, int splitk, void* stream);
@@ -244,7 +246,8 @@ int octmae_layernorm_bwd_ws_floats(int M, int D);
  * bwd: dx f32 [B*S][T][D] (written densely: the LayerNorm backward of dout[b] / S, divided by T-1 on tokens 1..T-1 and exact zeros
  *      on token 0 -- or on token 0 only in cls mode); optional 16-bit copy of dx (dx_bf16, NULL = none); dgamma / dbeta / dxsum
  *      (the column sums of dx over all rows) are ACCUMULATED (+=) when non-NULL.  All reductions run in a fixed order through the
- *      caller's workspace `ws` (no atomics: results are bit-reproducible).  D % 4 == 0, D <= 2048. */
+ *      caller's workspace `ws` (no atomics: results are bit-reproducible).  D % 4 == 0, D <= 2048; B * S <= 65 535 (a grid dimension)
+ *      and B * S * T <= 2^31 - 1 (rows are counted in int), -1 otherwise. */
 int octmae_slice_pool_ws_floats(int BS, int T, int D);     /* floats `ws` must hold (forward and backward), BS = B * S */
 int octmae_slice_pool_fwd(const float* x, const float* gamma, const float* beta, float* out, float* pooled, float* mean,
                           float* rstd, float* ws, int B, int S, int T, int D, int cls, float eps, void* stream);
@@ -340,7 +343,11 @@ int octmae_image_augment(const void* src, int n, int H, int W, const octmae_aug_
  * tracking runs first and raises *flag_ws if any softmax row sum is not a finite positive number; the online-max kernel is
  * always enqueued behind it and returns immediately unless the flag is set (no host synchronisation).  In the half build
  * (octmae_lp_dtype() == 1) flag_ws is ignored and only the online-max kernel runs: the optimistic kernel's un-normalised P does not
- * fit half's range (P = e^-20 rounds to zero, e^+12 overflows) and its give-up test assumes bfloat16's exponent range. */
+ * fit half's range (P = e^-20 rounds to zero, e^+12 overflows) and its give-up test assumes bfloat16's exponent range.
+ * Address ranges (docs/OFFSET_RANGES.md): one SAMPLE's qkv rows are reached through 32-bit byte offsets, everything across samples
+ * through 64-bit pointers.  -1, before any launch: (N + 512) * 3 * H * HD * 2 >= 2^32 bytes, B or H above 65 535 (forward and the
+ * dQ / dK/dV pair: the grid's z and y), B * N >= 2^31 - 65 536 (octmae_attn_bwd_rowconst); the fused forms: the same per-sample range, B * H >= 2^23 (one workgroup of
+ * 512 threads per (b, h); a launch holds fewer than 2^32 threads), B * (N / 64 + 2) above 2^31 - 1. */
 int octmae_attn_fwd(const void* qkv, void* o, float* lse, int* flag_ws, int B, int N, int H, int HD, float scale, void* stream);
 int octmae_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, float* rowc_ws, void* dqkv, int B,
                     int N, int H, int HD, float scale, void* stream);
@@ -425,7 +432,8 @@ int octmae_scatter_add_rows(const float* src, const long long* ids_restore, floa
 int octmae_dec_assemble_bwd(const float* dx, const long long* ids_restore, float* ddpos, float* dmask_part, int B, int nkeep, int L,
                             int D, void* stream);
 /* fused patchify + per-token MSE, models_mae_joint_res_flash_attn.py:289-314, :613-650.  pred f32 [B][L+1][PD]
- * (row 0 = cls, ignored); loss_tok f32 [B][L].  frame_idx int32 [pred_t_dim] or NULL (identity). */
+ * (row 0 = cls, ignored); loss_tok f32 [B][L].  frame_idx int32 [pred_t_dim] or NULL (identity).  The B * (L + 1) token rows
+ * are counted in int: -1 beyond 2^31 - 1 (both entry points); the elements are reached through 64-bit pointers. */
 int octmae_mse_fwd(const float* pred, const float* imgs, const int* frame_idx, float* loss_tok, int B, int C, int T, int H,
                    int W, int u_sz, int p, int L, int norm_pix, void* stream);
 /* dpred bf16 [B][L+1][PD] = *coef * mask * (pred - target), cls rows zero (backward of :649-663) */

@@ -669,6 +669,7 @@ extern "C" int octmae_attn_fwd(const void* qkv, void* o, float* lse, int* flag_w
                                void* stream) {
   OCTMAE_CHECK_ARG(qkv && o && lse && B > 0 && N > 0 && H > 0);
   OCTMAE_CHECK_ARG(HD == 64 || HD == 32);
+  OCTMAE_CHECK_ARG(attn_ranges_ok(B, N, H, HD));      // 32-bit descriptor offsets per sample; B, H in the grid's z, y
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #if OCTMAE_LP_IS_F16
   // The optimistic kernel packs the un-normalised P = exp2(s) as an MFMA operand, and its give-up test assumes bfloat16's (= fp32's)
@@ -684,12 +685,15 @@ extern "C" int octmae_attn_fwd(const void* qkv, void* o, float* lse, int* flag_w
 extern "C" int octmae_attn_bwd_rowconst(const void* o, const void* dout, const float* lse, float* rowc, int B, int N, int H, int HD,
                                         void* stream) {
   OCTMAE_CHECK_ARG(o && dout && lse && rowc && B > 0 && N > 0 && H > 0 && (HD == 64 || HD == 32));
+  // run_delta walks B * N rows with an int that steps by up to 16 384 waves, over rows of H * HD elements counted in int
+  OCTMAE_CHECK_ARG((size_t)B * N < 0x7FFF0000ull && (size_t)H * HD <= 0x7FFFFFFFull);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   return HD == 64 ? run_delta<64>(BFP(o), BFP(dout), lse, rowc, B, N, H, st) : run_delta<32>(BFP(o), BFP(dout), lse, rowc, B, N, H, st);
 }
 extern "C" int octmae_attn_bwd_dq(const void* qkv, const void* dout, const float* rowc, void* dqkv, int B, int N, int H, int HD,
                                   float scale, void* stream) {
   OCTMAE_CHECK_ARG(qkv && dout && rowc && dqkv && B > 0 && N > 0 && H > 0 && (HD == 64 || HD == 32));
+  OCTMAE_CHECK_ARG(attn_ranges_ok(B, N, H, HD));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   bf16_t* d = reinterpret_cast<bf16_t*>(dqkv);
   float* rc = const_cast<float*>(rowc);   // only read on this path
@@ -698,6 +702,7 @@ extern "C" int octmae_attn_bwd_dq(const void* qkv, const void* dout, const float
 extern "C" int octmae_attn_bwd_dkv(const void* qkv, const void* dout, const float* rowc, void* dqkv, int B, int N, int H, int HD,
                                    float scale, void* stream) {
   OCTMAE_CHECK_ARG(qkv && dout && rowc && dqkv && B > 0 && N > 0 && H > 0 && (HD == 64 || HD == 32));
+  OCTMAE_CHECK_ARG(attn_ranges_ok(B, N, H, HD));
   OCTMAE_CHECK_ARG((size_t)N * 4 < 0xFFFFFFFFull);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   bf16_t* d = reinterpret_cast<bf16_t*>(dqkv);
@@ -713,6 +718,7 @@ extern "C" int octmae_attn_bwd(const void* qkv, const void* o, const void* dout,
 extern "C" int octmae_attn_bwd_dq_rowconst(const void* qkv, const void* o, const void* dout, const float* lse, float* rowc,
                                            void* dqkv, int B, int N, int H, int HD, float scale, void* stream) {
   OCTMAE_CHECK_ARG(qkv && o && dout && lse && rowc && dqkv && B > 0 && N > 0 && H > 0 && (HD == 64 || HD == 32));
+  OCTMAE_CHECK_ARG(attn_ranges_ok(B, N, H, HD));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   bf16_t* d = reinterpret_cast<bf16_t*>(dqkv);
   return HD == 64 ? run_dq<64>(BFP(qkv), BFP(dout), rowc, d, B, N, H, scale, st, BFP(o), lse)

@@ -911,7 +911,7 @@ extern "C" int octmae_attn_bwd_fused_ws_kib(int B, int N, int H, int HD) {
 extern "C" int octmae_attn_bwd_fused(const void* qkv, const void* o, const void* dout, const float* lse, void* ws, void* dqkv, int B,
                                      int N, int H, int HD, float scale, void* stream) {
   OCTMAE_CHECK_ARG(qkv && o && dout && lse && ws && dqkv && B > 0 && N > 0 && H > 0 && (HD == 64 || HD == 32));
-  OCTMAE_CHECK_ARG(((size_t)N * 3 * H * HD * 2) < 0xFFFFFFFFull);      // one sample's qkv rows within a 32-bit buffer range
+  OCTMAE_CHECK_ARG(attn_fused_ranges_ok(B, N, H, HD));      // csrc/attn_tile.hpp: the per-sample 32-bit range, the grid, the block count
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bf16_t* q = reinterpret_cast<const bf16_t*>(qkv);
   const bf16_t* oo = reinterpret_cast<const bf16_t*>(o);
@@ -926,7 +926,7 @@ extern "C" int octmae_attn_bwd_fused(const void* qkv, const void* o, const void*
 extern "C" int octmae_attn_bwd_fused_delta(const void* qkv, const void* dout, const float* lse, const float* delta, void* ws, void* dqkv, int B,
                                      int N, int H, int HD, float scale, void* stream) {
   OCTMAE_CHECK_ARG(qkv && delta && dout && lse && ws && dqkv && H <= 64 && B > 0 && N > 0 && H > 0 && (HD == 64 || HD == 32));
-  OCTMAE_CHECK_ARG(((size_t)N * 3 * H * HD * 2) < 0xFFFFFFFFull);      // one sample's qkv rows within a 32-bit buffer range
+  OCTMAE_CHECK_ARG(attn_fused_ranges_ok(B, N, H, HD));      // csrc/attn_tile.hpp: the per-sample 32-bit range, the grid, the block count
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bf16_t* q = reinterpret_cast<const bf16_t*>(qkv);
   const bf16_t* oo = nullptr;

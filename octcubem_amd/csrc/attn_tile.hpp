@@ -115,6 +115,24 @@ struct TileDma {
   }
 };
 
+// Host side: the address ranges the entry points of csrc/attn.hip must hold before they launch (docs/OFFSET_RANGES.md).  TileDma's
+// nrec, voff and tile_stride are 32-bit byte offsets from ONE sample's first row, so one sample's qkv rows -- with the tiles the rings
+// fetch past the last one (at most 3 of 64 rows behind a length padded to 128: 512 rows cover every ring depth) -- must end below
+// 2^32 bytes; the batch and head indices sit in the grid's z and y (65 535 each).  Everything that spans samples is size_t.
+inline bool attn_ranges_ok(int B, int N, int H, int HD) {
+  return ((size_t)N + 512) * 3 * (size_t)H * HD * 2 < 0xFFFFFFFFull && B <= 65535 && H <= 65535;
+}
+
+// The same for the fused backward (csrc/attn_bwd.hip, csrc/attn_bwd1w*.hip).  Its kernels fetch tiles past the last one too (the
+// software pipelines drain on the padded tile), so the per-sample range carries the same 512 rows: an offset past the sample must
+// stay past the descriptor's range, where the read is zero, not wrap into valid rows.  One workgroup of 512 threads per (b, h) sits
+// in the grid's x, and a launch of 2^32 threads or more is refused by the runtime: B * H < 2^23.  The row-constant pre-pass counts
+// its B * (NPAD / 64) <= B * (N / 64 + 2) blocks in int.
+inline bool attn_fused_ranges_ok(int B, int N, int H, int HD) {
+  return ((size_t)N + 512) * 3 * (size_t)H * HD * 2 < 0xFFFFFFFFull && (size_t)B * H < (1ull << 23) &&
+         (size_t)B * ((size_t)N / 64 + 2) <= 0x7FFFFFFFull;
+}
+
 // s_waitcnt vmcnt(CNT) lgkmcnt(0); s_barrier  -- the CNT youngest LDS-DMA loads of this wave stay in flight across the barrier
 template <int CNT>
 __device__ __forceinline__ void dma_wait_barrier() {

@@ -1298,6 +1298,8 @@ static int gemm_impl(const void* A, const void* B, void* C, void* C2, const floa
   if (!a_kstrided) OCTMAE_CHECK_ARG(K % 8 == 0); else OCTMAE_CHECK_ARG(NA % 8 == 0);
   if (!b_kstrided) OCTMAE_CHECK_ARG(K % 8 == 0); else OCTMAE_CHECK_ARG(NB % 8 == 0);
   if (epilogue != EPI_ACCUM) OCTMAE_CHECK_ARG(NA % 4 == 0 && ldc % 4 == 0);
+  // the unsplit weight-gradient epilogue reaches the fp32 accumulator [NA][ldc] through one buffer descriptor (32-bit byte offsets)
+  if (epilogue == EPI_ACCUM) OCTMAE_CHECK_ARG((size_t)NA * ldc * 4 < 0xFFFFFFFFull);
   if (epilogue == EPI_GELU) OCTMAE_CHECK_ARG(C2 != nullptr);
   if (epilogue == EPI_RESID || epilogue == EPI_DGELU) OCTMAE_CHECK_ARG(aux != nullptr && ldaux % 4 == 0);
   const GemmProblem q{NA, NB, K, lda, ldb, a_kstrided != 0, b_kstrided != 0, epilogue, splitk, C2 != nullptr, colsum_ws != nullptr};
@@ -1388,6 +1390,7 @@ extern "C" int octmae_wgrad_accum_pair(const void* dY0, const void* X0, float* g
   OCTMAE_CHECK_ARG(dY0 && X0 && gW0 && dY1 && X1 && gW1 && M > 0 && N0 > 0 && K0 > 0 && N1 > 0 && K1 > 0);
   OCTMAE_CHECK_ARG((ldy0 % 8) == 0 && (ldx0 % 8) == 0 && (ldy1 % 8) == 0 && (ldx1 % 8) == 0);
   OCTMAE_CHECK_ARG((N0 % 8) == 0 && (K0 % 8) == 0 && (N1 % 8) == 0 && (K1 % 8) == 0);
+  OCTMAE_CHECK_ARG((size_t)N0 * ldw0 * 4 < 0xFFFFFFFFull && (size_t)N1 * ldw1 * 4 < 0xFFFFFFFFull);      // as epilogue 5 of octmae_gemm_bf16
   const int N[2] = {N0, N1}, K[2] = {K0, K1}, ldy[2] = {ldy0, ldy1}, ldx[2] = {ldx0, ldx1}, ldw[2] = {ldw0, ldw1};
   const void* const dY[2] = {dY0, dY1}, * const X[2] = {X0, X1};
   float* const gW[2] = {gW0, gW1}, * const gB[2] = {gB0, gB1};

@@ -225,6 +225,8 @@ extern "C" int octmae_slice_pool_fwd(const float* x, const float* gamma, const f
   OCTMAE_CHECK_ARG(S > 0 && T > 0 && row_shape_ok(B, D) && (cls == 0 || cls == 1));
   OCTMAE_CHECK_ARG(cls == 1 || T >= 2);
   OCTMAE_CHECK_ARG((long long)B * S * T * D < (1LL << 40));
+  // B * S is the grid's y of the column-sum launch, and the rows B * S * T are counted in int (docs/OFFSET_RANGES.md)
+  OCTMAE_CHECK_ARG((long long)B * S <= 65535 && (long long)B * S * T <= 0x7FFFFFFFLL);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int BS = B * S;
   const int nc = row_nc(D);
@@ -248,6 +250,8 @@ extern "C" int octmae_slice_pool_bwd(const float* dout, const float* pooled, con
   OCTMAE_CHECK_ARG(S > 0 && T > 0 && row_shape_ok(B, D) && (cls == 0 || cls == 1));
   OCTMAE_CHECK_ARG(cls == 1 || T >= 2);
   OCTMAE_CHECK_ARG((long long)B * S * T * D < (1LL << 40));
+  // B * S is the grid's y of the column-sum launch, and the rows B * S * T are counted in int (docs/OFFSET_RANGES.md)
+  OCTMAE_CHECK_ARG((long long)B * S <= 65535 && (long long)B * S * T <= 0x7FFFFFFFLL);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int BS = B * S;
   const int M = BS * T;

@@ -626,6 +626,7 @@ extern "C" int octmae_mse_fwd(const float* pred, const float* imgs, const int* f
                               int T, int H, int W, int u_sz, int p, int L, int norm_pix, void* stream) {
   OCTMAE_CHECK_ARG(pred && imgs && loss_tok && B > 0 && L > 0);
   OCTMAE_CHECK_ARG(p % 4 == 0 && (u_sz * p * p * C) % 8 == 0 && W % 4 == 0);
+  OCTMAE_CHECK_ARG((long long)B * (L + 1LL) <= 0x7FFFFFFFLL);      // mse_kernel walks the B * (L + 1) token rows with an int
   hipLaunchKernelGGL(mse_kernel<0>, dim3(grid_for((size_t)B * L, 4, 4096)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      pred, imgs, frame_idx, loss_tok /*mask unused: any valid pointer*/, nullptr, loss_tok, nullptr, B, C, T, H,
                      W, u_sz, p, L, norm_pix);
@@ -638,6 +639,7 @@ extern "C" int octmae_mse_bwd(const float* pred, const float* imgs, const int* f
                               int norm_pix, void* stream) {
   OCTMAE_CHECK_ARG(pred && imgs && mask && coef && dpred_bf16 && B > 0 && L > 0);
   OCTMAE_CHECK_ARG(p % 4 == 0 && (u_sz * p * p * C) % 8 == 0 && W % 4 == 0);
+  OCTMAE_CHECK_ARG((long long)B * (L + 1LL) <= 0x7FFFFFFFLL);      // mse_kernel walks the B * (L + 1) token rows with an int
   hipLaunchKernelGGL(mse_kernel<1>, dim3(grid_for((size_t)B * (L + 1), 4, 4096)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), pred, imgs, frame_idx, mask, coef, nullptr,
                      reinterpret_cast<bf16_t*>(dpred_bf16), B, C, T, H, W, u_sz, p, L, norm_pix);
