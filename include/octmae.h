@@ -67,8 +67,11 @@ extern "C" {
  * 33: octmae_bootstrap_rank_metrics (bootstrap resamples of AUROC / average precision / AUPRC / best F1 from one sort and a weighted
  *     prefix walk per resample, csrc/bootstrap.hip).
  * 34: octmae_unit_moments, octmae_bootstrap_moments (+ octmae_bootstrap_moments_ws): bootstrap resamples of the regression metrics as
- *     one int32 x f64 matrix product on v_mfma_f64_16x16x4_f64, in a fixed summation order (csrc/bootmoments.hip). */
-#define OCTMAE_ABI_VERSION 34
+ *     one int32 x f64 matrix product on v_mfma_f64_16x16x4_f64, in a fixed summation order (csrc/bootmoments.hip).
+ * 35: deterministic mode ("deterministic" of octmae_set_option, octmae_deterministic): k-split weight gradients through slabs and
+ *     octmae_wgrad_fold's kernel instead of fp32 atomics (octmae_wgrad_accum_pair_ws, octmae_wgrad_det_ws_bytes, octmae_gemm_plan_ws,
+ *     octmae_wgrad_pair_plan_ws), the gradient norm through per-chunk partials (octmae_mt_sumsq_ws, octmae_mt_adamw_fused_ws). */
+#define OCTMAE_ABI_VERSION 35
 int octmae_abi_version(void);
 
 /* The 16-bit operand type this library was built for: 0 = bfloat16 (liboctmae.so, the shipped build; BASELINE's headline type),
@@ -98,8 +101,19 @@ int octmae_lp_dtype(void);
  *                          through a buffer descriptor, 1 the fp32 atomics of a split launch, 0 one guarded load + store per register
  *   "wgrad_stagger"        v >= 0 (default 29): split-K weight gradients of >= 8 slices with <= 96 k-tiles each run with slice
  *                          lengths rising by v / 256 k-tiles per output tile of the launch from one slice to the next, so that the
- *                          slices' fp32-atomic epilogues follow one another instead of colliding; 0: equal slices */
+ *                          slices' fp32-atomic epilogues follow one another instead of colliding; 0: equal slices
+ *   "deterministic"        0 (default) / 1: DETERMINISTIC MODE -- no float of a training step is added in the order workgroups happen
+ *                          to finish.  The environment variable OCTMAE_DETERMINISTIC, read once per process, wins.  Under it
+ *                          (csrc/gemm_plan.hpp): a weight gradient (epilogue 5, octmae_wgrad_accum_pair[_ws]) with S > 1 k slices stores
+ *                          slice z as slab z of the lent workspace (fp32 [S][NA][NB], plain stores, need not be initialised: the
+ *                          split_ws of octmae_gemm_bf16_ws, whose counters are not touched) and one more launch folds
+ *                          gW = (...((gW + P_0) + P_1) ... + P_{S-1}) -- what S unsplit launches over the slices' rows, in order, leave;
+ *                          S is the split of the default mode capped to the slabs that fit (1 without a workspace: never atomics),
+ *                          the slices are equal (no stagger); the bias gradient of a weight gradient is octmae_colsum_accum over dY
+ *                          before the GEMM, that of epilogue 4 the per-slab workspace or octmae_colsum_accum over the output;
+ *                          octmae_mt_sumsq_ws / octmae_mt_adamw_fused_ws leave one partial per chunk and add them in chunk order. */
 int octmae_set_option(const char* key, int value);
+int octmae_deterministic(void);         /* the mode as the library sees it (the environment variable included): 0 / 1 */
 
 /* ---- GEMM with fused epilogues ------------------------------------------------------------------
  * X[a][b] = sum_k A[a][k] * B[b][k],  A has NA rows, B has NB rows, reduction length K.
@@ -157,6 +171,10 @@ int octmae_gemm_small_plan(int NA, int NB, int K, int cus, int have_ws, int big_
  *   2 per-slab rows + a folding launch, 3 / 4 a separate octmae_colsum_accum launch before / after the GEMM.
  * splitk as in octmae_gemm_bf16 (kinds 5 / 6: 0 = chosen by the planner, so that the answer is what a weight gradient launches). */
 int octmae_gemm_plan(int kind, int NA, int NB, int K, int lda, int ldb, int variant, int splitk, int have_ws, int cus, int* out);
+/* The same with the SIZE of the lent workspace (have_ws = ws_bytes >= octmae_gemm_split_ws_kib() KiB): in deterministic mode the k split of
+ * kinds 5 / 6 is capped to the slabs that fit into ws_bytes (at most the workspace's 64 MiB in front of its counters), and
+ * out[8] == 3 says that the launch stores slabs and is followed by the fold (out[7] == 0 and out[12] != 1 there). */
+int octmae_gemm_plan_ws(int kind, int NA, int NB, int K, int lda, int ldb, int variant, int splitk, long long ws_bytes, int cus, int* out);
 int octmae_gemm_bf16_ws(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux,
                         int NA, int NB, int K, int lda, int ldb, int ldc, int ldaux, int a_kstrided, int b_kstrided,
                         int epilogue, int splitk, void* split_ws, long long split_ws_bytes, void* stream);
@@ -187,18 +205,39 @@ int octmae_linear_dgrad_dgelu(const void* W, const void* dY, void* dX, const voi
 int octmae_wgrad_accum_pair(const void* dY0, const void* X0, float* gW0, float* gB0, int N0, int K0, int ldy0, int ldx0, int ldw0,
                             const void* dY1, const void* X1, float* gW1, float* gB1, int N1, int K1, int ldy1, int ldx1, int ldw1,
                             int M, int splitk, void* stream);
+/* The same with a workspace lent for the call: in deterministic mode the slabs of a k-split pair live there (those of gW0, then those
+ * of gW1, behind the column-sum rows; octmae_wgrad_det_ws_bytes) and one fold launch serves both outputs; without one (or through the entry point above) the pair
+ * runs unsplit there.  The split-K workspace of octmae_gemm_bf16_ws serves: only the bytes in front of its counters are written.
+ * Outside deterministic mode the workspace is not looked at. */
+int octmae_wgrad_accum_pair_ws(const void* dY0, const void* X0, float* gW0, float* gB0, int N0, int K0, int ldy0, int ldx0, int ldw0,
+                               const void* dY1, const void* X1, float* gW1, float* gB1, int N1, int K1, int ldy1, int ldx1, int ldw1,
+                               int M, int splitk, void* split_ws, long long split_ws_bytes, void* stream);
+/* host side only: *bytes = the workspace to lend so that a weight gradient [N0][K0] over M rows (and its partner [N1][K1] of a pair;
+ * 0, 0: a single launch) runs `slices` k slices in deterministic mode: the slabs (none for one slice) behind the head of the workspace,
+ * which holds the rows of the bias gradient's fixed-order column sums (octmae_colsum_ws_rows(M) x N floats, rounded up to 256 bytes:
+ * for a single launch when want_bias is set, for a pair always and for its wider dY).  With less lent the planner runs fewer slices,
+ * and column sums whose rows do not fit take the form that needs no workspace; the plan queries report what runs. */
+int octmae_wgrad_det_ws_bytes(int N0, int K0, int N1, int K1, int M, int want_bias, int slices, long long* bytes);
+/* The fold of deterministic mode on its own: gW fp32 [NA][ldc] <- (...((gW + P_0) + P_1) ... + P_{S-1}) over [NA][NB], P_z = slabs +
+ * z * slab_stride, fp32 [NA][ld_slab]; nothing outside [NA][NB] is read or written.  16-byte accesses when NB, ldc, ld_slab, slab_stride
+ * are multiples of 4 and both pointers 16-byte aligned, element by element otherwise; any size (docs/OFFSET_RANGES.md). */
+int octmae_wgrad_fold(float* gW, const float* slabs, int S, int NA, int NB, int ldc, int ld_slab, long long slab_stride, void* stream);
 
 /* Planning arithmetic of the split-K weight gradients, host side only (no GPU is touched; for tests): the number of k slices a launch of
  * `tiles` output tiles over M token rows uses for a requested splitk (-> *slices), the first 64-row k-tile of every slice
  * (bounds[0 .. *slices], bounds[*slices] = ceil(M / 64); room for splitk + 1 ints), and -- the return value -- the length step between
  * neighbouring slices in 1/256 k-tiles (0 = equal slices; see "wgrad_stagger" above).  Negative: argument error. */
 int octmae_wgrad_split_plan(int M, int splitk, int tiles, int* slices, int* bounds);
+/* (in deterministic mode the slices are equal: ask with splitk = the k slices a plan query reports to get the bounds its launch runs) */
 /* The launch plan of octmae_wgrad_accum_pair (csrc/gemm_plan.hpp: plan_wgrad_pair, with the 128- against 256-tile cost model), host side
  * only.  Returns 0 and writes 14 ints, or -2 as the entry point does:  out[0] kernel family (2: gemm256p_wgrad_pair_kernel,
  * 3: gemm128d_wgrad_kernel)  [1] workgroups  [2] k slices  [3] k-tiles per slice  [4] kstagger  [5] atomic1  [6] ring depth (family 3)
  * [7] bias-gradient route (1 inside the kernel, 3 a launch of its own before)  [8..10] / [11..13] tiles_a, tiles_b, cgroup of each problem.
  * splitk = 0: chosen by the planner, as in the entry point. */
 int octmae_wgrad_pair_plan(int N0, int K0, int ldy0, int ldx0, int N1, int K1, int ldy1, int ldx1, int M, int splitk, int cus, int* out);
+/* the plan of octmae_wgrad_accum_pair_ws with ws_bytes lent (the query above: none); out[5] == 3: slabs + the fold, as octmae_gemm_plan_ws */
+int octmae_wgrad_pair_plan_ws(int N0, int K0, int ldy0, int ldx0, int N1, int K1, int ldy1, int ldx1, int M, int splitk,
+                              long long ws_bytes, int cus, int* out);
 
 /* The proj dgrad of an attention block together with the attention backward's per-query constant delta (flash-attn's `dsoftmax_sum`,
  * the backward of video_vit.py:130-134 under autograd):
@@ -856,6 +895,17 @@ int octmae_mt_adamw(const void* tensor_table, const int* chunk_tensor, const lon
 int octmae_mt_adamw_fused(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,
                           const float* gscale, void* const* lp_table, float* sumsq, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, void* stream);
+/* octmae_mt_sumsq / octmae_mt_adamw_fused with a workspace for deterministic mode ("deterministic" above): partial = fp32 [nchunks],
+ * lent for the call, need not be initialised.  Under the mode every chunk stores the sum it would have added atomically -- the bits a
+ * one-chunk tensor gets today -- as partial[chunk], and a finish launch computes sumsq[t] = (...((sumsq[t] + partial[c0]) +
+ * partial[c0 + 1]) ...) over the chunks of tensor t in ascending order; the chunks of a tensor must be consecutive in the table.  There a
+ * call without `partial` -- the two entry points above, when a sumsq is asked for -- is refused with -1: the mode never falls back to adding
+ * in finishing order.  Outside the mode `partial` is not looked at. */
+int octmae_mt_sumsq_ws(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks, float* sumsq,
+                       float* partial, void* stream);
+int octmae_mt_adamw_fused_ws(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,
+                             const float* gscale, void* const* lp_table, float* sumsq, float* partial, float lr, float beta1, float beta2,
+                             float eps, float weight_decay, int step, void* stream);
 
 /* ---- data-parallel exchange over RCCL (xGMI) -----------------------------------------------------------
  * What the reference gets from torch.distributed's NCCL backend on this path:

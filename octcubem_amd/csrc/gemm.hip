@@ -151,6 +151,8 @@ __device__ __forceinline__ bf16x8 read_frag(const char* lds, int rb, int s, int 
 
 // Epilogue shared by both tile shapes.  acc[i][j] is the 32x32 block at rows a_base + 32 i, columns b_base + 32 j
 // of X[a][b]; register 4g+e of a lane (r = lane&31, h = lane>>5) is X[a_base + 32 i + 8g + 4h + e][b_base + 32 j + r].
+// EPI_ACCUM_SLAB (deterministic mode, a k-split weight gradient): C is the slice's slab, fp32 [NA][ldc], and receives X itself by plain
+// stores -- nothing is read and nothing is added here (wgrad_fold_kernel adds the slabs to the gradient in slice order).
 template <int EPI, bool OUT_AB, int MI, int NJ>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)[MI][NJ], int a_base, int b_base, int lane,
                                               bool atomic) {
@@ -219,7 +221,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
     // C[a][b] += X[a][b]: one register across a half-wave is 32 consecutive b of one row a: two 128-B row segments per
     // wave instruction (the full-rate fp32 atomic shape).
     float* C = reinterpret_cast<float*>(p.C);
-    if (!atomic && p.atomic1 == 2) {
+    if (EPI != EPI_ACCUM_SLAB && !atomic && p.atomic1 == 2) {
       // unsplit launch, plain read-modify-write in batches of 16 registers through a buffer descriptor: out-of-range elements are
       // clipped by the offset (no branches), 16 loads are in flight before the first add (the guarded form below makes one
       // dependent round trip per register: 35 us of a 75 us launch at 21 k-tiles, tools/gemm_small_fit.py)
@@ -254,13 +256,22 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
           const int a = a_base + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
           if (a < p.NA && b < p.NB) {
             float* dst = C + (size_t)a * p.ldc + b;
-            if (atomic) unsafeAtomicAdd(dst, acc[i][j][g]);
+            if (EPI == EPI_ACCUM_SLAB) *dst = acc[i][j][g];
+            else if (atomic) unsafeAtomicAdd(dst, acc[i][j][g]);
             else *dst += acc[i][j][g];
           }
         }
       }
     }
   }
+}
+
+// params of slice kz of a deterministic k-split weight gradient: C = slab kz of the workspace p.C points to, fp32 [NA][NB] packed
+__device__ __forceinline__ GemmParams slab_params(const GemmParams& p, int kz) {
+  GemmParams q = p;
+  q.C = reinterpret_cast<float*>(p.C) + (size_t)kz * ((size_t)p.NA * p.NB);
+  q.ldc = p.NB;
+  return q;
 }
 
 template <bool A_KS, bool B_KS, int EPI, bool OUT_AB>
@@ -331,7 +342,11 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmParams p) {
     }
   }
 
-  gemm_epilogue<EPI, OUT_AB, 2, 2>(p, acc, a0 + wa * 64, b0 + wb * 64, lane, gridDim.z > 1);
+  if constexpr (EPI == EPI_ACCUM_SLAB) {     // slice blockIdx.z of a deterministic k-split weight gradient, into its slab
+    gemm_epilogue<EPI, OUT_AB, 2, 2>(slab_params(p, (int)blockIdx.z), acc, a0 + wa * 64, b0 + wb * 64, lane, false);
+  } else {
+    gemm_epilogue<EPI, OUT_AB, 2, 2>(p, acc, a0 + wa * 64, b0 + wb * 64, lane, gridDim.z > 1);
+  }
 }
 
 // =====================================================================================================
@@ -758,7 +773,8 @@ __device__ __forceinline__ void glds16(const gi32x4& rsrc, unsigned lds_addr, un
 #pragma clang diagnostic pop
 }
 
-// the tile body: tile t of p, k-tiles kt0 .. kt1 - 1   (smem: [stage 2][operand 2][half 2] x 16 KiB); partial = split-K (atomics)
+// the tile body: tile t of p, k-tiles kt0 .. kt1 - 1   (smem: [stage 2][operand 2][half 2] x 16 KiB); partial = split-K (atomics);
+// EPI_ACCUM_SLAB: p is slab_params() of the slice (plain stores into its slab, `partial` is not looked at)
 template <bool A_KS, bool B_KS, int EPI, bool OUT_AB>
 __device__ __forceinline__ void gemm256p_body(const GemmParams& p, const int t, const int kt0, const int kt1, const bool partial,
                                               char* smem) {
@@ -950,6 +966,16 @@ __global__ __launch_bounds__(512, 1) void gemm256p_kernel(const GemmParams p) {
   split_range(p, kz, (int)gridDim.z, kt0, kt1);
   gemm256p_body<A_KS, B_KS, EPI, OUT_AB>(p, t, kt0, kt1, gridDim.z > 1 || p.atomic1 == 1, smem);
 }
+// the weight gradient of a deterministic k-split launch: the same tile order and k slices, slice kz into slab kz
+__global__ __launch_bounds__(512, 1) void gemm256p_wgrad_slab_kernel(const GemmParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nt = p.tiles_a * p.tiles_b;
+  const int L = xcd_remap((int)(blockIdx.x + nt * blockIdx.z), nt * (int)gridDim.z);
+  const int kz = L / nt, t = L - kz * nt;
+  int kt0, kt1;
+  split_range(p, kz, (int)gridDim.z, kt0, kt1);
+  gemm256p_body<true, true, EPI_ACCUM_SLAB, true>(slab_params(p, kz), t, kt0, kt1, false, smem);
+}
 
 
 // Two weight gradients with the same reduction length (the same token rows) in ONE launch: the tiles of both share the split, so the
@@ -975,6 +1001,21 @@ __global__ __launch_bounds__(512, 1) void gemm256p_wgrad_pair_kernel(const GemmP
     split_range(pp.p1, kz, pp.S, kt0, kt1);
     gemm256p_body<true, true, EPI_ACCUM, true>(pp.p1, t, kt0, kt1, pp.S > 1 || pp.p1.atomic1 == 1, smem);
   }
+}
+// The pair in deterministic mode, pp.S > 1: p0.C / p1.C are the two outputs' slab arrays (slab_params).  The kernel above keeps its
+// text -- its generated code is compared with the release's -- so this is a kernel of its own with the same tile and slice order.
+__global__ __launch_bounds__(512, 1) void gemm256p_wgrad_pair_slab_kernel(const GemmPair pp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nt = pp.nt0 + pp.nt1;
+  const int L = xcd_remap((int)blockIdx.x, nt * pp.S);
+  const int kz = L / nt;
+  int t = L - kz * nt;
+  const bool second = t >= pp.nt0;                              // workgroup-uniform
+  if (second) t -= pp.nt0;
+  const GemmParams& p = second ? pp.p1 : pp.p0;
+  int kt0, kt1;
+  split_range(p, kz, pp.S, kt0, kt1);
+  gemm256p_body<true, true, EPI_ACCUM_SLAB, true>(slab_params(p, kz), t, kt0, kt1, false, smem);
 }
 
 
@@ -1183,9 +1224,8 @@ __global__ __launch_bounds__(256, NST == 2 ? 2 : 1) void gemm128d_kernel(const G
 // both operands k-strided, the fp32-accumulating OUT_AB epilogue (atomics when the k range is split, batched read-modify-write
 // otherwise).  One volume per step gives the fc1 + fc2 pair 128 tiles of 256 x 256 over 21 k-tiles: half the CUs for 40 us; here
 // 512 workgroups of a quarter the work, two per CU.  The bias gradient (column sums of dY) is a separate launch on this path.
-template <int NST>
-__global__ __launch_bounds__(256, NST == 2 ? 2 : 1) void gemm128d_wgrad_kernel(const GemmPair pp) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+template <int NST, bool SLAB>
+__device__ __forceinline__ void gemm128d_wgrad_body(const GemmPair& pp, char* smem) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wa = wid >> 1, wb = wid & 1;
@@ -1199,10 +1239,68 @@ __global__ __launch_bounds__(256, NST == 2 ? 2 : 1) void gemm128d_wgrad_kernel(c
   int a0, b0;
   if (!second) {
     gemm128d_mainloop<true, true, NST>(pp.p0, t, kz, pp.S, smem, acc, a0, b0);
-    gemm_epilogue<EPI_ACCUM, true, 2, 2>(pp.p0, acc, a0 + wa * 64, b0 + wb * 64, lane, pp.S > 1 || pp.p0.atomic1 == 1);
+    if (SLAB) gemm_epilogue<EPI_ACCUM_SLAB, true, 2, 2>(slab_params(pp.p0, kz), acc, a0 + wa * 64, b0 + wb * 64, lane, false);
+    else gemm_epilogue<EPI_ACCUM, true, 2, 2>(pp.p0, acc, a0 + wa * 64, b0 + wb * 64, lane, pp.S > 1 || pp.p0.atomic1 == 1);
   } else {
     gemm128d_mainloop<true, true, NST>(pp.p1, t, kz, pp.S, smem, acc, a0, b0);
-    gemm_epilogue<EPI_ACCUM, true, 2, 2>(pp.p1, acc, a0 + wa * 64, b0 + wb * 64, lane, pp.S > 1 || pp.p1.atomic1 == 1);
+    if (SLAB) gemm_epilogue<EPI_ACCUM_SLAB, true, 2, 2>(slab_params(pp.p1, kz), acc, a0 + wa * 64, b0 + wb * 64, lane, false);
+    else gemm_epilogue<EPI_ACCUM, true, 2, 2>(pp.p1, acc, a0 + wa * 64, b0 + wb * 64, lane, pp.S > 1 || pp.p1.atomic1 == 1);
+  }
+}
+template <int NST>
+__global__ __launch_bounds__(256, NST == 2 ? 2 : 1) void gemm128d_wgrad_kernel(const GemmPair pp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemm128d_wgrad_body<NST, false>(pp, smem);
+}
+template <int NST>
+__global__ __launch_bounds__(256, NST == 2 ? 2 : 1) void gemm128d_wgrad_slab_kernel(const GemmPair pp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemm128d_wgrad_body<NST, true>(pp, smem);
+}
+
+// ---- the fold of a deterministic k-split weight gradient ---------------------------------------------------------------------------
+// gW[a][b] = (...((gW[a][b] + P_0[a][b]) + P_1[a][b]) ... + P_{S-1}[a][b]) for one or two outputs (a pair) in one launch: slices in
+// ascending order onto the value that was there, each element by exactly one thread -- no float is added in finishing order.
+// Bandwidth-bound: (S + 2) x 4 bytes per element.  VEC: 16-byte loads and stores over groups of 4 columns (every row start of gW and
+// of the slabs 16-byte aligned, NB % 4 == 0); otherwise element by element.  Grid-stride loop over the groups of both outputs, 64-bit
+// offsets throughout (docs/GRID_CAPS.md, docs/OFFSET_RANGES.md).
+struct FoldOne {
+  float* gW;              // [NA][ldc]
+  const float* slabs;     // [S] x (slab_stride floats), each [NA][ld_slab]
+  long long slab_stride;
+  int NA, NB, ldc, ld_slab;
+};
+struct FoldArgs {
+  FoldOne o[2];
+  long long groups0, groups;      // work items of o[0] / of both (VEC: groups of 4 columns; else elements)
+  int S;
+};
+constexpr int FOLD_MAX_BLOCKS = 2048;
+template <bool VEC>
+__global__ __launch_bounds__(256) void wgrad_fold_kernel(const FoldArgs f) {
+  const long long step = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < f.groups; i += step) {
+    const bool second = i >= f.groups0;
+    const FoldOne& o = second ? f.o[1] : f.o[0];
+    const long long g = second ? i - f.groups0 : i;
+    const int per_row = VEC ? o.NB >> 2 : o.NB;
+    const long long a = g / per_row;
+    const int b = (int)(g - a * per_row) * (VEC ? 4 : 1);
+    float* dst = o.gW + a * o.ldc + b;
+    const float* src = o.slabs + a * o.ld_slab + b;
+    if (VEC) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(dst);
+#pragma unroll 4
+      for (int z = 0; z < f.S; ++z) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(src + z * o.slab_stride);
+        v[0] += x[0]; v[1] += x[1]; v[2] += x[2]; v[3] += x[3];
+      }
+      *reinterpret_cast<f32x4*>(dst) = v;
+    } else {
+      float v = *dst;
+      for (int z = 0; z < f.S; ++z) v += src[z * o.slab_stride];
+      *dst = v;
+    }
   }
 }
 
@@ -1213,6 +1311,7 @@ std::atomic<int> g_wgrad_stagger{29};      // "wgrad_stagger" / OCTMAE_WGRAD_STA
 // 2 = read-modify-write in batches of 16 registers through a buffer descriptor.  "wgrad_s1_atomic" / OCTMAE_WGRAD_S1_ATOMIC.
 std::atomic<int> g_wgrad_s1_atomic{2};
 std::atomic<int> g_gemm_small{1};          // octmae_set_option("gemm_small", 0 / 1); OCTMAE_GEMM_SMALL overrides
+std::atomic<int> g_deterministic{0};       // octmae_set_option("deterministic", 0 / 1); OCTMAE_DETERMINISTIC overrides (gemm_plan.hpp)
 std::atomic<int> g_small_launches{0};      // how many launches took gemm128d_kernel ("gemm_small_launches": tests)
 std::atomic<int> g_small_split_launches{0};   // ... with a k split
 std::atomic<int> g_small_wgrad_launches{0};   // weight-gradient pairs that took gemm128d_wgrad_kernel ("gemm_small_wgrad_launches")
@@ -1269,10 +1368,46 @@ static int launch128d(const GemmParams& p, const GemmPlan& pl, void* ws, hipStre
   return rc;
 }
 
+// wgrad_fold_kernel over the slabs of one output (n = 1) or of a pair (n = 2): gW_i fp32 [NA_i][ldc_i] += the S slabs of
+// slab_stride_i floats each, rows of ld_slab_i floats, in ascending order
+static int launch_fold(int n, float* const gW[], const float* const slabs[], const long long slab_stride[], const int NA[], const int NB[],
+                       const int ldc[], const int ld_slab[], int S, hipStream_t st) {
+  FoldArgs f{};
+  bool vec = true;
+  for (int i = 0; i < n; ++i) {
+    f.o[i] = FoldOne{gW[i], slabs[i], slab_stride[i], NA[i], NB[i], ldc[i], ld_slab[i]};
+    vec = vec && (NB[i] % 4) == 0 && (ldc[i] % 4) == 0 && (ld_slab[i] % 4) == 0 && (slab_stride[i] % 4) == 0 &&
+          ((reinterpret_cast<uintptr_t>(gW[i]) | reinterpret_cast<uintptr_t>(slabs[i])) & 15) == 0;
+  }
+  const long long g0 = (long long)NA[0] * (vec ? NB[0] / 4 : NB[0]);
+  const long long g1 = n > 1 ? (long long)NA[1] * (vec ? NB[1] / 4 : NB[1]) : 0;
+  f.groups0 = g0; f.groups = g0 + g1; f.S = S;
+  const long long blocks = (f.groups + 255) / 256;
+  const dim3 grid((unsigned)(blocks < FOLD_MAX_BLOCKS ? blocks : FOLD_MAX_BLOCKS));
+  if (vec) hipLaunchKernelGGL(wgrad_fold_kernel<true>, grid, dim3(256), 0, st, f);
+  else hipLaunchKernelGGL(wgrad_fold_kernel<false>, grid, dim3(256), 0, st, f);
+  OCTMAE_LAUNCH_CHECK();
+  return 0;
+}
+
 // the kernel family the plan names, for one layout / epilogue combination
 template <bool A_KS, bool B_KS, int EPI, bool OUT_AB>
 static int launch_plan(const GemmParams& p, const GemmPlan& pl, void* split_ws, hipStream_t st) {
   const dim3 grid(pl.tiles_a * pl.tiles_b, 1, pl.slices);
+  if constexpr (EPI == EPI_ACCUM) {
+    if (pl.atomic1 == ATOMIC1_SLABS) {      // deterministic mode: slice z into slab z of the workspace, then the fold (p.C is gW)
+      GemmParams q = p;
+      q.C = split_ws; q.C2 = nullptr;
+      int rc = PLAN_FALLBACK;
+      if (pl.kernel == GemmKernel::Tile128) rc = launch_dyn<gemm_kernel<true, true, EPI_ACCUM_SLAB, true>>(grid, 256, 4 * TILE_BYTES, st, q);
+      if (pl.kernel == GemmKernel::Phased256) rc = launch_dyn<gemm256p_wgrad_slab_kernel>(grid, 512, 4 * TILE2_BYTES, st, q);
+      if (rc != 0) return rc;
+      float* const gW[1] = {reinterpret_cast<float*>(p.C)};
+      const float* const slabs[1] = {reinterpret_cast<const float*>(split_ws)};
+      const long long stride[1] = {(long long)p.NA * p.NB};
+      return launch_fold(1, gW, slabs, stride, &p.NA, &p.NB, &p.ldc, &p.NB, pl.slices, st);
+    }
+  }
   switch (pl.kernel) {
     case GemmKernel::Tile128: return launch_dyn<gemm_kernel<A_KS, B_KS, EPI, OUT_AB>>(grid, 256, 4 * TILE_BYTES, st, p);
     case GemmKernel::TwoStage256: return launch_dyn<gemm256_kernel<A_KS, B_KS, EPI, OUT_AB>>(grid, 512, 4 * TILE2_BYTES, st, p);
@@ -1286,6 +1421,22 @@ static int launch_plan(const GemmParams& p, const GemmPlan& pl, void* split_ws, 
 }  // namespace octmae
 using namespace octmae;
 extern "C" int octmae_colsum_accum(const void* in, int in_is_bf16, float* out, int M, int N, int ld, void* stream);
+extern "C" int octmae_colsum_ws_rows(int M);
+extern "C" int octmae_colsum_accum_ws(const void* in, int in_is_bf16, float* out, float* ws, int M, int N, int ld, void* stream);
+
+// Deterministic mode: the bias gradient of a weight gradient is a pass over dY [M][N] before the GEMM.  Where the rows are many that
+// pass splits them over workgroups and folds the splits' rows in order (octmae_colsum_accum_ws); its workspace is the HEAD of the lent
+// one, `det_colsum_bytes` bytes (0: none wanted, M short enough for one split, or it does not fit -- then the column-owning form of
+// octmae_colsum_accum, fixed order as well), and the slabs of the k slices follow it.
+static long long det_colsum_bytes(bool wanted, int M, int N, long long usable) {
+  if (!wanted) return 0;
+  const long long b = ((long long)octmae_colsum_ws_rows(M) * N * 4 + 255) / 256 * 256;
+  return b <= usable ? b : 0;
+}
+static int det_colsum(const void* dY, float* gB, void* ws, long long cs_bytes, int M, int N, int ld, void* stream) {
+  return cs_bytes > 0 ? octmae_colsum_accum_ws(dY, 1, gB, reinterpret_cast<float*>(ws), M, N, ld, stream)
+                      : octmae_colsum_accum(dY, 1, gB, M, N, ld, stream);
+}
 
 // C[b][a] (+epilogue) = sum_k A[a][k] B[b][k];  see include/octmae.h for the contract.
 static int gemm_impl(const void* A, const void* B, void* C, void* C2, const float* bias, const void* aux, int NA, int NB, int K, int lda,
@@ -1302,8 +1453,13 @@ static int gemm_impl(const void* A, const void* B, void* C, void* C2, const floa
   if (epilogue == EPI_ACCUM) OCTMAE_CHECK_ARG((size_t)NA * ldc * 4 < 0xFFFFFFFFull);
   if (epilogue == EPI_GELU) OCTMAE_CHECK_ARG(C2 != nullptr);
   if (epilogue == EPI_RESID || epilogue == EPI_DGELU) OCTMAE_CHECK_ARG(aux != nullptr && ldaux % 4 == 0);
-  const GemmProblem q{NA, NB, K, lda, ldb, a_kstrided != 0, b_kstrided != 0, epilogue, splitk, C2 != nullptr, colsum_ws != nullptr};
-  const GemmPlan pl = plan_gemm(q, v, current_options(), device_cus, split_ws != nullptr && split_bytes >= d_ws_bytes());
+  const GemmOptions opt = current_options();
+  const bool det_wgrad = opt.deterministic && epilogue == EPI_ACCUM;
+  const long long usable = det_wgrad ? det_usable_ws(split_ws ? split_bytes : 0) : 0;
+  const long long cs_bytes = det_wgrad ? det_colsum_bytes(C2 != nullptr, K, NA, usable) : 0;
+  const GemmProblem q{NA, NB, K, lda, ldb, a_kstrided != 0, b_kstrided != 0, epilogue, splitk, C2 != nullptr, colsum_ws != nullptr,
+                      usable - cs_bytes};
+  const GemmPlan pl = plan_gemm(q, v, opt, device_cus, split_ws != nullptr && split_bytes >= d_ws_bytes());
   if (pl.status != 0) return pl.status;
   GemmParams p = make_params(A, B, C, C2, aux, NA, NB, K, lda, ldb, ldc, ldaux);
   p.bias = bias; p.rowscale = rowscale; p.rows_per_scale = rows_per_scale > 0 ? rows_per_scale : 1;
@@ -1313,11 +1469,14 @@ static int gemm_impl(const void* A, const void* B, void* C, void* C2, const floa
   float* const colsum = pl.colsum != Colsum::None ? reinterpret_cast<float*>(C2) : nullptr;
   if (pl.colsum == Colsum::FoldWs) { p.C2 = colsum_ws; p.ldc2 = NA; }
   if (pl.colsum == Colsum::PassBefore || pl.colsum == Colsum::PassAfter) p.C2 = nullptr;
-  if (pl.colsum == Colsum::PassBefore) { if (int rc = octmae_colsum_accum(A, 1, colsum, K, NA, lda, stream)) return rc; }
+  if (pl.colsum == Colsum::PassBefore) {
+    if (int rc = det_wgrad ? det_colsum(A, colsum, split_ws, cs_bytes, K, NA, lda, stream) : octmae_colsum_accum(A, 1, colsum, K, NA, lda, stream)) return rc;
+  }
+  void* const lent = det_wgrad && split_ws ? reinterpret_cast<char*>(split_ws) + cs_bytes : split_ws;      // deterministic wgrad: the slabs
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int rc = PLAN_FALLBACK;
 #define OCTMAE_GEMM_CASE(AKS, BKS, E, AB) \
-  if (q.a_ks == AKS && q.b_ks == BKS && epilogue == E) rc = launch_plan<AKS, BKS, E, AB>(p, pl, split_ws, st);
+  if (q.a_ks == AKS && q.b_ks == BKS && epilogue == E) rc = launch_plan<AKS, BKS, E, AB>(p, pl, lent, st);
   OCTMAE_GEMM_CASE(0, 0, EPI_BF16, false)      // forward linears (nn.Linear layout both sides)
   OCTMAE_GEMM_CASE(0, 0, EPI_F32, false)
   OCTMAE_GEMM_CASE(0, 0, EPI_GELU, false)
@@ -1384,9 +1543,10 @@ extern "C" int octmae_linear_dgrad_delta(const void* W, const void* dY, void* dX
 // gW0[N0][K0] += dY0[M][N0]^T X0[M][K0]  and  gW1[N1][K1] += dY1[M][N1]^T X1[M][K1]  (gB: fp32 [N] += column sums of dY, or NULL) in
 // one launch of gemm256p_wgrad_pair_kernel or gemm128d_wgrad_kernel (plan_wgrad_pair).  Returns -2 when either problem does not take
 // the 256-tile kernel (the caller then issues two octmae_gemm_bf16 calls).
-extern "C" int octmae_wgrad_accum_pair(const void* dY0, const void* X0, float* gW0, float* gB0, int N0, int K0, int ldy0, int ldx0, int ldw0,
-                                       const void* dY1, const void* X1, float* gW1, float* gB1, int N1, int K1, int ldy1, int ldx1, int ldw1,
-                                       int M, int splitk, void* stream) {
+// _ws: with a workspace lent for the slabs of deterministic mode (read only there; the split-K workspace of octmae_gemm_bf16_ws serves)
+extern "C" int octmae_wgrad_accum_pair_ws(const void* dY0, const void* X0, float* gW0, float* gB0, int N0, int K0, int ldy0, int ldx0, int ldw0,
+                                          const void* dY1, const void* X1, float* gW1, float* gB1, int N1, int K1, int ldy1, int ldx1, int ldw1,
+                                          int M, int splitk, void* split_ws, long long split_ws_bytes, void* stream) {
   OCTMAE_CHECK_ARG(dY0 && X0 && gW0 && dY1 && X1 && gW1 && M > 0 && N0 > 0 && K0 > 0 && N1 > 0 && K1 > 0);
   OCTMAE_CHECK_ARG((ldy0 % 8) == 0 && (ldx0 % 8) == 0 && (ldy1 % 8) == 0 && (ldx1 % 8) == 0);
   OCTMAE_CHECK_ARG((N0 % 8) == 0 && (K0 % 8) == 0 && (N1 % 8) == 0 && (K1 % 8) == 0);
@@ -1394,24 +1554,66 @@ extern "C" int octmae_wgrad_accum_pair(const void* dY0, const void* X0, float* g
   const int N[2] = {N0, N1}, K[2] = {K0, K1}, ldy[2] = {ldy0, ldy1}, ldx[2] = {ldx0, ldx1}, ldw[2] = {ldw0, ldw1};
   const void* const dY[2] = {dY0, dY1}, * const X[2] = {X0, X1};
   float* const gW[2] = {gW0, gW1}, * const gB[2] = {gB0, gB1};
-  const PairPlan pl = plan_wgrad_pair(N, K, ldy, ldx, M, splitk, current_options(), device_cus());
+  const GemmOptions opt = current_options();
+  const long long usable = opt.deterministic ? det_usable_ws(split_ws ? split_ws_bytes : 0) : 0;
+  // (reserved whether or not a bias gradient is asked for: octmae_wgrad_pair_plan_ws, which does not know, reports this very plan)
+  const long long cs_bytes = opt.deterministic ? det_colsum_bytes(true, M, std::max(N0, N1), usable) : 0;
+  const PairPlan pl = plan_wgrad_pair(N, K, ldy, ldx, M, splitk, opt, device_cus(), usable - cs_bytes);
   if (pl.status != 0) return pl.status;
+  const bool slab = pl.atomic1 == ATOMIC1_SLABS;      // deterministic mode, split: [column-sum rows] slabs of output 0, those of output 1
+  float* const slab0 = reinterpret_cast<float*>(reinterpret_cast<char*>(split_ws) + cs_bytes);
+  float* const slabs[2] = {slab0, slab0 + (size_t)pl.slices * N0 * K0};
   GemmPair pp;
   for (int i = 0; i < 2; ++i) {
     GemmParams& p = i ? pp.p1 : pp.p0;
     if (gB[i] != nullptr && pl.colsum == Colsum::PassBefore)
-      if (int rc = octmae_colsum_accum(dY[i], 1, gB[i], M, N[i], ldy[i], stream)) return rc;
-    p = make_params(dY[i], X[i], gW[i], pl.colsum == Colsum::Fused ? gB[i] : nullptr, nullptr, N[i], K[i], M, ldy[i], ldx[i], ldw[i], 0);
+      if (int rc = opt.deterministic ? det_colsum(dY[i], gB[i], split_ws, cs_bytes, M, N[i], ldy[i], stream)
+                                     : octmae_colsum_accum(dY[i], 1, gB[i], M, N[i], ldy[i], stream)) return rc;
+    p = make_params(dY[i], X[i], slab ? slabs[i] : gW[i], pl.colsum == Colsum::Fused ? gB[i] : nullptr, nullptr, N[i], K[i], M, ldy[i], ldx[i], ldw[i], 0);
     p.tiles_a = pl.tiles_a[i]; p.tiles_b = pl.tiles_b[i]; p.cgroup = pl.cgroup[i];
     p.ktiles_per_split = pl.ktiles_per_split; p.kstagger = pl.kstagger; p.atomic1 = pl.atomic1;
   }
   pp.nt0 = pl.tiles_a[0] * pl.tiles_b[0]; pp.nt1 = pl.tiles_a[1] * pl.tiles_b[1]; pp.S = pl.slices;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (slab) {
+    int rc;
+    if (pl.kernel == GemmKernel::Phased256) rc = launch_dyn<gemm256p_wgrad_pair_slab_kernel>(dim3(pl.grid()), 512, 4 * TILE2_BYTES, st, pp);
+    else if (pl.nst != 4) return PLAN_FALLBACK;       // plan_wgrad_pair splits the 128-tile pair on the 4-stage ring only in this mode
+    else rc = launch_dyn<gemm128d_wgrad_slab_kernel<4>>(dim3(pl.grid()), 256, 4 * D_STAGE, st, pp);
+    if (rc != 0) return rc;
+    if (pl.kernel != GemmKernel::Phased256) g_small_wgrad_launches.fetch_add(1, std::memory_order_relaxed);
+    const long long stride[2] = {(long long)N0 * K0, (long long)N1 * K1};
+    return launch_fold(2, gW, slabs, stride, N, K, ldw, K, pl.slices, st);
+  }
   if (pl.kernel == GemmKernel::Phased256) return launch_dyn<gemm256p_wgrad_pair_kernel>(dim3(pl.grid()), 512, 4 * TILE2_BYTES, st, pp);
   const int rc = pl.nst == 2 ? launch_dyn<gemm128d_wgrad_kernel<2>>(dim3(pl.grid()), 256, 2 * D_STAGE, st, pp)
                              : launch_dyn<gemm128d_wgrad_kernel<4>>(dim3(pl.grid()), 256, 4 * D_STAGE, st, pp);
   if (rc == 0) g_small_wgrad_launches.fetch_add(1, std::memory_order_relaxed);
   return rc;
+}
+extern "C" int octmae_wgrad_accum_pair(const void* dY0, const void* X0, float* gW0, float* gB0, int N0, int K0, int ldy0, int ldx0, int ldw0,
+                                       const void* dY1, const void* X1, float* gW1, float* gB1, int N1, int K1, int ldy1, int ldx1, int ldw1,
+                                       int M, int splitk, void* stream) {
+  return octmae_wgrad_accum_pair_ws(dY0, X0, gW0, gB0, N0, K0, ldy0, ldx0, ldw0, dY1, X1, gW1, gB1, N1, K1, ldy1, ldx1, ldw1, M, splitk,
+                                    nullptr, 0, stream);
+}
+
+// ---- deterministic mode: the switch as the library sees it, the slab workspace, the fold on its own -------------------------------------
+extern "C" int octmae_deterministic(void) { return current_options().deterministic; }
+extern "C" int octmae_wgrad_det_ws_bytes(int N0, int K0, int N1, int K1, int M, int want_bias, int slices, long long* bytes) {
+  OCTMAE_CHECK_ARG(N0 > 0 && K0 > 0 && N1 >= 0 && K1 >= 0 && (N1 > 0) == (K1 > 0) && M > 0 && slices >= 1 && bytes);
+  // the head as the entry points carve it: a single launch with a bias gradient; a pair always, for its wider dY
+  const long long head = det_colsum_bytes(N1 > 0 || want_bias != 0, M, std::max(N0, N1), 1ll << 62);
+  *bytes = head + det_slab_bytes((long long)N0 * K0 + (long long)N1 * K1, slices);
+  return 0;
+}
+extern "C" int octmae_wgrad_fold(float* gW, const float* slabs, int S, int NA, int NB, int ldc, int ld_slab, long long slab_stride,
+                                 void* stream) {
+  OCTMAE_CHECK_ARG(gW && slabs && S >= 1 && NA > 0 && NB > 0 && ldc >= NB && ld_slab >= NB);
+  OCTMAE_CHECK_ARG(slab_stride >= (long long)(NA - 1) * ld_slab + NB);
+  float* const g[1] = {gW};
+  const float* const sl[1] = {slabs};
+  return launch_fold(1, g, sl, &slab_stride, &NA, &NB, &ldc, &ld_slab, S, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- plan queries: host-side arithmetic only, no GPU is touched (tests/test_cpu_host.py; include/octmae.h) ---------------------------
@@ -1425,16 +1627,21 @@ extern "C" int octmae_wgrad_split_plan(int M, int splitk, int tiles, int* slices
   OCTMAE_CHECK_ARG(M > 0 && tiles > 0 && slices && bounds);
   const int ktiles = cdiv(M, TK);
   const Split s = normalise_split(ktiles, splitk);
-  const int d = wgrad_stagger_for(ktiles, s.slices, tiles, current_options().wgrad_stagger);
+  const GemmOptions o = current_options();
+  const int d = o.deterministic ? 0 : wgrad_stagger_for(ktiles, s.slices, tiles, o.wgrad_stagger);     // deterministic mode: equal slices
   *slices = s.slices;
   for (int z = 0; z < s.slices; ++z) split_range_of(ktiles, s.per, d, z, s.slices, bounds[z], bounds[z + 1]);
   return d;
 }
-extern "C" int octmae_gemm_plan(int kind, int NA, int NB, int K, int lda, int ldb, int variant, int splitk, int have_ws, int cus, int* out) {
-  OCTMAE_CHECK_ARG(kind >= 0 && kind <= 6 && NA > 0 && NB > 0 && K > 0 && cus > 0 && out);
+extern "C" int octmae_gemm_plan_ws(int kind, int NA, int NB, int K, int lda, int ldb, int variant, int splitk, long long ws_bytes, int cus, int* out) {
+  OCTMAE_CHECK_ARG(kind >= 0 && kind <= 6 && NA > 0 && NB > 0 && K > 0 && cus > 0 && out && ws_bytes >= 0);
+  const int have_ws = ws_bytes >= d_ws_bytes();
   const int epi = kind == 0 || kind == 1 ? EPI_BF16 : kind <= 3 ? EPI_DGELU : kind == 4 ? EPI_DELTA : EPI_ACCUM;       // include/octmae.h
-  const GemmProblem q{NA, NB, K, lda, ldb, kind >= 1, kind >= 5, epi, splitk, kind == 2 || kind == 3 || kind == 6, kind == 3};
-  const GemmPlan pl = plan_gemm(q, decode_variant(variant), current_options(), [cus] { return cus; }, have_ws != 0);
+  const GemmOptions opt = current_options();
+  const long long usable = opt.deterministic && kind >= 5 ? det_usable_ws(ws_bytes) : 0;
+  const GemmProblem q{NA, NB, K, lda, ldb, kind >= 1, kind >= 5, epi, splitk, kind == 2 || kind == 3 || kind == 6, kind == 3,
+                      usable - (opt.deterministic ? det_colsum_bytes(kind == 6, K, NA, usable) : 0)};
+  const GemmPlan pl = plan_gemm(q, decode_variant(variant), opt, [cus] { return cus; }, have_ws != 0);
   const bool small = pl.kernel == GemmKernel::Small128d;
   const int o[13] = {(int)pl.kernel, pl.grid(), pl.tiles_a, pl.tiles_b, pl.cgroup,                                // [0..4]
                      pl.slices, pl.ktiles_per_split, pl.kstagger, pl.atomic1, small ? pl.nst : 0,                 // [5..9]
@@ -1442,13 +1649,22 @@ extern "C" int octmae_gemm_plan(int kind, int NA, int NB, int K, int lda, int ld
   for (int i = 0; i < 13; ++i) out[i] = pl.status == 0 ? o[i] : 0;
   return pl.status;
 }
-extern "C" int octmae_wgrad_pair_plan(int N0, int K0, int ldy0, int ldx0, int N1, int K1, int ldy1, int ldx1, int M, int splitk, int cus, int* out) {
-  OCTMAE_CHECK_ARG(N0 > 0 && K0 > 0 && N1 > 0 && K1 > 0 && M > 0 && cus > 0 && out);
+extern "C" int octmae_gemm_plan(int kind, int NA, int NB, int K, int lda, int ldb, int variant, int splitk, int have_ws, int cus, int* out) {
+  return octmae_gemm_plan_ws(kind, NA, NB, K, lda, ldb, variant, splitk, have_ws ? d_ws_bytes() : 0, cus, out);
+}
+extern "C" int octmae_wgrad_pair_plan_ws(int N0, int K0, int ldy0, int ldx0, int N1, int K1, int ldy1, int ldx1, int M, int splitk,
+                                         long long ws_bytes, int cus, int* out) {
+  OCTMAE_CHECK_ARG(N0 > 0 && K0 > 0 && N1 > 0 && K1 > 0 && M > 0 && cus > 0 && out && ws_bytes >= 0);
   const int N[2] = {N0, N1}, K[2] = {K0, K1}, ldy[2] = {ldy0, ldy1}, ldx[2] = {ldx0, ldx1};
-  const PairPlan pl = plan_wgrad_pair(N, K, ldy, ldx, M, splitk, current_options(), cus);
+  const GemmOptions opt = current_options();
+  const long long usable = opt.deterministic ? det_usable_ws(ws_bytes) : 0;
+  const PairPlan pl = plan_wgrad_pair(N, K, ldy, ldx, M, splitk, opt, cus, usable - (opt.deterministic ? det_colsum_bytes(true, M, std::max(N0, N1), usable) : 0));
   const int o[14] = {(int)pl.kernel, pl.grid(), pl.slices, pl.ktiles_per_split, pl.kstagger, pl.atomic1,           // [0..5]
                      pl.nst, (int)pl.colsum, pl.tiles_a[0], pl.tiles_b[0], pl.cgroup[0],                          // [6..10]
                      pl.tiles_a[1], pl.tiles_b[1], pl.cgroup[1]};                                                 // [11..13]
   for (int i = 0; i < 14; ++i) out[i] = pl.status == 0 ? o[i] : 0;
   return pl.status;
+}
+extern "C" int octmae_wgrad_pair_plan(int N0, int K0, int ldy0, int ldx0, int N1, int K1, int ldy1, int ldx1, int M, int splitk, int cus, int* out) {
+  return octmae_wgrad_pair_plan_ws(N0, K0, ldy0, ldx0, N1, K1, ldy1, ldx1, M, splitk, 0, cus, out);      // as octmae_wgrad_accum_pair: no workspace
 }

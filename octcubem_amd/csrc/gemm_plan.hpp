@@ -25,6 +25,7 @@ enum Epi : int {
   EPI_DELTA = 6,     // C bf16 = X, C2 f32 [NB][ldc2]: C2[b][a / hd] = -sum_{j < hd} bf16(X[b][a0 + j]) * aux_bf16[b][a0 + j]
                      //   (the attention backward's per-query delta = rowsum(dO * O), from the proj dgrad that produces dO;
                      //   256-tile LDS-transposing epilogue only)
+  EPI_ACCUM_SLAB = 7,   // C f32 = X, C the slab of one k slice (deterministic mode; inside gemm.hip only, never an entry point's `epilogue`)
 };
 
 // ---- variant bits ---------------------------------------------------------------------------------------------------------------
@@ -50,21 +51,23 @@ inline GemmVariant decode_variant(int bits) {
 
 // ---- options ---------------------------------------------------------------------------------------------------------------------
 // octmae_set_option atomics (defined in gemm.hip, set in attn_bwd.hip); an environment variable, read once per process, wins.
-extern std::atomic<int> g_gemm_small, g_wgrad_stagger, g_wgrad_s1_atomic;
+extern std::atomic<int> g_gemm_small, g_wgrad_stagger, g_wgrad_s1_atomic, g_deterministic;
 struct GemmOptions {
   int gemm_small;        // "gemm_small" / OCTMAE_GEMM_SMALL: the small-launch kernels where the cost models pick them
   int wgrad_stagger;     // "wgrad_stagger" / OCTMAE_WGRAD_STAGGER: see wgrad_stagger_for
   int wgrad_s1_atomic;   // "wgrad_s1_atomic" / OCTMAE_WGRAD_S1_ATOMIC: GemmParams::atomic1 of the phased weight-gradient kernels
   int cgroup_force;      // OCTMAE_CGROUP (A/B runs): column-tile group of forward / dgrad launches, 0 = the rule of cgroup_for
   int wgrad128_maxkt;    // OCTMAE_WGRAD128_MAXKT (A/B runs): longest reduction the 128-tile weight-gradient pair takes, default 96
+  int deterministic;     // "deterministic" / OCTMAE_DETERMINISTIC: no float is added in the order workgroups finish (det_* below; optim.hip)
 };
 inline GemmOptions current_options() {
   auto env = [](const char* name, int dflt) { const char* s = getenv(name); return s ? atoi(s) : dflt; };
   static const GemmOptions e{env("OCTMAE_GEMM_SMALL", -1), env("OCTMAE_WGRAD_STAGGER", -1), env("OCTMAE_WGRAD_S1_ATOMIC", -1),
-                             env("OCTMAE_CGROUP", 0), env("OCTMAE_WGRAD128_MAXKT", 96)};
+                             env("OCTMAE_CGROUP", 0), env("OCTMAE_WGRAD128_MAXKT", 96), env("OCTMAE_DETERMINISTIC", -1)};
   return {e.gemm_small >= 0 ? e.gemm_small : g_gemm_small.load(std::memory_order_relaxed),
           e.wgrad_stagger >= 0 ? e.wgrad_stagger : g_wgrad_stagger.load(std::memory_order_relaxed),
-          e.wgrad_s1_atomic >= 0 ? e.wgrad_s1_atomic : g_wgrad_s1_atomic.load(std::memory_order_relaxed), e.cgroup_force, e.wgrad128_maxkt};
+          e.wgrad_s1_atomic >= 0 ? e.wgrad_s1_atomic : g_wgrad_s1_atomic.load(std::memory_order_relaxed), e.cgroup_force, e.wgrad128_maxkt,
+          (e.deterministic >= 0 ? e.deterministic : g_deterministic.load(std::memory_order_relaxed)) != 0};
 }
 
 // ---- shared rules ----------------------------------------------------------------------------------------------------------------
@@ -149,6 +152,24 @@ inline int wgrad_stagger_for(int ktiles, int splitk, int tiles, int v) {
   if (d > dmax) d = dmax;
   return d > 0 ? (int)d : 0;
 }
+// ---- deterministic mode ("deterministic") ----------------------------------------------------------------------------------------
+// A weight gradient split S > 1 ways over k adds nothing into gW from the GEMM: slice z leaves its fp32 partial as slab z of a lent
+// workspace -- fp32 [S][NA][NB], rows packed, plain stores, need not be initialised -- and wgrad_fold_kernel (one launch of its own,
+// both outputs of a pair) computes gW = (...((gW + P_0) + P_1) ... + P_{S-1}): what S unsplit launches over the slices' row ranges,
+// issued in order, would leave.  GemmParams::atomic1 of such a launch is ATOMIC1_SLABS.  The split is the one chosen without the mode,
+// capped so that the slabs fit (down to 1: never atomics), and unstaggered (the stagger spreads atomic epilogues).
+constexpr int ATOMIC1_SLABS = 3;
+inline long long det_slab_bytes(long long out_elems, int slices) { return slices > 1 ? out_elems * 4 * slices : 0; }
+inline int det_cap_split(int slices, long long out_elems, long long ws_bytes) {
+  const long long fit = ws_bytes / (out_elems * 4);
+  return fit < 2 ? 1 : fit < slices ? (int)fit : slices;
+}
+// the bytes of a lent split-K workspace the slabs may take: everything in front of the arrival counters of the small-launch kernel
+inline long long det_usable_ws(long long bytes) {
+  const long long slots = (long long)D_WS_SLOTS * D_SLOT_FLOATS * 4;
+  return bytes <= 0 ? 0 : bytes < slots ? bytes : slots;
+}
+
 // use = 1: gemm128d_kernel; S: k slices per tile (1: no workspace needed); nst: ring stages, 4 (one workgroup per CU) or 2 (two)
 struct Plan128 { int use, S, nst; };
 // Which kernel a forward / dgrad launch of NA x NB x K takes on G CUs (fitted on MI355X with tools/gemm_small_fit.py: device times of
@@ -209,6 +230,7 @@ struct GemmProblem {
   int epi, splitk;       // Epi (EPI_DELTA included); the k split the caller asks for (weight gradients: <= 0 = auto_wgrad_split)
   bool have_c2;          // EPI_DGELU / EPI_ACCUM: column sums are wanted
   bool have_colsum_ws;   // EPI_DGELU: a per-slab workspace for them was given
+  long long slab_bytes = 0;   // EPI_ACCUM in deterministic mode: bytes of the workspace lent for the slices' slabs
 };
 struct GemmPlan {
   int status;            // 0, or PLAN_FALLBACK
@@ -251,19 +273,24 @@ inline GemmPlan plan_gemm(const GemmProblem& q, const GemmVariant& v, const Gemm
     const int tile = big ? T2 : TA;
     pl.tiles_a = cdiv(q.NA, tile); pl.tiles_b = cdiv(q.NB, tile);
     pl.cgroup = big ? cgroup_for(q.epi, pl.tiles_a, pl.tiles_b, q.K, o) : pl.tiles_a;
-    const Split s = normalise_split(ktiles, !wgrad ? 1 : q.splitk > 0 ? q.splitk : auto_wgrad_split(pl.tiles_a * pl.tiles_b, ktiles, big ? 256 : 1024));
+    Split s = normalise_split(ktiles, !wgrad ? 1 : q.splitk > 0 ? q.splitk : auto_wgrad_split(pl.tiles_a * pl.tiles_b, ktiles, big ? 256 : 1024));
+    // deterministic mode: as many of those slices as have a slab; the two-stage loop (A/B runs only) has no slab form and runs unsplit
+    if (wgrad && o.deterministic && s.slices > 1)
+      s = normalise_split(ktiles, pl.kernel == GemmKernel::TwoStage256 ? 1 : det_cap_split(s.slices, (long long)q.NA * q.NB, q.slab_bytes));
     pl.slices = s.slices; pl.ktiles_per_split = s.per;
-    pl.kstagger = (big && wgrad) ? wgrad_stagger_for(ktiles, s.slices, pl.tiles_a * pl.tiles_b, o.wgrad_stagger) : 0;
+    pl.kstagger = (big && wgrad && !o.deterministic) ? wgrad_stagger_for(ktiles, s.slices, pl.tiles_a * pl.tiles_b, o.wgrad_stagger) : 0;
     pl.atomic1 = (pl.kernel == GemmKernel::Phased256 && wgrad) ? o.wgrad_s1_atomic : 0;
+    if (wgrad && o.deterministic && s.slices > 1) pl.atomic1 = ATOMIC1_SLABS;
     pl.ws_rows = 4 * pl.tiles_b;
   }
   // EPI_DGELU: fused into the LDS-transposing epilogues (256-tile kernels, small-launch kernel); the 128-tile register-staged
   // kernel is followed by the stand-alone column-sum kernel.  EPI_ACCUM: fused into the phased 256-tile kernel's main loop.
   if (q.have_c2 && q.epi == EPI_DGELU)
     pl.colsum = (pl.kernel == GemmKernel::Tile128 || (q.NA & 7) != 0) ? Colsum::PassAfter
-                                                                      : q.have_colsum_ws ? Colsum::FoldWs : Colsum::Fused;
+                                                                      : q.have_colsum_ws ? Colsum::FoldWs
+                                                                      : o.deterministic ? Colsum::PassAfter : Colsum::Fused;
   else if (q.have_c2 && q.epi == EPI_ACCUM)
-    pl.colsum = pl.kernel == GemmKernel::Phased256 ? Colsum::Fused : Colsum::PassBefore;
+    pl.colsum = (pl.kernel == GemmKernel::Phased256 && !o.deterministic) ? Colsum::Fused : Colsum::PassBefore;
   return pl;
 }
 
@@ -276,23 +303,31 @@ struct PairPlan {
   int grid() const { return (tiles_a[0] * tiles_b[0] + tiles_a[1] * tiles_b[1]) * slices; }
 };
 // gW_i[N_i][K_i] += dY_i[M][N_i]^T X_i[M][K_i], i = 0, 1, sharing one split over the M rows
+// slab_bytes: deterministic mode, the workspace lent for the slices' slabs (0: none, the pair runs unsplit there)
 inline PairPlan plan_wgrad_pair(const int N[2], const int K[2], const int ldy[2], const int ldx[2], int M, int splitk,
-                                const GemmOptions& o, int cus) {
+                                const GemmOptions& o, int cus, long long slab_bytes = 0) {
   PairPlan pl{};
   for (int i = 0; i < 2; ++i)
     if (!fits_256(N[i], K[i], M, ldy[i], ldx[i], true, true)) { pl.status = PLAN_FALLBACK; return pl; }
   const int ktiles = cdiv(M, TK);
   const int nt256 = cdiv(N[0], T2) * cdiv(K[0], T2) + cdiv(N[1], T2) * cdiv(K[1], T2);
-  const Split s = normalise_split(ktiles, splitk > 0 ? splitk : auto_wgrad_split(nt256, ktiles, 256));   // splitk <= 0: the planner's own
+  Split s = normalise_split(ktiles, splitk > 0 ? splitk : auto_wgrad_split(nt256, ktiles, 256));   // splitk <= 0: the planner's own
+  if (o.deterministic && s.slices > 1)
+    s = normalise_split(ktiles, det_cap_split(s.slices, (long long)N[0] * K[0] + (long long)N[1] * K[1], slab_bytes));
   const long long nt128 = (long long)cdiv(N[0], T1) * cdiv(K[0], T1) + (long long)cdiv(N[1], T1) * cdiv(K[1], T1);
   pl.atomic1 = o.wgrad_s1_atomic;
-  pl.colsum = Colsum::Fused;
+  pl.colsum = o.deterministic ? Colsum::PassBefore : Colsum::Fused;
   // Small launches (round 6): 128 x 128 tiles when the cost model prices them faster.  Microseconds, fitted with tools/gemm_small_fit.py:
   // the 256-tile pair ~1.4 per k-tile of a slice + 0.22 per tile and slice of fp32 atomics (split) or ~10 of read-modify-write
   // (unsplit); a 128-tile workgroup (both operands through transposing LDS reads) ~0.6 per k-tile alone on its CU (4-stage ring), ~1.05
   // two per CU (2-stage), + ~8, + 0.055 per tile and slice of atomics.  Measured (profiles/r06_gemm_small_fit.txt): one volume, encoder
   // fc pair 40 -> 32 us, qkv + proj 40 -> 26, decoder 52 -> 39 and 40 -> 32; four volumes 113 -> 90 and 77 -> 64.  Short reductions only
   // (<= 96 k-tiles per launch): beyond, both kernels stream and the larger tile wins.
+  // Deterministic mode keeps these prices although a split launch no longer ends in atomics there (both sides store slabs, and the fold
+  // that follows costs the same for either tile size): the terms were fitted for the default mode, the mode's own have not been
+  // measured, so the kernel family may differ from the default's for a split launch -- a matter of speed only.  A split 128-tile pair
+  // takes the 4-stage ring there: the 2-stage ring never wins with a split (S2 <= 4, kper >= 8: one more slice on the 4-stage ring is
+  // cheaper), so its slab form is not built.
   if (o.gemm_small && ktiles <= o.wgrad128_maxkt && nt128 <= 2 * cus) {
     const double c256 = 1.4 * s.per + (s.slices > 1 ? 0.22 * nt256 * s.slices : 10.0);
     double best = 1e30;
@@ -303,19 +338,21 @@ inline PairPlan plan_wgrad_pair(const int N[2], const int K[2], const int ldy[2]
       const long long wg = nt128 * S2;
       const double at = S2 > 1 ? 0.055 * nt128 * S2 : 0.0;
       if (wg <= cus && 0.6 * kper + 8.0 + at < best) { best = 0.6 * kper + 8.0 + at; bS = S2; bN = 4; }
-      if (wg > cus && wg <= 2 * cus && 1.05 * kper + 8.0 + at < best) { best = 1.05 * kper + 8.0 + at; bS = S2; bN = 2; }
+      if (wg > cus && wg <= 2 * cus && !(o.deterministic && S2 > 1) && 1.05 * kper + 8.0 + at < best) { best = 1.05 * kper + 8.0 + at; bS = S2; bN = 2; }
     }
     if (best < 0.9 * c256) {
       // the bias gradients ride in the 256-tile kernel's main loop; on this path they are a pass of their own over dY
       pl.kernel = GemmKernel::Small128d; pl.colsum = Colsum::PassBefore;
       pl.slices = bS; pl.ktiles_per_split = cdiv(ktiles, bS); pl.nst = bN;
+      if (o.deterministic && bS > 1) pl.atomic1 = ATOMIC1_SLABS;
       for (int i = 0; i < 2; ++i) { pl.tiles_a[i] = cdiv(N[i], T1); pl.tiles_b[i] = cdiv(K[i], T1); pl.cgroup[i] = pl.tiles_a[i]; }
       return pl;
     }
   }
   pl.kernel = GemmKernel::Phased256;
   pl.slices = s.slices; pl.ktiles_per_split = s.per;
-  pl.kstagger = wgrad_stagger_for(ktiles, s.slices, nt256, o.wgrad_stagger);
+  pl.kstagger = o.deterministic ? 0 : wgrad_stagger_for(ktiles, s.slices, nt256, o.wgrad_stagger);
+  if (o.deterministic && s.slices > 1) pl.atomic1 = ATOMIC1_SLABS;
   for (int i = 0; i < 2; ++i) {
     pl.tiles_a[i] = cdiv(N[i], T2); pl.tiles_b[i] = cdiv(K[i], T2);
     pl.cgroup[i] = cgroup_for(EPI_ACCUM, pl.tiles_a[i], pl.tiles_b[i], M, o);

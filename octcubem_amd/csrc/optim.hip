@@ -6,6 +6,7 @@
 // Multi-tensor addressing: a device table of tensors {p, g, m, v, n} plus a chunk table mapping every
 // 65536-element chunk to (tensor, offset); one workgroup per chunk, 16-byte accesses.
 #include "common.hpp"
+#include "gemm_plan.hpp"   // current_options(): the "deterministic" option
 #include "../../include/octmae.h"
 
 namespace octmae {
@@ -48,6 +49,49 @@ __global__ __launch_bounds__(256) void mt_sumsq_kernel(const TensorDesc* __restr
   if (threadIdx.x == 0) unsafeAtomicAdd(sumsq + t, (red[0] + red[1]) + (red[2] + red[3]));
 }
 
+// Deterministic mode.  The default kernels above and below keep their text (their generated code is compared with the release's), so
+// the per-chunk form of mt_sumsq_kernel is a kernel of its own: the same sum -- the bits a one-chunk tensor's sumsq[t] gets from the
+// kernel above -- stored as partial[chunk] instead of added to sumsq[t].
+__global__ __launch_bounds__(256) void mt_sumsq_part_kernel(const TensorDesc* __restrict__ tensors, const int* __restrict__ chunk_tensor,
+                                                            const long long* __restrict__ chunk_off, float* __restrict__ partial) {
+  __shared__ float red[4];
+  const int t = chunk_tensor[blockIdx.x];
+  const long long off = chunk_off[blockIdx.x];
+  const TensorDesc d = tensors[t];
+  long long n = d.n - off;
+  if (n > CHUNK) n = CHUNK;
+  const float* g = d.g + off;
+  float s = 0.f;
+  const bool vec = ((reinterpret_cast<uintptr_t>(g) & 15) == 0);
+  if (vec) {
+    const long long n4 = n >> 2;
+    for (long long i = threadIdx.x; i < n4; i += 256) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(g + 4 * i);
+      s += (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
+    }
+    for (long long i = (n4 << 2) + threadIdx.x; i < n; i += 256) s += g[i] * g[i];
+  } else {
+    for (long long i = threadIdx.x; i < n; i += 256) s += g[i] * g[i];
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// sumsq[t] = (...((sumsq[t] + partial[c0]) + partial[c0 + 1]) ...) over the chunks c0, c0 + 1, ... of tensor t, in ascending order.
+// The chunks of a tensor are consecutive in the table (octcubem_amd/optim.py builds it so); the thread of a tensor's FIRST chunk walks
+// the run, so every sumsq[t] has one writer.  One thread per chunk: no grid cap and no loop behind one (docs/GRID_CAPS.md).
+__global__ __launch_bounds__(256) void mt_sumsq_finish_kernel(const float* __restrict__ partial, const int* __restrict__ chunk_tensor,
+                                                              int nchunks, float* __restrict__ sumsq) {
+  const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= nchunks) return;
+  const int t = chunk_tensor[c];
+  if (c > 0 && chunk_tensor[c - 1] == t) return;
+  float s = sumsq[t];
+  for (long long i = c; i < nchunks && chunk_tensor[i] == t; ++i) s += partial[i];
+  sumsq[t] = s;
+}
+
 // total_norm = sqrt(sum_t sumsq[t])  (== 2-norm of the stack of per-tensor 2-norms);
 // clip_coef = min(1, max_norm / (total_norm + 1e-6)) when max_norm > 0 (torch clip_grad_norm_), else 1
 __global__ void mt_finish_norm_kernel(const float* __restrict__ sumsq, int nt, float max_norm, float* __restrict__ out_norm,
@@ -83,7 +127,8 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 // LP: also write the 16-bit operand copy of the updated parameter (lp_table[t], the arena's mirror: the per-forward cast pass over
 // the whole arena -- 6 B per parameter -- becomes 2 B written here).  SQ: also accumulate sumsq[t] += sum(g^2) of the RAW gradient
 // (get_grad_norm_ without its own pass over the gradients; only when no clip coefficient has to be known before the update).
-template <bool LP, bool SQ>
+// PART (deterministic mode, with SQ): `sumsq` is the workspace fp32 [nchunks] and the chunk STORES its sum as sumsq[chunk].
+template <bool LP, bool SQ, bool PART = false>
 __global__ __launch_bounds__(256) void mt_adamw_kernel(const TensorDesc* __restrict__ tensors, const int* __restrict__ chunk_tensor,
                                                        const long long* __restrict__ chunk_off, const float* __restrict__ gscale,
                                                        bf16_t* const* __restrict__ lp_table, float* __restrict__ sumsq,
@@ -141,8 +186,19 @@ __global__ __launch_bounds__(256) void mt_adamw_kernel(const TensorDesc* __restr
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(sumsq + t, (red[0] + red[1]) + (red[2] + red[3]));
+    if constexpr (PART) {
+      if (threadIdx.x == 0) sumsq[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    } else {
+      if (threadIdx.x == 0) unsafeAtomicAdd(sumsq + t, (red[0] + red[1]) + (red[2] + red[3]));
+    }
   }
+}
+
+
+static int sumsq_finish(const float* partial, const int* chunk_tensor, int nchunks, float* sumsq, hipStream_t st) {
+  hipLaunchKernelGGL(mt_sumsq_finish_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, st, partial, chunk_tensor, nchunks, sumsq);
+  OCTMAE_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace octmae
@@ -150,13 +206,27 @@ using namespace octmae;
 
 extern "C" int octmae_mt_chunk_elems(void) { return CHUNK; }
 
-extern "C" int octmae_mt_sumsq(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,
-                               float* sumsq, void* stream) {
+// partial: fp32 [nchunks], lent for the call, need not be initialised; read only in deterministic mode, where it is REQUIRED: the
+// mode never adds in finishing order, so a call without it is refused (-1)
+extern "C" int octmae_mt_sumsq_ws(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,
+                                  float* sumsq, float* partial, void* stream) {
   OCTMAE_CHECK_ARG(tensor_table && chunk_tensor && chunk_off && sumsq && nchunks > 0);
+  if (current_options().deterministic) {
+    OCTMAE_CHECK_ARG(partial != nullptr);
+    hipLaunchKernelGGL(mt_sumsq_part_kernel, dim3(nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<const TensorDesc*>(tensor_table), chunk_tensor, chunk_off, partial);
+    OCTMAE_LAUNCH_CHECK();
+    return sumsq_finish(partial, chunk_tensor, nchunks, sumsq, reinterpret_cast<hipStream_t>(stream));
+  }
   hipLaunchKernelGGL(mt_sumsq_kernel, dim3(nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const TensorDesc*>(tensor_table), chunk_tensor, chunk_off, sumsq);
   OCTMAE_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int octmae_mt_sumsq(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,
+                               float* sumsq, void* stream) {
+  return octmae_mt_sumsq_ws(tensor_table, chunk_tensor, chunk_off, nchunks, sumsq, nullptr, stream);
 }
 
 extern "C" int octmae_mt_finish_norm(const float* sumsq, int ntensors, float max_norm, float* out_norm, float* out_coef,
@@ -168,10 +238,13 @@ extern "C" int octmae_mt_finish_norm(const float* sumsq, int ntensors, float max
   return 0;
 }
 
-extern "C" int octmae_mt_adamw_fused(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,
-                                     const float* gscale, void* const* lp_table, float* sumsq, float lr, float beta1, float beta2,
-                                     float eps, float weight_decay, int step, void* stream) {
+// partial: as in octmae_mt_sumsq_ws (looked at only with `sumsq`)
+extern "C" int octmae_mt_adamw_fused_ws(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,
+                                        const float* gscale, void* const* lp_table, float* sumsq, float* partial, float lr, float beta1,
+                                        float beta2, float eps, float weight_decay, int step, void* stream) {
   OCTMAE_CHECK_ARG(tensor_table && chunk_tensor && chunk_off && nchunks > 0 && step >= 1);
+  const bool det = sumsq != nullptr && current_options().deterministic;
+  if (det) OCTMAE_CHECK_ARG(partial != nullptr);
   AdamArgs a;
   a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
   a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
@@ -179,12 +252,25 @@ extern "C" int octmae_mt_adamw_fused(const void* tensor_table, const int* chunk_
   const TensorDesc* tt = reinterpret_cast<const TensorDesc*>(tensor_table);
   bf16_t* const* lpt = reinterpret_cast<bf16_t* const*>(lp_table);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (det) {
+    if (lpt) hipLaunchKernelGGL((mt_adamw_kernel<true, true, true>), dim3(nchunks), dim3(256), 0, st, tt, chunk_tensor, chunk_off, gscale, lpt, partial, a);
+    else hipLaunchKernelGGL((mt_adamw_kernel<false, true, true>), dim3(nchunks), dim3(256), 0, st, tt, chunk_tensor, chunk_off, gscale, lpt, partial, a);
+    OCTMAE_LAUNCH_CHECK();
+    return sumsq_finish(partial, chunk_tensor, nchunks, sumsq, st);
+  }
   if (lpt && sumsq) hipLaunchKernelGGL((mt_adamw_kernel<true, true>), dim3(nchunks), dim3(256), 0, st, tt, chunk_tensor, chunk_off, gscale, lpt, sumsq, a);
   else if (lpt) hipLaunchKernelGGL((mt_adamw_kernel<true, false>), dim3(nchunks), dim3(256), 0, st, tt, chunk_tensor, chunk_off, gscale, lpt, sumsq, a);
   else if (sumsq) hipLaunchKernelGGL((mt_adamw_kernel<false, true>), dim3(nchunks), dim3(256), 0, st, tt, chunk_tensor, chunk_off, gscale, lpt, sumsq, a);
   else hipLaunchKernelGGL((mt_adamw_kernel<false, false>), dim3(nchunks), dim3(256), 0, st, tt, chunk_tensor, chunk_off, gscale, lpt, sumsq, a);
   OCTMAE_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int octmae_mt_adamw_fused(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,
+                                     const float* gscale, void* const* lp_table, float* sumsq, float lr, float beta1, float beta2,
+                                     float eps, float weight_decay, int step, void* stream) {
+  return octmae_mt_adamw_fused_ws(tensor_table, chunk_tensor, chunk_off, nchunks, gscale, lp_table, sumsq, nullptr, lr, beta1, beta2, eps,
+                                  weight_decay, step, stream);
 }
 
 extern "C" int octmae_mt_adamw(const void* tensor_table, const int* chunk_tensor, const long long* chunk_off, int nchunks,

@@ -280,10 +280,11 @@ def _split_ws_for(st: int):
 
 def _gemm(A, B, C, NA, NB, K, lda, ldb, ldc, a_ks, b_ks, epi, C2=None, bias=None, aux=None, ldaux=0, splitk=0):
     st = _stream()
-    if (epi & 0xff) != EPI_ACCUM and not FORCE_SMALL_TILE:   # forward / dgrad kinds: lend the split-K workspace
+    # forward / dgrad kinds: lend the split-K workspace; weight gradients: in deterministic mode, for the slabs of their k slices
+    if ((epi & 0xff) != EPI_ACCUM and not FORCE_SMALL_TILE) or ((epi & 0xff) == EPI_ACCUM and is_deterministic()):
         skp, skn = _split_ws_for(st)
         args = (A.data_ptr(), B.data_ptr(), C.data_ptr(), _p(C2), _p(bias), _p(aux), NA, NB, K, lda, ldb, ldc, ldaux, a_ks, b_ks,
-                epi | _variant_bits(), FORCE_SPLITK if FORCE_SMALL_LAUNCH > 0 else splitk, skp, skn, st)
+                epi | _variant_bits(), FORCE_SPLITK if FORCE_SMALL_LAUNCH > 0 and (epi & 0xff) != EPI_ACCUM else splitk, skp, skn, st)
         fn = "octmae_gemm_bf16_ws"
     else:
         args = (A.data_ptr(), B.data_ptr(), C.data_ptr(), _p(C2), _p(bias), _p(aux), NA, NB, K, lda, ldb, ldc, ldaux, a_ks, b_ks,
@@ -435,10 +436,13 @@ def linear_wgrad_accum_pair(first, second):
                 if not (t_.is_cuda and t_.dtype == dt_ and t_.dim() == 2 and t_.stride(1) == 1):
                     raise RuntimeError(f"linear_wgrad_accum_pair: {nm_} must be a GPU {dt_} matrix with contiguous rows")
             args += [dy.data_ptr(), x.data_ptr(), gw.data_ptr(), _p(gb), dy.shape[1], x.shape[1], dy.stride(0), x.stride(0), gw.stride(0)]
-        args += [M, 0, _stream()]                        # k split 0: the planner's (auto_wgrad_split)
+        det = is_deterministic()                         # the slabs of the k slices live in the stream's split-K workspace
+        st = _stream()
+        args += [M, 0] + (list(_split_ws_for(st)) if det else []) + [st]     # k split 0: the planner's (auto_wgrad_split)
+        pair = load().octmae_wgrad_accum_pair_ws if det else load().octmae_wgrad_accum_pair
 
         def run():
-            rc[0] = load().octmae_wgrad_accum_pair(*args)
+            rc[0] = pair(*args)
             return rc[0] != -2
 
         fl = 2.0 * M * (dy0.shape[1] * x0.shape[1] + dy1.shape[1] * x1.shape[1])
@@ -1687,6 +1691,19 @@ def set_option(key: str, value: int) -> int:
     if prev < 0:
         raise RuntimeError(f"octmae_set_option: unknown key {key!r}")
     return prev
+
+
+def set_deterministic(flag: bool) -> bool:
+    """Deterministic mode (octmae_set_option("deterministic"), include/octmae.h): no float of a training step is added in the order
+    workgroups happen to finish -- k-split weight gradients go through slabs and a fixed-order fold, bias gradients through the
+    fixed-order column sums, the gradient norm through per-chunk partials.  Off by default; with it off nothing changes.  Returns
+    the previous setting.  The environment variable OCTMAE_DETERMINISTIC wins over this call (is_deterministic() tells)."""
+    return bool(set_option("deterministic", 1 if flag else 0))
+
+
+def is_deterministic() -> bool:
+    """Whether the library runs in deterministic mode (the environment variable included)."""
+    return bool(load().octmae_deterministic())
 
 
 _N_CU = {}

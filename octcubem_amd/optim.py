@@ -14,7 +14,7 @@ from typing import List, Optional
 import torch
 
 from ._lib import call
-from .ops import _stream
+from .ops import _stream, is_deterministic
 
 
 def _entry_key(p, g, m=None, v=None):
@@ -57,11 +57,18 @@ class _MultiTensorTable:
         self.table = torch.frombuffer(raw, dtype=torch.uint8).clone().to(dev)
         self.chunk_tensor = torch.tensor(ct, dtype=torch.int32, device=dev)
         self.chunk_off = torch.tensor(co, dtype=torch.int64, device=dev)
+        self._partial = None
         self.lp_table = None
         if lps is not None and any(lps):
             self.lp_table = torch.tensor([int(a) for a in lps], dtype=torch.int64, device=dev)
         # every pointer the table holds is part of its identity: a loaded optimizer state replaces exp_avg / exp_avg_sq
         self.key = tuple(_entry_key(p, g, m, v) for p, g, m, v in zip(ps, gs, ms, vs))
+
+    def partial_ws(self) -> torch.Tensor:
+        """Deterministic mode: the fp32 [n_chunks] workspace the sum-of-squares kernels leave one partial per chunk in."""
+        if self._partial is None:
+            self._partial = torch.empty(max(self.n_chunks, 1), dtype=torch.float32, device=self.table.device)
+        return self._partial
 
 
 def grad_norm_and_coef(params, max_norm: Optional[float], cache: dict):
@@ -79,8 +86,12 @@ def grad_norm_and_coef(params, max_norm: Optional[float], cache: dict):
     sumsq = torch.zeros(tab.n_tensors, dtype=torch.float32, device=dev)
     out = torch.empty(2, dtype=torch.float32, device=dev)
     if tab.n_chunks:                                       # every gradient empty: the norm of nothing is 0
-        call("octmae_mt_sumsq", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(), tab.n_chunks,
-             sumsq.data_ptr(), _stream())
+        if is_deterministic():
+            call("octmae_mt_sumsq_ws", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(), tab.n_chunks,
+                 sumsq.data_ptr(), tab.partial_ws().data_ptr(), _stream())
+        else:
+            call("octmae_mt_sumsq", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(), tab.n_chunks,
+                 sumsq.data_ptr(), _stream())
     call("octmae_mt_finish_norm", sumsq.data_ptr(), tab.n_tensors, float(max_norm) if max_norm is not None else 0.0,
          out.data_ptr(), out.data_ptr() + 4, _stream())
     return out[0], out[1]
@@ -185,10 +196,14 @@ class FusedAdamW(torch.optim.Optimizer):
                 continue
             b1, b2 = group["betas"]
             gs = self._grad_scale
-            call("octmae_mt_adamw_fused", tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(), tab.n_chunks,
-                 gs.data_ptr() if gs is not None else None, tab.lp_table.data_ptr() if tab.lp_table is not None else None,
-                 sumsq[gi].data_ptr() if sumsq is not None else None, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                 float(group["weight_decay"]), int(group["_step"]), _stream())
+            head = (tab.table.data_ptr(), tab.chunk_tensor.data_ptr(), tab.chunk_off.data_ptr(), tab.n_chunks,
+                    gs.data_ptr() if gs is not None else None, tab.lp_table.data_ptr() if tab.lp_table is not None else None,
+                    sumsq[gi].data_ptr() if sumsq is not None else None)
+            tail = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), int(group["_step"]), _stream())
+            if sumsq is not None and is_deterministic():      # the by-product through per-chunk partials, added in chunk order
+                call("octmae_mt_adamw_fused_ws", *head, tab.partial_ws().data_ptr(), *tail)
+            else:
+                call("octmae_mt_adamw_fused", *head, *tail)
         if not want_norm:
             return loss
         if sumsq is None:
