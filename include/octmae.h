@@ -70,7 +70,9 @@ extern "C" {
  *     one int32 x f64 matrix product on v_mfma_f64_16x16x4_f64, in a fixed summation order (csrc/bootmoments.hip).
  * 35: deterministic mode ("deterministic" of octmae_set_option, octmae_deterministic): k-split weight gradients through slabs and
  *     octmae_wgrad_fold's kernel instead of fp32 atomics (octmae_wgrad_accum_pair_ws, octmae_wgrad_det_ws_bytes, octmae_gemm_plan_ws,
- *     octmae_wgrad_pair_plan_ws), the gradient norm through per-chunk partials (octmae_mt_sumsq_ws, octmae_mt_adamw_fused_ws). */
+ *     octmae_wgrad_pair_plan_ws), the gradient norm through per-chunk partials (octmae_mt_sumsq_ws, octmae_mt_adamw_fused_ws).
+ *     Added under 35 (new entry points only; no caller of an earlier 35 breaks): octmae_rollout_step (+ octmae_rollout_ws), one step of
+ *     attention rollout as a weighted column sum of a recomputed softmax off the tiles of 19 (csrc/rollout.hip). */
 #define OCTMAE_ABI_VERSION 35
 int octmae_abi_version(void);
 
@@ -718,6 +720,32 @@ long long int octmae_retrieval_topk_ws(long long n, long long m, int k);
 int octmae_retrieval_topk(const float* a, long long a_stride, const float* b, long long b_stride, const uint8_t* keep,
                           const int* row_group, const int* col_group, int k, int* out_idx, float* out_score, void* ws,
                           long long ws_bytes, long long n, long long m, int d, void* stream);
+
+/* ---- one step of attention rollout (csrc/rollout.hip) -------------------------------------------------
+ * Abnar & Zuidema 2020: R = Ahat_L ... Ahat_1 with Ahat_l = (F_l + I) / rho_l, F_l = fuse_h softmax_j(scale q_i . k_j), rho_l[i] =
+ * 1 + sum_j F_l[i, j].  The map of a start row w is w^T R, a chain of L vector-times-matrix steps; this entry point is one of them,
+ *   r_out[b][j] = sum_i (r_in[b][i] / rho[b][i]) (F[b][i, j] + [i == j]),
+ * with the probabilities recomputed on the tiles of octmae_retrieval_ranks; nothing of size N N is stored, in `ws` either.
+ *   q, k    f32; row b N + i, head h at columns h HD .. h HD + HD - 1; rows q_stride / k_stride ELEMENTS apart (>= H HD).  The caller
+ *           widens the 16-bit q | k of the packed qkv its attention consumed (exact for bfloat16 and for half)
+ *   s, z, P s^h(i, j) = the f32 chain of octmae_retrieval_ranks over the head's HD columns (the same bits); z = scale * s (one
+ *           rounding); lse = M + logf(sum_j expf(z - M)) with an online maximum; P = expf(z - lse)
+ *   fusion  0 mean: ((P^0 + P^1) + ...) * (1.0f / H), rho = 2 by definition;  1 max, 2 min over the heads in ascending order (a NaN
+ *           stays), rho summed
+ *   r_in, r_out  f32 [B][N], contiguous, distinct
+ *   ws      at least octmae_rollout_ws(B, N, H, fusion) BYTES, 4-byte aligned: lse [B][H][N], for max / min rho [B][N], and where the
+ *           rows of a column block are split over `split` workgroups (a function of N alone, at most 64) the partial sums
+ *           [split][B][N].  The query returns -2 for B, N or H <= 0, N above 2^31 - 1, fusion outside 0 .. 2, more than
+ *           2^31 - 1 (b, h, block of 64 rows) triples, or a workspace above 2^31 - 1 bytes (an `int`, like octmae_clip_loss_ws_floats:
+ *           3600 ViT-L volumes of 5121 tokens fit)
+ * Deterministic: no atomics; the partial sums are added in ascending order by a finishing launch; two launches give the same bits
+ * and r_out[b] depends neither on B nor on the other samples.  A non-finite q or k of sample b makes r_out[b] NaN.  The library
+ * allocates nothing and does not synchronise.  Same code in the two builds of the library.
+ * -2, before any launch and with nothing written: a NULL q / k / r_in / r_out / ws, B, N or H <= 0, HD outside 1 .. 128, a stride below
+ * H HD, fusion outside 0 .. 2, N above 2^31 - 1, r_in == r_out, a size the query refuses, ws_bytes below the query. */
+int octmae_rollout_ws(int B, long long N, int H, int fusion);
+int octmae_rollout_step(const float* q, long long q_stride, const float* k, long long k_stride, int B, long long N, int H, int HD,
+                        float scale, int fusion, const float* r_in, float* r_out, void* ws, long long ws_bytes, void* stream);
 
 /* ---- both directions of up to three retrieval problems (csrc/retrieval_pair.hip) -----------------------
  * retinal-COEM/src/training/train_retclip_3modalities.py:561-604 (get_metrics_3modalities) ranks six directions: three [n][n] products,

@@ -1665,7 +1665,31 @@ def mix_batch(x: torch.Tensor, kind, lam, oml, box, H: int, W: int) -> torch.Ten
 ATTN_OPTIMISTIC = not LP_IS_F16
 
 
+_ATTN_CAPTURE: Optional[list] = None
+
+
+class capture_attention:
+    """``with ops.capture_attention() as seen:`` -- while it is active every ``attn_fwd`` appends ``(qkv, B, N, H, HD, scale)`` to
+    ``seen``: the tensor it was given, no copy (the caller decides how long it lives: L * B * N * 3C * 2 bytes for a trunk of L
+    blocks).  Off by default, and off it is one ``is None`` test: no launch, no allocation, not a bit of any output.  One hook for
+    ``AttentionFn``, ``BlockFn`` and the SLIViT head (``saliency.attention_rollout`` reads it).  Not re-entrant across threads; a nested
+    use captures into the inner list and restores the outer one."""
+
+    def __enter__(self) -> list:
+        global _ATTN_CAPTURE
+        self._outer = _ATTN_CAPTURE
+        _ATTN_CAPTURE = seen = []
+        return seen
+
+    def __exit__(self, *exc):
+        global _ATTN_CAPTURE
+        _ATTN_CAPTURE = self._outer
+        return False
+
+
 def attn_fwd(qkv: torch.Tensor, B: int, N: int, H: int, HD: int, scale: float, optimistic: Optional[bool] = None):
+    if _ATTN_CAPTURE is not None:
+        _ATTN_CAPTURE.append((qkv, B, N, H, HD, scale))
     o = torch.empty((B * N, H * HD), dtype=BF16, device=qkv.device)
     lse = torch.empty((B, H, N), dtype=F32, device=qkv.device)
     opt = ATTN_OPTIMISTIC if optimistic is None else optimistic
@@ -1924,6 +1948,64 @@ def heatmap(m: torch.Tensor, size) -> torch.Tensor:
     out = torch.empty((Bn, Fo, Ho, Wo), dtype=torch.uint8, device=m.device)
     _launch("heatmap", 0.0, 4.0 * m.numel() + float(out.numel()),
             lambda: call("octmae_heatmap", m.data_ptr(), mnmx.data_ptr(), out.data_ptr(), Bn, t, h, w, Fo, Ho, Wo, _stream()))
+    return out
+
+
+ROLLOUT_FUSIONS = ("mean", "max", "min")    # the `fusion` codes 0, 1, 2 of octmae_rollout_step
+ROLLOUT_MAX_HD = 128                        # RO_MAX_HD of csrc/rollout.hip
+
+
+def rollout_step(q: torch.Tensor, k: torch.Tensor, B: int, N: int, H: int, HD: int, scale: float, r: torch.Tensor,
+                 head_fusion: str = "mean", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One block of attention rollout as a vector step (csrc/rollout.hip): float32 [B, N]
+
+        r_out[b, j] = sum_i (r[b, i] / rho[b, i]) * (F[b, i, j] + [i == j])
+
+    with ``P^h = softmax_j(scale * q_i . k_j)`` recomputed on the f32 MFMA tile of csrc/simtile.hpp, ``F = head_fusion_h P^h`` ("mean",
+    "max" or "min") and ``rho = 1 + sum_j F`` (2 for "mean").  ``q``, ``k``: float32 [B * N, H * HD] (row b * N + i, head h at columns
+    h * HD ..), unit column stride, any row stride >= H * HD -- the two thirds of a widened packed ``qkv`` are such slices.  ``r``:
+    float32 [B, N], contiguous; ``out`` (optional): the same, another buffer.  Nothing of size [N, N] is stored; the workspace is
+    (H + 1 + split) * B * N floats.  No atomics: two calls give the same bits, and a sample's row does not depend on the batch around
+    it.  A non-finite ``q`` or ``k`` comes out as NaN.  No autograd; no 16-bit operand, so autocast changes nothing."""
+    name = "rollout_step"
+    B, N, H, HD = int(B), int(N), int(H), int(HD)
+    if head_fusion not in ROLLOUT_FUSIONS:
+        raise ValueError(f"{name}: head_fusion should be one of {ROLLOUT_FUSIONS}, got {head_fusion!r}")
+    if min(B, N, H) < 1 or not 1 <= HD <= ROLLOUT_MAX_HD:
+        raise ValueError(f"{name}: B, N, H >= 1 and 1 <= HD <= {ROLLOUT_MAX_HD} expected, got B={B}, N={N}, H={H}, HD={HD}")
+    operands = ((q, "q"), (k, "k"), (r, "r")) + (((out, "out"),) if out is not None else ())
+    for t, nm in operands:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{name}: {nm} must be a GPU tensor (the HIP path has no CPU fallback)")
+        if t.dtype != F32:
+            raise TypeError(f"{name}: {nm} must be float32, got {t.dtype}")
+        if t.device != q.device:
+            raise ValueError(f"{name}: {nm} is on {t.device}, q on {q.device}")
+    q, k, r = q.detach(), k.detach(), r.detach()
+    W = H * HD
+    for t, nm in ((q, "q"), (k, "k")):
+        if tuple(t.shape) != (B * N, W):
+            raise ValueError(f"{name}: {nm} must be [B * N, H * HD] = [{B * N}, {W}], got {tuple(t.shape)}")
+        if (W > 1 and t.stride(1) != 1) or (B * N > 1 and t.stride(0) < W):
+            raise ValueError(f"{name}: {nm} needs unit column stride and a row stride >= {W}, got strides {tuple(t.stride())}")
+    for t, nm in operands[2:]:
+        if tuple(t.shape) != (B, N) or not t.is_contiguous():
+            raise ValueError(f"{name}: {nm} must be a contiguous [{B}, {N}] tensor, got {tuple(t.shape)} with strides {tuple(t.stride())}")
+    if out is None:
+        out = torch.empty((B, N), dtype=F32, device=q.device)
+    elif out.requires_grad or out.data_ptr() == r.data_ptr():
+        raise ValueError(f"{name}: out must be a buffer of its own that needs no gradient")
+    fusion = ROLLOUT_FUSIONS.index(head_fusion)
+    nws = int(load().octmae_rollout_ws(B, N, H, fusion))
+    if nws < 0:
+        raise ValueError(f"{name}: B = {B}, N = {N}, H = {H} is beyond the kernel's workspace query")
+    ws = torch.empty(nws, dtype=torch.uint8, device=q.device)
+    sq, sk = (q.stride(0) if B * N > 1 else W), (k.stride(0) if B * N > 1 else W)
+    walks = 2 if fusion == 0 else 3
+    # algorithmic HBM bytes: q and k read once per walk (the re-reads per tile hit the caches), the statistics written and read
+    _launch(f"{name}_{head_fusion}", walks * 2.0 * B * H * N * N * HD, float(walks * 8 * B * N * W + 8 * B * H * N + 8 * B * N),
+            lambda: call("octmae_rollout_step", q.data_ptr(), sq, k.data_ptr(), sk, B, N, H, HD, float(scale), fusion, r.data_ptr(),
+                         out.data_ptr(), ws.data_ptr(), nws, _stream()))
     return out
 
 

@@ -10,9 +10,12 @@ The reference ships a Grad-CAM base class over ``pytorch_grad_cam`` (retinal-COE
     grad_cam_multimodal(model, inputs, target=None, *, layers=-1, single_modality=None)
                                                                -> dict(logits, target, cam = {modality: map or None})
                                                                   for the COEM classifiers; the same three switches, dicts per modality
+    attention_rollout(model, x, *, head_fusion="mean", start=None, first_layer=0)
+                                                               -> dict(logits, tokens, rollout): class-free, no backward pass; the
+                                                                  reference has no counterpart (csrc/rollout.hip)
     heatmap(map, size)                                         -> uint8 [B, F, H, W]   ([B, H, W] for 2-D maps)
 
-Both passes run the model in ``eval()`` mode under ``torch.enable_grad()`` and ``ops.weight_grads(False)``: the backward launches the
+The gradient passes run the model in ``eval()`` mode under ``torch.enable_grad()`` and ``ops.weight_grads(False)``: the backward launches the
 activation-gradient kernels only, so no ``p.grad``, no gradient arena and no registered reducer is touched -- a saliency pass may sit
 between two accumulation micro-steps.  The score is ``sum_b logits[b, target[b]]``; ``target=None`` takes the arg-max class of every
 sample (pytorch_grad_cam's ClassifierOutputTarget default), a one-column head (regression, one-logit binary) column 0.
@@ -23,7 +26,8 @@ a fixed number of power iterations (``ops.cam_eigen``) with a stated sign -- the
 CAM, where the reference keeps whatever sign LAPACK's SVD returns -- and a ``residual`` that tells an unconverged map.  Augmentation
 smoothing runs the reference's six default passes one after the other, normalises each COARSE map, mirrors it back along W and averages
 (``ops.cam_accumulate``); the flip takes the last axis of volumes too (ttach's ``flip(3)`` is H there).  Still out: several target layers
-per tower averaged (``aggregate_multi_layers``), ``cv2.resize`` and the matplotlib side.
+per tower averaged (``aggregate_multi_layers``), ``cv2.resize`` and the matplotlib side; for ``attention_rollout`` a ``discard_ratio``, a
+gradient-weighted rollout and both COEM towers in one call.
 """
 from __future__ import annotations
 
@@ -32,7 +36,7 @@ import torch
 from . import ops
 from ._autocast import no_autocast
 
-__all__ = ["input_gradient", "grad_cam", "grad_cam_multimodal", "heatmap"]
+__all__ = ["input_gradient", "grad_cam", "grad_cam_multimodal", "attention_rollout", "heatmap"]
 
 
 def _logits_of(out):
@@ -332,6 +336,77 @@ def grad_cam_multimodal(model, inputs, target=None, *, layers=-1, single_modalit
         res["activations"] = {n: (streams[n][0] if n in present else None) for n in names}
         res["gradients"] = {n: (streams[n][1] if n in present else None) for n in names}
     return res
+
+
+def _rollout_start(model, start, Bn, N, n_prefix, dev):
+    """the start row w float32 [B, N]: given, or the row the model's own pooling reads"""
+    if start is None:
+        w = torch.zeros((Bn, N), dtype=torch.float32, device=dev)
+        if getattr(model, "global_pool", False):
+            w[:, n_prefix:] = 1.0 / (N - n_prefix)          # the head reads the mean of the patch tokens
+        else:
+            w[:, 0] = 1.0                                   # the head reads the class token
+        return w
+    if not isinstance(start, torch.Tensor) or tuple(start.shape) != (Bn, N):
+        raise ValueError(f"attention_rollout: start must be a tensor [{Bn}, {N}] (one weight per token, prefix first)")
+    w = start.detach().to(dev, torch.float32).contiguous()
+    if not bool((torch.isfinite(w) & (w >= 0)).all()):
+        raise ValueError("attention_rollout: start must be finite and non-negative")
+    return w.clone() if w.data_ptr() == start.data_ptr() else w
+
+
+@no_autocast
+def attention_rollout(model, x, *, head_fusion: str = "mean", start=None, first_layer: int = 0) -> dict:
+    """Attention rollout (Abnar & Zuidema 2020) for the classes ``grad_cam`` knows: how much of the start row's attention reaches
+    every input token when the attention matrices of the blocks are multiplied through, the residual connection counted as an
+    identity.  Per block l: P_l^h = softmax(scale q k^T) from the 16-bit q, k that the model's own attention consumed in this forward,
+    F_l = ``head_fusion`` over the heads ("mean", "max", "min"), Ahat_l = (F_l + I) / rowsum, R = Ahat_L ... Ahat_{first_layer + 1};
+    the map is ``start^T R``.  Only that row is computed: L vector steps of ``ops.rollout_step``, each a weighted column sum of a
+    softmax that is recomputed on f32 MFMA tiles and never stored -- no [B, H, N, N] array exists, no atomics, two calls give the same
+    bits.
+
+    What it is not: it uses no class score and no gradient, so it says where attention flows, not what moved a logit (``grad_cam``
+    does that, and needs a head); it ignores the MLPs, the LayerNorms and the value vectors.  That is also why it works for an encoder
+    without a head -- an MAE-pre-trained trunk, a COEM tower, any checkpoint in between -- as long as ``model(x)`` runs.
+
+    ``start=None`` follows the model's pooling: the class-token row where the head reads the class token, uniform over the patch tokens
+    where ``global_pool`` averages them.  A float tensor [B, N] (prefix first) is used as given; a negative or non-finite entry raises.
+    ``first_layer``: the blocks below it are left out of the product.  One forward under ``no_grad`` in eval mode inside
+    ``ops.capture_attention()``; the captured ``qkv`` stay alive until the chain is done: L * B * N * 3C * 2 bytes (755 MB per ViT-L
+    volume of 5121 tokens), plus one block's widened q | k (42 MB per volume) at a time.
+
+    Returns ``logits`` (whatever ``model(x)`` returns first), ``tokens`` float32 [B, N] (sums to sum(start) per sample) and ``rollout``
+    float32 [B, *grid]: the patch tokens of ``tokens``, prefix dropped, as ``heatmap`` takes a CAM."""
+    blocks, grid = _cam_grid(model, x)
+    if head_fusion not in ops.ROLLOUT_FUSIONS:
+        raise ValueError(f"attention_rollout: head_fusion should be one of {ops.ROLLOUT_FUSIONS}, got {head_fusion!r}")
+    depth = len(blocks)
+    first_layer = int(first_layer)
+    if not 0 <= first_layer < depth:
+        raise ValueError(f"attention_rollout: first_layer must lie in [0, {depth}), got {first_layer}")
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("saliency: x must be a GPU tensor (the HIP path has no CPU fallback)")
+    with _Quiet(model), torch.no_grad(), ops.capture_attention() as seen:
+        logits = _logits_of(model(x.detach().float().contiguous()))
+    if len(seen) != depth or len({e[1:5] for e in seen}) != 1:
+        raise RuntimeError(f"attention_rollout: the forward ran {len(seen)} attention launches of shapes "
+                           f"{sorted({e[1:5] for e in seen})}; one per block ({depth}) of one (B, N, H, HD) expected")
+    _, Bn, N, H, HD, _ = seen[0]
+    L = 1
+    for v in grid:
+        L *= v
+    n_prefix = N - L
+    if n_prefix < 0 or Bn != x.shape[0]:
+        raise RuntimeError(f"attention_rollout: the blocks ran at {Bn} x {N} tokens, the token grid {grid} of {x.shape[0]} samples needs {L}")
+    r = _rollout_start(model, start, Bn, N, n_prefix, x.device)
+    C = H * HD
+    for layer in range(depth - 1, first_layer - 1, -1):
+        qkv, _, _, _, _, scale = seen[layer]
+        qk = qkv.detach().view(Bn * N, 3 * C)[:, :2 * C].float()          # widening 16 bits to f32 is exact
+        r = ops.rollout_step(qk[:, :C], qk[:, C:], Bn, N, H, HD, scale, r, head_fusion)
+        seen[layer] = None                                               # one block's qkv less to hold
+        del qkv, qk
+    return {"logits": logits.detach(), "tokens": r, "rollout": r[:, n_prefix:].reshape(Bn, *grid)}
 
 
 @no_autocast
