@@ -72,7 +72,11 @@ extern "C" {
  *     octmae_wgrad_fold's kernel instead of fp32 atomics (octmae_wgrad_accum_pair_ws, octmae_wgrad_det_ws_bytes, octmae_gemm_plan_ws,
  *     octmae_wgrad_pair_plan_ws), the gradient norm through per-chunk partials (octmae_mt_sumsq_ws, octmae_mt_adamw_fused_ws).
  *     Added under 35 (new entry points only; no caller of an earlier 35 breaks): octmae_rollout_step (+ octmae_rollout_ws), one step of
- *     attention rollout as a weighted column sum of a recomputed softmax off the tiles of 19 (csrc/rollout.hip). */
+ *     attention rollout as a weighted column sum of a recomputed softmax off the tiles of 19 (csrc/rollout.hip).
+ *     Added under 35 in the same way: octmae_cover_accumulate, octmae_cover_finish, the per-token sums of the masked predictions over
+ *     complementary masks and their finishing pass into a reconstruction volume, a squared-error volume and token scores
+ *     (csrc/cover.hip).  The number stays 35 because tests/test_cpu_deterministic.py pins it; the next change to an existing entry
+ *     point takes 36. */
 #define OCTMAE_ABI_VERSION 35
 int octmae_abi_version(void);
 
@@ -531,6 +535,42 @@ int octmae_mae_compose_nc(const float* pred, long long pred_batch_stride, const 
 int octmae_white_border_ws_floats(int B, int T, int H, int W);
 int octmae_white_border(float* imgs, uint8_t* region, float* ws, int B, int T, int H, int W, int left_idle_from, int left_ext_from,
                         int right_live_from, int right_ext_below, void* stream);
+
+/* ---- full-coverage reconstruction and error maps of the 3-D MAE (csrc/cover.hip) -----------------------
+ * No counterpart in the reference, whose validation pass predicts the masked three quarters of a volume once.  K forwards over
+ * complementary masks (models_mae.cover_noise) hide every token at least once; the masked predictions are summed per token and one
+ * finishing pass gives the mean prediction as grey levels, its squared error against the scan and a score per token.
+ * Shapes and conventions are octmae_mae_compose's: one channel; pred f32 [L][PD] per sample, PD = u_sz * p * p, samples
+ * pred_batch_stride FLOATS apart (>= L * PD, a multiple of 4: the [:, 1:, :] view of the decoder's output is read in place); mask f32
+ * [B][L], != 0 = removed; frame_idx NULL or Tp int32 source frames, clamped on the device; 64-bit element offsets, token rows in int.
+ *
+ * octmae_cover_accumulate: one pass into the running sums.
+ *   sum   f32 [B][L][PD], contiguous, 16-byte aligned;  cnt int32 [B][L]
+ *   first != 0: every row is written -- a removed token's row of sum is its row of pred (a copy) and its cnt 1, every other row is
+ *               +0.0f and its cnt 0; nothing has to be zeroed in front.
+ *   first == 0: a removed token gets sum += pred (one fp32 add per element) and cnt += 1; the rows of the other tokens are neither read
+ *               from pred nor written.  Pass by pass the result has the bits of torch.where(mask, sum + pred, sum).
+ * -1: NULL / non-positive / misaligned arguments, PD % 4, a batch stride below L * PD or not a multiple of 4, pred == sum.
+ * -2: more than 2^31 - 1 tokens.
+ *
+ * octmae_cover_finish: the sums into volumes.  For a token with cnt > 0:
+ *   v      = sum / (float) cnt, a correctly rounded fp32 division; with denorm == 1 then v = fma(v, sqrt(var + 1e-6), mean) with the
+ *            mean / unbiased variance of the token's target patch, the arithmetic of octmae_mae_compose with denorm == 1
+ *   recon  uint8 [B][Tp][H][W] = g(v), un-shuffled from (t, h, w | u, py, px) to (frame, y, x): what panel 2 of octmae_mae_compose
+ *            holds for pred = v (g: see there; a non-finite v gives 0)
+ *   err    f32 [B][Tp][H][W] or NULL: d * d with d = v - x, x the source frame's voxel; the subtraction and the product each rounded on
+ *            their own (no fused multiply-add in any formula of this entry point but the denorm one above)
+ *   score  f32 [B][L] or NULL: the mean of the token's PD squared errors (computed whether or not err is stored): per lane the float4
+ *            groups q = lane, lane + 64, ... as ((e0 + e1) + (e2 + e3)) added in ascending order, the 64 lanes by the wave reduction,
+ *            one division by PD.  A fixed order: two calls give the same bits.
+ * A token with cnt == 0 draws the input: recon = g(x), err = 0, score = 0.  No atomics; a token's outputs depend on its own inputs only.
+ * -1: NULL sum / cnt / imgs / recon, non-positive or misaligned arguments (sum, imgs, err: 16 bytes), p % 4, W % 4, PD % 4, H % p,
+ * W % p, L not a multiple of the (H/p) * (W/p) grid, more predicted frames than T without frame_idx.
+ * -2: denorm outside {0, 1}, more than 2^31 - 1 tokens.  Same code in the two builds of the library. */
+int octmae_cover_accumulate(const float* pred, long long pred_batch_stride, const float* mask, float* sum, int* cnt, int B, int L, int PD,
+                            int first, void* stream);
+int octmae_cover_finish(const float* sum, const int* cnt, const float* imgs, const int* frame_idx, uint8_t* recon, float* err, float* score,
+                        int B, int T, int H, int W, int u_sz, int p, int L, int denorm, void* stream);
 
 /* ---- saliency: input gradients, Grad-CAM, heat volumes (csrc/saliency.hip) ---------------------------
  * retinal-COEM/src/oph_vis_util/base_cam_retclip_3mod.py (the reference's Grad-CAM base class over pytorch_grad_cam) and its

@@ -255,6 +255,55 @@ def _eval_one_epoch(model, data_loader, device, epoch, log_writer, args, joint, 
     return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
 
 
+def cover_one_epoch(model: torch.nn.Module, data_loader: Iterable, device: torch.device, epoch: int, args=None, mask_ratio=None,
+                    generator=None, save_volumes=0):
+    """Full-coverage reconstruction over a validation loader (no counterpart in the reference): per batch, in the form
+    ``eval_one_epoch`` takes them (``(samples, img_names)``, a 6-D batch folded into the batch axis, a bare tensor accepted),
+    ``model.reconstruct_full(samples, mask_ratio, generator)`` -- every voxel predicted while hidden, and its squared error against
+    the scan.  One row per volume is appended to ``args.output_dir/cover_scores_<epoch>.csv``: ``index,name,volume_score,
+    max_frame_score,max_frame`` (the name is empty where the batch carries none).  ``mask_ratio=None`` means ``args.mask_ratio``.
+    ``save_volumes = n`` also writes ``recon`` and ``error`` of the first n volumes to ``cover_volumes_<epoch>.npz``.  Returns
+    ``{"volume_score": float64 [V], "frame_score": float64 [V, Tp], "max_frame": int64 [V], "names": [...], "loss": the mean of all
+    passes' losses}`` as numpy arrays.  ``reconstruct_full`` leaves the training flag and ``.grad`` as found."""
+    import numpy as np
+    inner = getattr(model, "module", model)
+    if mask_ratio is None:
+        mask_ratio = args.mask_ratio
+    os.makedirs(args.output_dir, exist_ok=True)
+    path = os.path.join(args.output_dir, f"cover_scores_{epoch}.csv")
+    vol, frm, names, losses, kept = [], [], [], [], {"recon": [], "error": []}
+    new_file = not os.path.exists(path)
+    with open(path, "a") as f:
+        if new_file:
+            f.write("index,name,volume_score,max_frame_score,max_frame\n")
+        for batch in data_loader:
+            samples, img_names = (batch[0], batch[1]) if isinstance(batch, (tuple, list)) else (batch, None)
+            samples = samples.to(device, non_blocking=True)
+            if samples.dim() == 6:
+                b, r, c, t, h, w = samples.shape
+                samples = samples.reshape(b * r, c, t, h, w)
+            n = samples.shape[0]
+            if img_names is None or isinstance(img_names, str) or len(img_names) != n:
+                img_names = [""] * n
+            out = inner.reconstruct_full(samples, mask_ratio=mask_ratio, generator=generator, error_volume=True)
+            vs, fs = out["volume_score"].cpu().numpy(), out["frame_score"].cpu().numpy()
+            losses += out["losses"]
+            for i in range(n):
+                k = int(fs[i].argmax())
+                f.write(f"{len(vol)},{str(img_names[i]).replace(',', ';')},{float(vs[i])!r},{float(fs[i, k])!r},{k}\n")
+                if len(vol) < save_volumes:
+                    kept["recon"].append(out["recon"][i].cpu().numpy())
+                    kept["error"].append(out["error"][i].cpu().numpy())
+                vol.append(float(vs[i])); frm.append(fs[i]); names.append(str(img_names[i]))
+    if save_volumes > 0 and kept["recon"]:
+        np.savez_compressed(os.path.join(args.output_dir, f"cover_volumes_{epoch}.npz"), recon=np.stack(kept["recon"]),
+                            error=np.stack(kept["error"]), names=np.array(names[:len(kept["recon"])]))
+    frame = np.stack(frm) if frm else np.zeros((0, 0))
+    return {"volume_score": np.asarray(vol, dtype=np.float64), "frame_score": frame,
+            "max_frame": frame.argmax(axis=1) if frm else np.zeros((0,), dtype=np.int64), "names": names,
+            "loss": float(np.mean(losses)) if losses else float("nan")}
+
+
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 

@@ -25,6 +25,34 @@ from .video_vit import layer_norm
 from ._autocast import autocast_invariant, no_autocast
 
 
+def cover_noise(N, L, mask_ratio, generator=None, device=None):
+    """The masking noise of ``K`` complementary passes: float32 [K, N, L] for ``forward(..., noise=noise[k])``.  With ``len_keep =
+    int(L * (1 - mask_ratio))`` (random_masking_ids') and ``K = ceil(L / len_keep)``, sample b draws one permutation ``rank[b] =
+    torch.randperm(L, generator=generator)`` on the host (in sample order) and ``noise[k, b, l] = (rank[b, l] - k * len_keep) mod L``:
+    distinct integers below 2^24, exact in fp32, so the argsort has no ties and pass k keeps exactly the tokens whose rank lies in
+    ``[k len_keep, (k + 1) len_keep) mod L``.  When len_keep divides L every token is kept once and masked K - 1 times; otherwise the
+    tokens of rank < K len_keep - L are kept in pass 0 and in pass K - 1 and masked K - 2 times.  ValueError for a schedule that cannot
+    hide every token: len_keep < 1, len_keep >= L, L >= 2^24, or K == 2 with a remainder (any ratio below 0.5 in practice)."""
+    N, L = int(N), int(L)
+    len_keep = int(L * (1 - mask_ratio))
+    if N < 1 or L < 1:
+        raise ValueError(f"cover_noise: N = {N} and L = {L} must be positive")
+    if L >= 1 << 24:
+        raise ValueError(f"cover_noise: L = {L} ranks are not all exact in float32 (L must be below 2^24 = {1 << 24})")
+    if len_keep < 1:
+        raise ValueError(f"cover_noise: mask_ratio {mask_ratio} keeps len_keep = {len_keep} of L = {L} tokens: a pass needs at least one")
+    if len_keep >= L:
+        raise ValueError(f"cover_noise: mask_ratio {mask_ratio} keeps len_keep = {len_keep} of L = {L} tokens: nothing is ever masked")
+    K = -(-L // len_keep)
+    if K == 2 and L % len_keep:
+        raise ValueError(f"cover_noise: mask_ratio {mask_ratio} gives K = 2 passes of len_keep = {len_keep} over L = {L} tokens; the "
+                         f"{2 * len_keep - L} tokens kept in both would never be masked (use a ratio of at least 0.5)")
+    rank = torch.stack([torch.randperm(L, generator=generator) for _ in range(N)])                 # int64 [N, L], host
+    shift = torch.arange(K, dtype=torch.int64).view(K, 1, 1) * len_keep
+    noise = torch.remainder(rank.unsqueeze(0) - shift, L).to(torch.float32)
+    return noise if device is None else noise.to(device)
+
+
 @autocast_invariant
 class MaskedAutoencoderViT(nn.Module):
     """Masked Autoencoder with VisionTransformer backbone"""
@@ -364,6 +392,47 @@ class MaskedAutoencoderViT(nn.Module):
                                       denorm=bool(denormalize))[..., 0]
         return ops.mae_compose(pred.float(), imgs, mask.float(), self._frame_idx(imgs.shape[2], imgs.device),
                                self.t_pred_patch_size, pe_mod.patch_size[0], bool(denormalize))
+
+    @no_autocast
+    @torch.no_grad()
+    def reconstruct_full(self, imgs, mask_ratio=0.75, generator=None, denormalize=None, error_volume=True):
+        """Every voxel predicted while it was hidden, and where that prediction disagrees with the scan (no counterpart in the
+        reference, whose validation pass predicts the masked three quarters once).  ``cover_noise`` is drawn once; each of its K
+        passes is one ``forward(imgs, mask_ratio, noise=noise[k])`` followed by one ``ops.cover_accumulate`` on the ``pred`` view it
+        returned; one ``ops.cover_finish`` turns the per-token sums into the result (csrc/cover.hip).  For the 3-D model and its 512^2
+        B-scan branch, by shape alone as ``reconstruct``; ``denormalize=None`` means ``self.norm_pix_loss``.  Returns a dict:
+        ``recon`` uint8 [N, Tp, H, W], the grey levels of the mean masked prediction; ``error`` f32 [N, Tp, H, W], its squared
+        difference from the source frames in the model's input units (None with ``error_volume=False``); ``token_score`` f32 [N, L],
+        a token's mean squared error; ``count`` int32 [N, L], how often a token was predicted; ``frame_score`` float64 [N, Tp], the mean
+        of ``error`` over a frame (None without it); ``volume_score`` float64 [N], the mean of ``token_score``; ``passes`` K; ``losses``
+        the K masked-MSE losses as floats.  The training flag and the weight-gradient buffers are left as found."""
+        if self.in_chans != 1:
+            raise NotImplementedError("reconstruct_full: one channel (as reconstruct)")
+        imgs = imgs.float().contiguous()
+        pe_mod = self.high_res_patch_embed if self._is_high_res(imgs) else self.patch_embed
+        N, _, T = imgs.shape[:3]
+        L = (T // pe_mod.t_patch_size) * pe_mod.input_size[1] * pe_mod.input_size[2]
+        noise = cover_noise(N, L, mask_ratio, generator=generator, device=imgs.device)
+        denorm = self.norm_pix_loss if denormalize is None else bool(denormalize)
+        was_training = self.training
+        no_grad_at_entry = [p for p in self.parameters() if p.grad is None]      # the arena's first forward attaches its views
+        self.eval()
+        try:
+            acc, cnt, losses = None, None, []
+            for k in range(noise.shape[0]):
+                loss, pred, mask = self(imgs, mask_ratio, noise=noise[k])
+                acc, cnt = ops.cover_accumulate(pred, mask, acc, cnt)
+                losses.append(loss)
+            recon, err, score = ops.cover_finish(acc, cnt, imgs, self._frame_idx(T, imgs.device), self.t_pred_patch_size,
+                                                 pe_mod.patch_size[0], denorm, error_volume=bool(error_volume))
+        finally:
+            self.train(was_training)
+            for p in no_grad_at_entry:
+                p.grad = None
+        return {"recon": recon, "error": err, "token_score": score, "count": cnt,
+                "frame_score": None if err is None else err.double().mean(dim=(2, 3)),
+                "volume_score": score.double().mean(dim=1), "passes": int(noise.shape[0]),
+                "losses": [float(x) for x in torch.stack(losses).tolist()]}
 
     def forward(self, imgs, mask_ratio=0.75, frame_loss=False, pre_mask=None, noise=None):
         self.prepare()

@@ -1053,6 +1053,106 @@ def mae_compose_nc(pred: torch.Tensor, imgs: torch.Tensor, mask: torch.Tensor, u
     return out
 
 
+def _cover_pred(pred: torch.Tensor, what: str):
+    """pred f32 [B, L, PD] as the entry points read it: (tensor, batch stride in floats); a view they cannot read in place is copied."""
+    if pred.dim() != 3:
+        raise RuntimeError(f"{what} pred: expected [B, L, PD], got {tuple(pred.shape)}")
+    if not pred.is_cuda or pred.dtype != F32:
+        raise RuntimeError(f"{what} pred: expected a float32 GPU tensor, got {pred.dtype} on {pred.device}")
+    Bn, L, PD = pred.shape
+    if Bn < 1 or L < 1 or PD < 4 or PD % 4:
+        raise RuntimeError(f"{what} pred: B and L must be positive and PD a positive multiple of 4, got {tuple(pred.shape)}")
+    if Bn * L > 0x7fffffff:
+        raise RuntimeError(f"{what} pred: {Bn} x {L} tokens are more than 2^31 - 1")
+    if pred.stride(2) != 1 or pred.stride(1) != PD or (Bn > 1 and (pred.stride(0) < L * PD or pred.stride(0) % 4)) or \
+            pred.data_ptr() % 16:
+        pred = pred.contiguous()
+    return pred, (pred.stride(0) if Bn > 1 else L * PD)
+
+
+def cover_accumulate(pred: torch.Tensor, mask: torch.Tensor, sum: Optional[torch.Tensor] = None, cnt: Optional[torch.Tensor] = None,
+                     first: Optional[bool] = None):
+    """One pass of the full-coverage reconstruction (csrc/cover.hip): the predictions of the tokens ``mask`` removed are added into the
+    per-token sums.  ``pred`` f32 [B, L, PD], contiguous or the ``pred_full[:, 1:, :]`` view ``forward`` returns (read in place);
+    ``mask`` f32 [B, L], != 0 = removed.  Without ``sum`` / ``cnt`` this is the first pass: both are allocated here and every row is
+    written (a removed token's row is its prediction and its count 1, every other row +0.0 and 0).  With them (f32 [B, L, PD] and int32
+    [B, L], updated in place) a removed token gets ``sum += pred`` and ``cnt += 1`` and no other row is touched: pass by pass the
+    bits of ``torch.where(mask, sum + pred, sum)``.  ``first=True`` with buffers overwrites them as the first pass does.  Returns
+    ``(sum, cnt)``.  Everything the entry point refuses is refused here first, before a launch.  No autograd."""
+    pred, bs = _cover_pred(pred.detach(), "cover_accumulate")
+    Bn, L, PD = pred.shape
+    mask = mask.detach()
+    if mask.numel() != Bn * L:
+        raise RuntimeError(f"cover_accumulate mask: expected {Bn} x {L} values, got {tuple(mask.shape)}")
+    mask = _chk(mask.reshape(Bn, L), F32, "cover_accumulate mask")
+    if (sum is None) != (cnt is None):
+        raise RuntimeError("cover_accumulate: sum and cnt are given together or not at all")
+    if first is None:
+        first = sum is None
+    if sum is None:
+        if not first:
+            raise RuntimeError("cover_accumulate: first=False needs the sum and cnt of the earlier passes")
+        sum = torch.empty((Bn, L, PD), dtype=F32, device=pred.device)
+        cnt = torch.empty((Bn, L), dtype=torch.int32, device=pred.device)
+    else:
+        _chk(sum, F32, "cover_accumulate sum"); _chk(cnt, torch.int32, "cover_accumulate cnt")
+        if tuple(sum.shape) != (Bn, L, PD) or tuple(cnt.shape) != (Bn, L) or sum.device != pred.device or cnt.device != pred.device:
+            raise RuntimeError(f"cover_accumulate: sum {tuple(sum.shape)} / cnt {tuple(cnt.shape)} do not match pred {tuple(pred.shape)}")
+        if sum.data_ptr() % 16 or sum.data_ptr() == pred.data_ptr():
+            raise RuntimeError("cover_accumulate sum: expected a 16-byte aligned buffer of its own")
+    # algorithmic HBM bytes: the mask; the first pass writes every row and reads the removed ones; a later pass reads both and writes one
+    # on the removed rows only (their number is data: counted as all rows, an upper bound)
+    _launch("cover_accumulate", 0.0, float(4 * Bn * L + 4 * Bn * L * PD * (2 if first else 3)),
+            lambda: call("octmae_cover_accumulate", pred.data_ptr(), bs, mask.data_ptr(), sum.data_ptr(), cnt.data_ptr(), Bn, L, PD,
+                         int(bool(first)), _stream()))
+    return sum, cnt
+
+
+def cover_finish(sum: torch.Tensor, cnt: torch.Tensor, imgs: torch.Tensor, frame_idx: Optional[torch.Tensor], u: int, p: int,
+                 denorm: bool = False, error_volume: bool = True, token_score: bool = True):
+    """The finishing pass of the full-coverage reconstruction (csrc/cover.hip): ``(recon, err, score)`` from the sums of
+    ``cover_accumulate``.  For a token with ``cnt > 0`` the value is ``v = sum / cnt`` (``denorm``: mapped back through the mean and
+    unbiased variance of the token's target patch first, as ``mae_compose`` does); ``recon`` uint8 [B, Tp, H, W] holds the grey levels
+    of ``v`` un-shuffled to (frame, y, x) -- panel 2 of ``mae_compose`` for ``pred = v``; ``err`` f32 [B, Tp, H, W] (None with
+    ``error_volume=False``) holds ``(v - x) ** 2`` against the source frame's voxel; ``score`` f32 [B, L] (None with
+    ``token_score=False``) the mean of a token's squared errors.  A token that was never removed draws the input: its grey levels,
+    error 0, score 0.  ``imgs`` f32 [B, 1, T, H, W]; ``frame_idx`` None or Tp int32 source frames.  Deterministic; no autograd."""
+    u, p = int(u), int(p)
+    if sum.dim() != 3 or imgs.dim() != 5 or imgs.shape[1] != 1:
+        raise RuntimeError(f"cover_finish: expected sum [B, L, PD] and imgs [B, 1, T, H, W], got {tuple(sum.shape)} and {tuple(imgs.shape)}")
+    sum, cnt = _chk(sum.detach(), F32, "cover_finish sum"), _chk(cnt.detach(), torch.int32, "cover_finish cnt")
+    imgs = _chk(imgs.detach(), F32, "cover_finish imgs")
+    Bn, L, PD = sum.shape
+    _, _, T, Hh, Ww = imgs.shape
+    if u < 1 or p < 4 or p % 4 or Ww % 4:
+        raise RuntimeError(f"cover_finish: p and W must be multiples of 4 and u positive, got u={u}, p={p}, W={Ww}")
+    if imgs.shape[0] != Bn or Bn < 1 or L < 1 or PD != u * p * p or Hh % p or Ww % p or L % ((Hh // p) * (Ww // p)):
+        raise RuntimeError(f"cover_finish: sum {tuple(sum.shape)} does not tile imgs {tuple(imgs.shape)} with u={u}, p={p}")
+    if tuple(cnt.shape) != (Bn, L) or cnt.device != sum.device or imgs.device != sum.device:
+        raise RuntimeError(f"cover_finish cnt: expected int32 {(Bn, L)} on {sum.device}, got {tuple(cnt.shape)} on {cnt.device}")
+    if Bn * L > 0x7fffffff:
+        raise RuntimeError(f"cover_finish sum: {Bn} x {L} tokens are more than 2^31 - 1")
+    if sum.data_ptr() % 16 or imgs.data_ptr() % 16:
+        raise RuntimeError("cover_finish: sum and imgs must be 16-byte aligned")
+    Tp = L // ((Hh // p) * (Ww // p)) * u
+    if frame_idx is not None:
+        _chk(frame_idx, torch.int32, "cover_finish frame_idx")
+        if frame_idx.numel() != Tp:
+            raise RuntimeError(f"cover_finish: frame_idx has {frame_idx.numel()} entries, the prediction has {Tp} frames")
+    elif Tp > T:
+        raise RuntimeError(f"cover_finish: the prediction has {Tp} frames, the volume {T}, and no frame_idx says which")
+    recon = torch.empty((Bn, Tp, Hh, Ww), dtype=torch.uint8, device=sum.device)
+    err = torch.empty((Bn, Tp, Hh, Ww), dtype=F32, device=sum.device) if error_volume else None
+    score = torch.empty((Bn, L), dtype=F32, device=sum.device) if token_score else None
+    nvox = Bn * Tp * Hh * Ww
+    # algorithmic HBM bytes: the sums, the counts and the gathered frames read (twice more with denorm), recon, err and score written
+    _launch("cover_finish", 0.0, float(4 * Bn * L * PD + 4 * Bn * L + 4 * nvox * (3 if denorm else 1) + nvox
+                                       + (4 * nvox if error_volume else 0) + (4 * Bn * L if token_score else 0)),
+            lambda: call("octmae_cover_finish", sum.data_ptr(), cnt.data_ptr(), imgs.data_ptr(), _p(frame_idx), recon.data_ptr(), _p(err),
+                         _p(score), Bn, T, Hh, Ww, u, p, L, int(bool(denorm)), _stream()))
+    return recon, err, score
+
+
 def white_border_limits(W: int):
     """The four column limits of the reference's border blanking (custom_util/misc.py:1458-1473) as integers, each found with the
     reference's own double expression: the left run is followed iff ``not (f > 0.01 * W)`` i.e. f < limits[0]; it is extended iff its
