@@ -75,8 +75,10 @@ extern "C" {
  *     attention rollout as a weighted column sum of a recomputed softmax off the tiles of 19 (csrc/rollout.hip).
  *     Added under 35 in the same way: octmae_cover_accumulate, octmae_cover_finish, the per-token sums of the masked predictions over
  *     complementary masks and their finishing pass into a reconstruction volume, a squared-error volume and token scores
- *     (csrc/cover.hip).  The number stays 35 because tests/test_cpu_deterministic.py pins it; the next change to an existing entry
- *     point takes 36. */
+ *     (csrc/cover.hip).
+ *     Added under 35 in the same way: octmae_lora_merge, octmae_lora_wgrad (+ octmae_lora_plan, octmae_lora_ws_bytes), the merged
+ *     operand of a Linear with a low-rank adapter and the adapter gradients without a weight gradient (csrc/lora.hip).
+ *     The number stays 35 because tests/test_cpu_deterministic.py pins it; the next change to an existing entry point takes 36. */
 #define OCTMAE_ABI_VERSION 35
 int octmae_abi_version(void);
 
@@ -571,6 +573,37 @@ int octmae_cover_accumulate(const float* pred, long long pred_batch_stride, cons
                             int first, void* stream);
 int octmae_cover_finish(const float* sum, const int* cnt, const float* imgs, const int* frame_idx, uint8_t* recon, float* err, float* score,
                         int B, int T, int H, int W, int u_sz, int p, int L, int denorm, void* stream);
+
+/* ---- low-rank adapters on the Block's Linears (csrc/lora.hip) -------------------------------------------
+ * No counterpart in the reference, which fine-tunes every weight.  An adapted Linear computes with W + s B A (W f32 [O][I], A f32
+ * [r][I], B f32 [O][r], s = alpha / r); its GEMMs run unchanged on a merged 16-bit operand, and the adapter gradients come from skinny
+ * products over the X and dY the weight-gradient GEMM would have read -- no [O][I] gradient exists.  rp = r rounded up to 16.
+ * The contract of every entry point below: 1 <= r <= 64; I and O are the widths of 16-bit GEMM operands, multiples of 8 (16-byte operand
+ * loads), and so are the leading dimensions ldx, ldy; W, A, out_w, X, dY, A_lp, B_lp and ws are 16-byte aligned, B, gA, gB 4-byte.
+ * -1 before any launch otherwise.  Row offsets are 64-bit ((size_t) row * ld): operands of any size (docs/OFFSET_RANGES.md).
+ *
+ * octmae_lora_merge: delta = fmaf(B[o][k], A[k][i], delta) for k = 0 .. r - 1 in that order (from +0), v = fmaf(s, delta, W[o][i]);
+ *   out_w [O][I] = v (out_is_f32 = 1) or v rounded once to the 16-bit operand type (0): the SAME v, so the cast of the f32 output has the
+ *   bits of the 16-bit output.  A_lp [rp][I] / B_lp [O][rp] (either may be NULL): A and B rounded to the operand type, +0 in rows /
+ *   columns r .. rp - 1.  With B == 0 the 16-bit output has the value of cvt(W).
+ *
+ * octmae_lora_wgrad: X [M][I] (rows ldx apart), dY [M][O] (rows ldy apart), A_lp, B_lp as written by the merge ->
+ *   gA f32 (rows ldga >= I apart; rows 0 .. r - 1 touched) += s U^T X,  U = dY B_lp   [M][rp]
+ *   gB f32 (rows ldgb >= r apart; columns 0 .. r - 1 touched) += s dY^T T,  T = X A_lp^T [M][rp]
+ *   T and U: fp32 MFMA accumulation, one rounding to the operand type.  The two outer products reduce over row chunks of
+ *   octmae_lora_plan's size; each chunk's fp32 partial is stored to a slab of ws, and g = fmaf(s, ((P_0 + P_1) + ...) + P_{n-1}, g)
+ *   in ascending chunk order.  No atomics: two calls give the same bits, in and out of deterministic mode.  gA or gB may be NULL (not
+ *   both).  This is the two-pass form: X and dY are read twice (projection, then outer products).
+ *   ws: at least *bytes of octmae_lora_ws_bytes(M, I, O, rp, &bytes), need not be initialised; ws_bytes below that: -1.
+ * octmae_lora_plan: host side only; out[0] rows per chunk (a multiple of 32, at least 256), [1] chunks, [2] / [3] the 64-column tiles of
+ *   X / dY (workgroups of the outer-product launch = ([2] + [3]) * [1]).  octmae_lora_ws_bytes: host side only, as
+ *   octmae_wgrad_det_ws_bytes; -1 on bad arguments. */
+int octmae_lora_merge(const float* W, const float* A, const float* B, float s, int O, int I, int r, void* out_w, int out_is_f32,
+                      void* A_lp, void* B_lp, void* stream);
+int octmae_lora_wgrad(const void* X, int ldx, const void* dY, int ldy, const void* A_lp, const void* B_lp, float s, int M, int I, int O,
+                      int r, float* gA, int ldga, float* gB, int ldgb, void* ws, long long ws_bytes, void* stream);
+int octmae_lora_plan(int M, int I, int O, int rp, int* out);
+int octmae_lora_ws_bytes(int M, int I, int O, int rp, long long* bytes);
 
 /* ---- saliency: input gradients, Grad-CAM, heat volumes (csrc/saliency.hip) ---------------------------
  * retinal-COEM/src/oph_vis_util/base_cam_retclip_3mod.py (the reference's Grad-CAM base class over pytorch_grad_cam) and its

@@ -7,7 +7,8 @@ from . import _lib  # noqa: F401  (does not load the shared library until first 
 from .mixup import Mixup  # noqa: F401  (the fine-tune loop's mixup_fn; host decisions + one launch of csrc/mixup.hip)
 
 from . import saliency  # noqa: F401  (input gradients, Grad-CAM and heat volumes; csrc/saliency.hip)
+from . import lora  # noqa: F401  (low-rank adapters on the fused Block: parameter-efficient fine-tuning; csrc/lora.hip)
 from .ops import set_deterministic  # noqa: F401  (deterministic mode: bit-reproducible weight gradients and gradient norm)
 
 __all__ = ["models_mae", "video_vit", "misc", "lr_sched", "engine_pretrain", "optim", "parallel", "ops", "Mixup", "saliency",
-           "set_deterministic"]
+           "lora", "set_deterministic"]

@@ -138,4 +138,7 @@ def load_pretrained(model, checkpoint, strict=False, filter_keys=(), smaller_int
             if k in own and own[k].shape != sd[k].shape:
                 print(f"Removing key {k} from pretrained checkpoint (shape {tuple(sd[k].shape)} vs {tuple(own[k].shape)})")
             del sd[k]
+    for k, v in own.items():          # low-rank adapters (octcubem_amd.lora) are no part of a pretrained checkpoint: they keep their values
+        if ".lora." in k and k not in sd:
+            sd[k] = v
     return model.load_state_dict(sd, strict=strict)

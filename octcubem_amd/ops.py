@@ -1153,6 +1153,161 @@ def cover_finish(sum: torch.Tensor, cnt: torch.Tensor, imgs: torch.Tensor, frame
     return recon, err, score
 
 
+# ------------------------------------------------------------------------------------------------
+# low-rank adapters (csrc/lora.hip)
+# ------------------------------------------------------------------------------------------------
+LORA_MAX_RANK = 64
+
+
+def lora_rp(r: int) -> int:
+    """the rank rounded up to the 16 columns of an MFMA tile: the width of the padded operand copies"""
+    return (int(r) + 15) // 16 * 16
+
+
+def _lora_gpu(name: str, t, dtype, what: str, dims: int = 2):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"{name}: {what} must be a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+    if t.dim() != dims:
+        raise ValueError(f"{name}: {what} must have {dims} dimensions, got {tuple(t.shape)}")
+    return t
+
+
+def _lora_rows(name: str, t: torch.Tensor, what: str, align: int):
+    """unit column stride, a row stride >= the width (a view into a wider buffer), the first element ``align`` bytes aligned"""
+    rows, cols = t.shape
+    if (cols > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < cols):
+        raise ValueError(f"{name}: {what} needs unit column stride and a row stride >= {cols}, got strides {tuple(t.stride())}")
+    if t.data_ptr() % align:
+        raise ValueError(f"{name}: {what} must be {align}-byte aligned")
+    return t.stride(0) if rows > 1 else cols
+
+
+def _lora_dims(name: str, O: int, I: int, r: int):
+    if not 1 <= r <= LORA_MAX_RANK:
+        raise ValueError(f"{name}: rank {r} outside 1 .. {LORA_MAX_RANK}")
+    if I < 8 or O < 8 or I % 8 or O % 8:
+        raise ValueError(f"{name}: in / out features must be positive multiples of 8 (the widths of 16-bit GEMM operands), got {I} / {O}")
+
+
+def lora_merge(W: torch.Tensor, A: torch.Tensor, B: torch.Tensor, s: float, out: torch.Tensor, A_lp: Optional[torch.Tensor] = None,
+               B_lp: Optional[torch.Tensor] = None):
+    """``out [O, I] = W + s B A`` for the fp32 master weight ``W [O, I]`` and the adapter ``A [r, I]``, ``B [O, r]`` (csrc/lora.hip):
+    ``delta`` by fused multiply-adds in ascending k, then ``v = fma(s, delta, W)``; ``out`` is float32 (``v``) or the 16-bit operand type
+    (``v`` rounded once).  ``A_lp [rp, I]`` / ``B_lp [O, rp]`` (optional) receive the adapter rounded to the operand type with zeros in
+    the padding, ``rp = lora_rp(r)``: the operands of ``lora_wgrad``.  All contiguous.  No autograd."""
+    name = "lora_merge"
+    W, A, B = (_lora_gpu(name, t.detach(), F32, nm) for t, nm in ((W, "W"), (A, "A"), (B, "B")))
+    O, I = W.shape
+    r = A.shape[0]
+    _lora_dims(name, O, I, r)
+    if tuple(A.shape) != (r, I) or tuple(B.shape) != (O, r):
+        raise ValueError(f"{name}: expected A [{r}, {I}] and B [{O}, {r}] for W {tuple(W.shape)}, got {tuple(A.shape)} and {tuple(B.shape)}")
+    rp = lora_rp(r)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype not in (F32, BF16) or tuple(out.shape) != (O, I):
+        raise ValueError(f"{name}: out must be a float32 or {BF16} GPU tensor of shape {(O, I)}")
+    tensors = [(W, "W"), (A, "A"), (B, "B"), (out, "out")]
+    for t, nm, shape in ((A_lp, "A_lp", (rp, I)), (B_lp, "B_lp", (O, rp))):
+        if t is not None:
+            _lora_gpu(name, t, BF16, nm)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name}: {nm} must be {shape}, got {tuple(t.shape)}")
+            tensors.append((t, nm))
+    for t, nm in tensors:
+        if not t.is_contiguous() or t.device != W.device:
+            raise ValueError(f"{name}: {nm} must be contiguous and on {W.device}")
+        if t.data_ptr() % (4 if nm == "B" else 16):
+            raise ValueError(f"{name}: {nm} must be 16-byte aligned")
+    esz = 4 if out.dtype == F32 else 2
+    _launch("lora_merge", 2.0 * O * I * (r + 1), float(4 * O * I + esz * O * I + 4 * r * (I + O) + 2 * rp * (I + O)),
+            lambda: call("octmae_lora_merge", W.data_ptr(), A.data_ptr(), B.data_ptr(), float(s), O, I, r, out.data_ptr(),
+                         int(out.dtype == F32), _p(A_lp), _p(B_lp), _stream()))
+    return out
+
+
+def lora_plan(M: int, I: int, O: int, rp: int):
+    """(rows per chunk, chunks, 64-column tiles of X, of dY) of ``lora_wgrad``: host-side arithmetic, no GPU is touched"""
+    import ctypes
+    out = (ctypes.c_int * 4)()
+    call("octmae_lora_plan", int(M), int(I), int(O), int(rp), out)
+    return tuple(out)
+
+
+def lora_ws_bytes(M: int, I: int, O: int, rp: int) -> int:
+    import ctypes
+    n = ctypes.c_longlong()
+    call("octmae_lora_ws_bytes", int(M), int(I), int(O), int(rp), ctypes.byref(n))
+    return n.value
+
+
+_lora_ws = {}
+
+
+def _lora_ws_for(nbytes: int, dev) -> torch.Tensor:
+    """one workspace per device and stream, grown on demand: launches on one stream run in order, so consecutive calls may share it"""
+    key = (dev.index, _stream())
+    ws = _lora_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _lora_ws[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def lora_wgrad(x: torch.Tensor, dy: torch.Tensor, A_lp: torch.Tensor, B_lp: torch.Tensor, s: float, r: int,
+               gA: Optional[torch.Tensor], gB: Optional[torch.Tensor], ws: Optional[torch.Tensor] = None):
+    """The adapter gradients of one Linear without its weight gradient (csrc/lora.hip, the two-pass form): with ``x [M, I]`` and
+    ``dy [M, O]`` (16 bit, row views of wider buffers allowed) and the padded operand copies of ``lora_merge``,
+    ``gA [r.., I] += s (dy B)^T x`` and ``gB [O, r..] += s dy^T (x A^T)`` in fp32; only the first r rows of ``gA`` and the first r columns
+    of ``gB`` are touched (views with their own row strides).  Either gradient may be None.  No atomics: a fixed order of additions."""
+    name = "lora_wgrad"
+    x, dy = _lora_gpu(name, x, BF16, "x"), _lora_gpu(name, dy, BF16, "dy")
+    _lora_gpu(name, A_lp, BF16, "A_lp"); _lora_gpu(name, B_lp, BF16, "B_lp")
+    M, I = x.shape
+    O = dy.shape[1]
+    r = int(r)
+    _lora_dims(name, O, I, r)
+    rp = lora_rp(r)
+    if dy.shape[0] != M or M < 1 or M > 2 ** 31 - 1:
+        raise ValueError(f"{name}: x {tuple(x.shape)} and dy {tuple(dy.shape)} must share a positive row count below 2^31")
+    if tuple(A_lp.shape) != (rp, I) or tuple(B_lp.shape) != (O, rp) or not A_lp.is_contiguous() or not B_lp.is_contiguous():
+        raise ValueError(f"{name}: expected contiguous A_lp {(rp, I)} and B_lp {(O, rp)}, got {tuple(A_lp.shape)} and {tuple(B_lp.shape)}")
+    if A_lp.data_ptr() % 16 or B_lp.data_ptr() % 16:
+        raise ValueError(f"{name}: A_lp and B_lp must be 16-byte aligned")
+    ldx, ldy = _lora_rows(name, x, "x", 16), _lora_rows(name, dy, "dy", 16)
+    if ldx % 8 or ldy % 8:
+        raise ValueError(f"{name}: the row strides of x and dy must be multiples of 8, got {ldx} and {ldy}")
+    if gA is None and gB is None:
+        raise ValueError(f"{name}: neither gA nor gB")
+    lda = ldb = 0
+    if gA is not None:
+        _lora_gpu(name, gA, F32, "gA")
+        if gA.shape[0] < r or gA.shape[1] != I:
+            raise ValueError(f"{name}: gA must be [>= {r}, {I}], got {tuple(gA.shape)}")
+        lda = _lora_rows(name, gA, "gA", 4)
+    if gB is not None:
+        _lora_gpu(name, gB, F32, "gB")
+        if gB.shape[0] != O or gB.shape[1] < r:
+            raise ValueError(f"{name}: gB must be [{O}, >= {r}], got {tuple(gB.shape)}")
+        ldb = _lora_rows(name, gB, "gB", 4)
+    for t, nm in ((dy, "dy"), (A_lp, "A_lp"), (B_lp, "B_lp"), (gA, "gA"), (gB, "gB")):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"{name}: {nm} is on {t.device}, x on {x.device}")
+    need = lora_ws_bytes(M, I, O, rp)
+    if ws is None:
+        ws = _lora_ws_for(need, x.device)
+    elif not ws.is_cuda or ws.device != x.device or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16 or not ws.is_contiguous():
+        raise ValueError(f"{name}: ws must be a contiguous 16-byte aligned buffer of at least {need} bytes on {x.device}")
+    _, nchunks, _, _ = lora_plan(M, I, O, rp)
+    both = int(gA is not None) + int(gB is not None)
+    # per wanted gradient: one operand read by its projection and the other by its outer product (both gradients: X and dY twice),
+    # T or U written and read, its half of the slabs written and read, the gradient read and written
+    flops = 2.0 * M * rp * (I + O) * both
+    nbytes = 2.0 * M * (I + O) * both + 4.0 * M * rp * both + 4.0 * nchunks * rp * (I + O) * both + 4.0 * r * (I + O) * both
+    _launch("lora_wgrad", flops, nbytes,
+            lambda: call("octmae_lora_wgrad", x.data_ptr(), ldx, dy.data_ptr(), ldy, A_lp.data_ptr(), B_lp.data_ptr(), float(s), M, I, O, r,
+                         _p(gA), lda, _p(gB), ldb, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()))
+
+
 def white_border_limits(W: int):
     """The four column limits of the reference's border blanking (custom_util/misc.py:1458-1473) as integers, each found with the
     reference's own double expression: the left run is followed iff ``not (f > 0.01 * W)`` i.e. f < limits[0]; it is extended iff its
@@ -2570,8 +2725,11 @@ class BlockFn(torch.autograd.Function):
     in split-K weight gradients that add fp32 atomically, at large sizes).  The stochastic-depth factors are the saved ones, never redrawn."""
 
     @staticmethod
-    def forward(ctx, x, H, eps1, eps2, lp, grads, s1, s2, final_residual, recompute, *params):
-        """s1 / s2: None, or fp32 [B] per-sample stochastic-depth factors (0 or 1/keep_prob) of the attention / MLP branch.
+    def forward(ctx, x, H, eps1, eps2, lp, grads, s1, s2, final_residual, recompute, lora, *params):
+        """lora: None, or the adapter bundle of an adapted Block (octcubem_amd.lora.LoraBundle): its ``lp`` -- the merged operands
+        W + s B A of the adapted Linears, written by ops.lora_merge -- replaces ``lp``, and the backward produces the adapter gradients
+        (ops.lora_wgrad) and NO gradient of a base parameter of this Block (class docstring of LoraBundle).
+        s1 / s2: None, or fp32 [B] per-sample stochastic-depth factors (0 or 1/keep_prob) of the attention / MLP branch.
         final_residual=False returns the MLP branch alone (flash_compat: what flash-attn's prenorm Block hands back as
         ``hidden_states`` and the reference's flash models feed to the final norm, models_mae_joint_res_flash_attn.py:480-489)."""
         if recompute not in (RECOMPUTE_NONE, RECOMPUTE_LIGHT, RECOMPUTE_FULL):
@@ -2583,6 +2741,9 @@ class BlockFn(torch.autograd.Function):
         scale = HD ** -0.5
         if _grad_sidecar:
             _sidecar_purge()
+        if lora is not None:
+            lp = lora.lp
+        ctx.lora = lora
         wqkv, bqkv, wproj, bproj, w1, b1, w2, b2 = lp
         g1, be1, g2, be2 = params[0], params[1], params[2], params[3]
         x2d = _chk(x.reshape(-1, C), F32, "block input")
@@ -2622,7 +2783,11 @@ class BlockFn(torch.autograd.Function):
                     x2d, Bn, N, H, HD, scale, *ctx.eps, (wqkv, bqkv, wproj, bproj, w1, b1), (g1, be1, g2, be2), s1, ctx.pre_is_dgelu)
         else:
             x2d, mean1, rstd1, y1, qkv, o, lse, x2, mean2, rstd2, y2, pre, act, wqkv, wproj, w1, w2, g1, g2, *betas = ctx.saved_tensors
-        wg = _weight_grads      # off: every parameter-gradient side output below is a null pointer, the launches are the same
+        lora = ctx.lora
+        awg = _weight_grads and lora is not None      # adapter gradients at the two weight-gradient sites
+        # off: every parameter-gradient side output below is a null pointer, the launches are the same.  An adapted Block never
+        # produces a gradient of a base parameter: its side outputs are the null pointers of the switched-off path.
+        wg = _weight_grads and lora is None
         (gg1, gb1n, gg2, gb2n, gwqkv, gbqkv, gwproj, gbproj, gw1, gb1, gw2, gb2) = ctx.grads() if wg else (None,) * 12
         if dx3.dtype != F32 or not dx3.is_contiguous():
             dx3 = dx3.contiguous().float()
@@ -2649,6 +2814,15 @@ class BlockFn(torch.autograd.Function):
                 act = gelu_apply(pre) if act is None else act
                 y2 = ln_apply(x2, mean2, rstd2, g2, betas[1])
             linear_wgrad_accum_pair((d3b, act, gw2, None), (dpre, y2, gw1, None))
+        elif awg and (lora.has("fc1") or lora.has("fc2")):
+            if ctx.recompute == RECOMPUTE_LIGHT:      # rebuilt only for the adapters that read them
+                if lora.has("fc2"):
+                    act = gelu_apply(pre) if act is None else act
+                if lora.has("fc1"):
+                    y2 = ln_apply(x2, mean2, rstd2, g2, betas[1])
+            lora.wgrad("fc2", act, d3b)
+            lora.wgrad("fc1", y2, dpre)
+        if wg or awg:
             act = y2 = None
         dy2 = linear_dgrad(dpre, w1)
         # ---- LN2 backward + residual add + bf16 copy + proj bias gradient
@@ -2673,15 +2847,22 @@ class BlockFn(torch.autograd.Function):
             if ctx.recompute == RECOMPUTE_LIGHT:
                 y1 = ln_apply(x2d, mean1, rstd1, g1, betas[0])
             linear_wgrad_accum_pair((dx2b, o, gwproj, None), (dqkv, y1, gwqkv, gbqkv))
+        elif awg and (lora.has("proj") or lora.has("qkv")):
+            if ctx.recompute == RECOMPUTE_LIGHT and lora.has("qkv"):
+                y1 = ln_apply(x2d, mean1, rstd1, g1, betas[0])
+            lora.wgrad("proj", o, dx2b)
+            lora.wgrad("qkv", y1, dqkv)
         dy1 = linear_dgrad(dqkv, wqkv)
         # ---- LN1 backward + residual add; its bf16 copy / column sums are what the previous Block's backward needs
         colsum = torch.zeros(C, dtype=F32, device=dx3.device)
         dx, dxb = layernorm_bwd(dy1, x2d, mean1, rstd1, g1, gg1, gb1n, dres=dx2, want_bf16=True, dxsum=colsum)
         if wg:
             notify_grad_ready(ctx.params)
+        elif awg:
+            notify_grad_ready(lora.params)
         dx = dx.view(shp)
         _sidecar_put(dx, dxb.view(shp), colsum)
-        return (dx, None, None, None, None, None, None, None, None, None) + (None,) * len(ctx.params)
+        return (dx, None, None, None, None, None, None, None, None, None, None) + (None,) * len(ctx.params)
 
 
 class EncAssembleFn(torch.autograd.Function):

@@ -346,6 +346,11 @@ class Block(nn.Module):
             object.__setattr__(self, "_views", (arena, (wqkv, bqkv, wproj, bproj, w1, b1, w2, b2), grads, params))
         return self._views
 
+    def _lora_bundle(self):
+        """None, or the merged operands and adapter tables of this forward (octcubem_amd.lora.attach registers ``self.lora``)"""
+        ad = self._modules.get("lora")
+        return None if ad is None else ad.bundle(self)
+
     def forward(self, x, final_residual=True, return_stream=False):
         """``final_residual=False`` (flash_compat, last block only): return the MLP branch without the residual stream;
         with ``return_stream`` also the stream it would have been added to, as a pair."""
@@ -360,8 +365,11 @@ class Block(nn.Module):
             s1 = s2 = None
             if not no_drop:     # stochastic depth: one keep/drop draw per sample and branch, folded into the residual epilogues
                 s1, s2 = self.drop_path.sample(x.shape[0], x.device), self.drop_path.sample(x.shape[0], x.device)
+            bundle = self._lora_bundle()
+            if bundle is not None:
+                params = params + bundle.params
             out = ops.BlockFn.apply(x, self.attn.num_heads, self.norm1.eps, self.norm2.eps, lp, grads, s1, s2, final_residual,
-                                    _recompute_level(self.recompute), *params)
+                                    _recompute_level(self.recompute), bundle, *params)
             if final_residual:
                 return out
             return out if return_stream else out[0]
@@ -461,8 +469,11 @@ class FlashBlock(Block):
         s1 = None
         if self.training and self.drop_path2.drop_prob > 0.0:
             s1 = self.drop_path2.sample(x.shape[0], x.device)
+        bundle = self._lora_bundle()
+        if bundle is not None:
+            params = params + bundle.params
         return ops.BlockFn.apply(x, self.mixer.num_heads, self.norm1.eps, self.norm2.eps, lp, grads, s1, None, False,
-                                 _recompute_level(self.recompute), *params)
+                                 _recompute_level(self.recompute), bundle, *params)
 
 
 def create_block(embed_dim, num_heads, mlp_ratio, qkv_bias, drop_rate, attn_drop_rate, drop_path1, drop_path2, norm_layer,
