@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Generates octcubem_amd/csrc/attn_bwd1w_body.inc: the hand-placed tile body of the one-wave-per-SIMD attention backward
-(csrc/attn_bwd1w.hip).  The body of one 64-query tile = two 32-query sub-steps; each sub-step is a list of BUNDLES -- one MFMA
-followed by the vector / LDS instructions placed in its shadow -- pinned with __builtin_amdgcn_sched_barrier(0) between bundles,
-so the order below IS the order of the emitted instruction stream (the compiler still allocates registers, inserts the
-s_waitcnt for its own LDS reads and pads MFMA hazards).  The placement follows MI355X_MICROARCH.md, 'vector-instruction ISSUE
-cost': an MFMA holds the issue port 8 of its 32 cycles, v_exp_f32 8, v_mul / v_cvt_pk 4-5, LDS 4-13; fillers are dealt to the
-MFMA slots so that every bundle costs about the same, in dependency order.
+"""Generates the hand-placed tile bodies and drains of the one-wave-per-SIMD attention backward kernels:
+octcubem_amd/csrc/attn_bwd1w_body.inc, attn_bwd1w_drain.inc (csrc/attn_bwd1w.hip, head_dim 32) and attn_bwd1w_body_hd64.inc,
+attn_bwd1w_drain_hd64.inc (csrc/attn_bwd1w64.hip, head_dim 64).  The body of one 64-query tile = two 32-query sub-steps; each
+sub-step is a list of BUNDLES -- one MFMA followed by the vector / LDS instructions placed in its shadow -- pinned with
+__builtin_amdgcn_sched_barrier(0) between bundles, so the order below IS the order of the emitted instruction stream (the compiler
+still allocates registers, inserts the s_waitcnt for its own LDS reads and pads MFMA hazards).  The placement follows
+MI355X_MICROARCH.md, 'vector-instruction ISSUE cost': an MFMA holds the issue port 8 of its 32 cycles, v_exp_f32 8, v_mul /
+v_cvt_pk 4-5, LDS 4-13; fillers are dealt to the MFMA slots so that every bundle costs about the same, in dependency order.
 
-Software pipeline of sub-step i (32 queries x this wave's 128 keys), group-step g = 0..3 (32 keys each):
+Software pipeline of sub-step i at head_dim 32 (32 queries x this wave's 128 keys), group-step g = 0..3 (32 keys each):
     C1(g-1)  dV^T, dK^T += (second 16 queries of the previous group)          2 MFMA   (accumulators in AGPRs, inline asm)
     A(g+1)   S, dP of the NEXT group (for g = 3: group 0 of the next sub-step)  4 MFMA
     B(g)     exp2, dS = P * dP, bf16 conversions, dS -> private LDS image       48 VALU + 4 ds_write
@@ -19,13 +20,18 @@ Software pipeline of sub-step i (32 queries x this wave's 128 keys), group-step 
     g = 2: row constants and Q / dO row fragments of the next sub-step (after A(3) has consumed the current ones)
     g = 3: transposed Q / dO fragments of the next sub-step
     end:  s_waitcnt lgkmcnt(0); s_barrier
-Run: python tools/gen_attn_bwd1w.py [--report]   (writes the .inc next to the kernel; --report prints the bundle table)
+(head_dim 64: sub_step64.)  The stages the two head dims share are emitted by the helpers above the two tables.  Timing-only
+ablations wrap single statements in the ABL_*() macros of csrc/attn_bwd1w.hpp; every body opens with static_asserts of what its
+kernel's vmcnt ring and LDS layout must agree with.
+Run: python tools/gen_attn_bwd1w.py [--report | --report64 | --check]   (writes the .inc files next to the kernels; --report prints
+the bundle table)
 """
 import os
 import sys
 
-IMG_BUF = 512 * 64        # bytes of one dS image: [512 keys][32 queries] bf16
-IMG_BUF64 = 256 * 64      # head_dim 64: [256 keys][32 queries]
+IMG_KSTEP = 32 * 64       # bytes of one k-step (32 keys) of a dS image: 64-byte rows
+OLD_QUAD = 4096           # bytes between the workspace-value quads of two 16-query tiles / two sub-tiles in the OLD buffers
+WS_QT = 4096              # head_dim 64: bytes from a wave's first 16-query tile to its second in the fp32 workspace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "octcubem_amd", "csrc", "attn_bwd1w_body.inc")
@@ -90,12 +96,71 @@ def merge(mf, F, need, bundles, issued_m):
         raise RuntimeError("fillers left over: " + " ".join(op.tag for op, _ in pending))
 
 
+# ---- the stages both head dims share.  `add(kind, code, after=None, tag="")` appends a filler to the group-step's list; `nqt` = 16-query
+# tiles of dQ^T a wave owns (1 at head_dim 32, 2 at 64); at nqt = 1 the tags carry no tile index (the bundle tables are the record).
+
+def image_reads(add, j, rb, nqt, after=None):
+    """B operands of the dQ^T product, k-step j: transposed reads of the previous sub-step's dS image (at byte rb)."""
+    for qt in range(nqt):
+        x, q = (" ^ 32u" if qt else ""), (f"q{qt}" if nqt > 1 else "")
+        add("ldsr", f"const bf16x4 bj{j}q{qt}l = lds_tr_ld((a_imglo{x}) + {rb + j * IMG_KSTEP});", after=after, tag=f"RD{j}{q}l")
+        add("ldsr", f"const bf16x4 bj{j}q{qt}h = lds_tr_ld((a_imghi{x}) + {rb + j * IMG_KSTEP});", after=after, tag=f"RD{j}{q}h")
+
+
+def old_reads(add, s, nqt):
+    """Write-out, first part: the workspace values of the earlier key blocks for the tile(s) finished in the previous sub-step."""
+    add("vaddr", "const unsigned ao = a_old + s_oldr;", tag="AO")
+    for qt in range(nqt):
+        add("ldsr", f"const f32x4 rold{qt} = lds_ld<f32x4>(ao + {(s * nqt + qt) * OLD_QUAD});", tag=f"ROLD{qt if nqt > 1 else ''}")
+
+
+def write_out(add, s, nqt, dqo):
+    """Write-out, second part: old value + finished tile -> workspace.  Element by element: a <4 x float> add becomes
+    v_pk_add_f32, which costs more beside MFMAs than two v_add_f32."""
+    for qt in range(nqt):
+        add("add", f"f32x4 rv{qt}; " + " ".join(f"rv{qt}[{e}] = {dqo[qt]}[{e}] + rold{qt}[{e}];" for e in range(4)), tag=f"RA{qt}")
+    add("vaddr", f"const unsigned rvo = BWD1W_RVO(wsoff + s_redoff{s});", tag="RVO")
+    for qt in range(nqt):
+        off = f" + {qt * WS_QT}u" if qt else ""
+        add("store", f"__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rv{qt}), rsWs, rvo{off}, 0, BWD1W_WS_ST_AUX);",
+            tag=f"RST{qt if nqt > 1 else ''}")
+
+
+def reload_rows(add, after, nx, lse, dlt, qrows, orows):
+    """Row constants and Q / dO row fragments of the next sub-step (ring offsets s_pc<nx> / s_x<nx>), once their last reader
+    `after` has been issued."""
+    add("vaddr", f"const unsigned pc_ = a_const + s_pc{nx};", after=after, tag="PC")
+    add("vaddr", f"const unsigned pr_ = a_row + s_x{nx};", after=after, tag="PR")
+    for G in range(4):
+        for v, base, t in ((lse, 0, "a"), (dlt, 256, "d")):
+            add("ldsr", f"{{ const f32x4 c_ = lds_ld<f32x4>(pc_ + {base + 32 * G}); "
+                        + " ".join(f"{v}[{4 * G + e}] = c_[{e}];" for e in range(4)) + " }", after=after, tag=f"LC{t}{G}")
+    for ks, (q, o) in enumerate(zip(qrows, orows)):
+        add("ldsr", f"{q} = lds_ld<bf16x8>(pr_ ^ {32 * ks}u);", after=after, tag=f"LQ{ks}")
+        add("ldsr", f"{o} = lds_ld<bf16x8>((pr_ ^ {32 * ks}u) + (OR_ - QR));", after=after, tag=f"LO{ks}")
+
+
+def softmax_half(add, sa, dp, half, wimg):
+    """exp2, dS = P * dP, the bf16 packs and the dS image write (at byte wimg) of 8 of a lane's 16 scores."""
+    e0, pf, dsf = 8 * half, f"pf{half}", f"dsf{half}"
+    for e in range(e0, e0 + 8):
+        add("exp", f"{sa}[{e}] = fast_exp2({sa}[{e}]);", tag=f"E{e}")
+    for e in range(e0, e0 + 8):
+        add("mul", f"{dp}[{e}] = {sa}[{e}] * {dp}[{e}];", tag=f"MU{e}")
+    for v, src, t in ((pf, sa, "CP"), (dsf, dp, "CD")):
+        for i in range(4):
+            add("cvt", f"{v}[{i}] = pack2bf({src}[{e0 + 2 * i}], {src}[{e0 + 2 * i + 1}]);", tag=f"{t}{4 * half + i}")
+    for k in range(2):
+        add("ldsw8", f"lds_st<u32x2>((a_imgw ^ {32 * half + 16 * k}u) + {wimg}, u32x2{{{dsf}[{2 * k}], {dsf}[{2 * k + 1}]}});", tag=f"WR{half}{k}")
+
+
 def sub_step(s):
     """Returns the list of bundles [(mfma Op or None, [filler Ops])] of sub-step s (0 / 1) of a tile."""
     cur_par, nxt_par = ("a", "b") if s == 0 else ("b", "a")       # parity of the transposed fragments (qT / oT)
     prev_par = nxt_par
     bundles = []
-    issued_m = {"MD(7)"} if False else set()     # MFMA tags issued so far in this sub-step
+    issued_m = set()     # MFMA tags issued so far in this sub-step
+    img_buf = 512 * 64   # bytes of one dS image: [512 keys][32 queries] bf16
 
     def mfma_acc(acc, a, b, tag):
         return Op("mfma", f"MFMA_ACC({acc}, {a}, {b});", tag)
@@ -128,78 +193,40 @@ def sub_step(s):
         dj = list(range(4 * g, 4 * g + 4))
         for j in dj:
             c = "zero4" if j == 0 else dqn
-            mf.append(Op("mfma", f"{dqn} = mfma16(kT[{j}], cat4(bj{j}l, bj{j}h), {c});", f"MD({j})"))
+            mf.append(Op("mfma", f"{dqn} = mfma16(kT[{j}], cat4(bj{j}q0l, bj{j}q0h), {c});", f"MD({j})"))
         # ---- fillers in dependency order.  Entries: (Op, not_before_mfma_tag or None)
         F = []
 
         def add(kind, code, after=None, tag=""):
             F.append((Op(kind, code, tag), after))
 
-        rb = ((s + 1) % 2) * IMG_BUF               # image of the previous sub-step
-        wb = s * IMG_BUF                           # image this sub-step writes
-
-        def rd(j):
-            add("ldsr", f"const bf16x4 bj{j}l = lds_tr_ld(a_imglo + {rb + j * 2048});", tag=f"RD{j}l")
-            add("ldsr", f"const bf16x4 bj{j}h = lds_tr_ld(a_imghi + {rb + j * 2048});", tag=f"RD{j}h")
-
+        rb = ((s + 1) % 2) * img_buf               # image of the previous sub-step
+        wb = s * img_buf                           # image this sub-step writes
+        nx = "1" if s == 0 else "n"
         if g == 0:
             for j in range(4):
-                rd(j)
-            # write-out of the tile finished in the previous sub-step: + workspace value of the earlier key blocks -> workspace
-            add("vaddr", f"const unsigned ao = a_old + s_oldr;", tag="AO")
-            add("ldsr", f"const f32x4 rold = lds_ld<f32x4>(ao + {s * 4096});", tag="ROLD")
+                image_reads(add, j, rb, 1)
+            old_reads(add, s, 1)
         for half in range(2):
-            e0 = 8 * half
-            pf, dsf = f"pf{half}", f"dsf{half}"
-            if half == 1 and g == 2:   # listed first, placed as soon as A(3) has been issued
-                # next sub-step's row constants and row fragments: A(3) (issued in this group-step) was the last reader of the old ones
-                nx = "1" if s == 0 else "n"
-                add("vaddr", f"const unsigned pc_ = a_const + s_pc{nx};", after="AP1(3)", tag="PC")
-                add("vaddr", f"const unsigned pr_ = a_row + s_x{nx};", after="AP1(3)", tag="PR")
-                for G in range(4):
-                    add("ldsr", f"{{ const f32x4 c_ = lds_ld<f32x4>(pc_ + {32 * G}); lse_{nxt_par}[{4 * G}] = c_[0]; lse_{nxt_par}[{4 * G + 1}] = c_[1]; "
-                                f"lse_{nxt_par}[{4 * G + 2}] = c_[2]; lse_{nxt_par}[{4 * G + 3}] = c_[3]; }}", after="AP1(3)", tag=f"LCa{G}")
-                    add("ldsr", f"{{ const f32x4 c_ = lds_ld<f32x4>(pc_ + {256 + 32 * G}); dlt_{nxt_par}[{4 * G}] = c_[0]; dlt_{nxt_par}[{4 * G + 1}] = c_[1]; "
-                                f"dlt_{nxt_par}[{4 * G + 2}] = c_[2]; dlt_{nxt_par}[{4 * G + 3}] = c_[3]; }}", after="AP1(3)", tag=f"LCd{G}")
-                add("ldsr", f"qrow{nxt_par}0 = lds_ld<bf16x8>(pr_);", after="AP1(3)", tag="LQ0")
-                add("ldsr", f"orow{nxt_par}0 = lds_ld<bf16x8>(pr_ + (OR_ - QR));", after="AP1(3)", tag="LO0")
-                add("ldsr", f"qrow{nxt_par}1 = lds_ld<bf16x8>(pr_ ^ 32u);", after="AP1(3)", tag="LQ1")
-                add("ldsr", f"orow{nxt_par}1 = lds_ld<bf16x8>((pr_ ^ 32u) + (OR_ - QR));", after="AP1(3)", tag="LO1")
-            for e in range(e0, e0 + 8):
-                add("exp", f"{sa}[{e}] = fast_exp2({sa}[{e}]);", tag=f"E{e}")
-            for e in range(e0, e0 + 8):
-                if e % 2 == 0:
-                    add("mul", f"\n#ifdef BWD1W_PKMUL\n  {{ const f32x2 t_ = f32x2{{{sa}[{e}], {sa}[{e + 1}]}} * f32x2{{{dp}[{e}], {dp}[{e + 1}]}}; "
-                               f"{dp}[{e}] = t_[0]; {dp}[{e + 1}] = t_[1]; }}\n#else\n  {dp}[{e}] = {sa}[{e}] * {dp}[{e}];\n#endif\n ", tag=f"MU{e}")
-                else:
-                    add("mul", f"\n#ifndef BWD1W_PKMUL\n  {dp}[{e}] = {sa}[{e}] * {dp}[{e}];\n#endif\n ", tag=f"MU{e}")
-            for i in range(4):
-                add("cvt", f"{pf}[{i}] = pack2bf({sa}[{e0 + 2 * i}], {sa}[{e0 + 2 * i + 1}]);", tag=f"CP{4 * half + i}")
-            for i in range(4):
-                add("cvt", f"{dsf}[{i}] = pack2bf({dp}[{e0 + 2 * i}], {dp}[{e0 + 2 * i + 1}]);", tag=f"CD{4 * half + i}")
-            add("ldsw8", f"lds_st<u32x2>((a_imgw ^ {32 * half}u) + {wb + g * 32 * 64}, u32x2{{{dsf}[0], {dsf}[1]}});", tag=f"WR{half}0")
-            add("ldsw8", f"lds_st<u32x2>((a_imgw ^ {32 * half + 16}u) + {wb + g * 32 * 64}, u32x2{{{dsf}[2], {dsf}[3]}});", tag=f"WR{half}1")
+            if half == 1 and g == 2:   # listed first, placed as soon as A(3), the last reader of the old ones, has been issued
+                reload_rows(add, "AP1(3)", nx, f"lse_{nxt_par}", f"dlt_{nxt_par}", [f"qrow{nxt_par}{ks}" for ks in range(2)],
+                            [f"orow{nxt_par}{ks}" for ks in range(2)])
+            softmax_half(add, sa, dp, half, wb + g * IMG_KSTEP)
             if half == 0 and g == 0:
-                dqo = "dqB" if s == 0 else "dqA"       # the tile finished in the previous sub-step
-                # element by element: a <4 x float> add becomes v_pk_add_f32, which costs more beside MFMAs than two v_add_f32
-                add("add", f"f32x4 rv; rv[0] = {dqo}[0] + rold[0]; rv[1] = {dqo}[1] + rold[1]; rv[2] = {dqo}[2] + rold[2]; rv[3] = {dqo}[3] + rold[3];", tag="RA0")
-                add("vaddr", f"const unsigned rvo = BWD1W_RVO(wsoff + s_redoff{s});", tag="RVO")
-                add("store", "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rv), rsWs, rvo, 0, BWD1W_WS_ST_AUX);", tag="RST")
+                write_out(add, s, 1, ["dqB" if s == 0 else "dqA"])       # the tile finished in the previous sub-step
             if half == 1 and g < 3:
                 for j in range(4 * g + 4, 4 * g + 8):
-                    rd(j)
+                    image_reads(add, j, rb, 1)
             if half == 0 and g == 1 and s == 0:
                 add("dma", "issue_tile();", tag="DMA")
             if half == 1 and g == 3:
-                nx = "1" if s == 0 else "n"
                 add("vaddr", f"const unsigned pl_ = a_trlo + s_x{nx};", tag="PL")
                 add("vaddr", f"const unsigned ph_ = a_trhi + s_x{nx};", tag="PH")
                 for ss in range(2):
                     add("ldsr", f"qT{nxt_par}{ss} = cat4(lds_tr_ld(pl_ + {ss * 16 * 64}), lds_tr_ld(ph_ + {ss * 16 * 64}));", tag=f"LTq{ss}")
                     add("ldsr", f"oT{nxt_par}{ss} = cat4(lds_tr_ld(pl_ + {ss * 16 * 64} + (OR_ - QR)), lds_tr_ld(ph_ + {ss * 16 * 64} + (OR_ - QR)));",
                         tag=f"LTo{ss}")
-        # the two-read fillers above count double
-        # ---- merge: deal the fillers to the MFMA slots by cost
+        # (the two-read fillers above count double in merge)
         need = {  # MFMA tag -> filler tags that must precede it
             f"CV0({g})": ["CP3"], f"CK0({g})": ["CD3"],
         }
@@ -209,7 +236,6 @@ def sub_step(s):
     return bundles
 
 
-
 def sub_step64(s):
     """head_dim 64: a wave owns 64 keys (two 32-key groups) of a 256-key block; S / dP take 4 k-steps of 16 head dims, dV^T / dK^T
     two 32-wide head-dim blocks each; the wave's part of dQ^T[64][32] is head-dim tile `wid` (16 dims) of BOTH 16-query tiles over
@@ -217,13 +243,14 @@ def sub_step64(s):
     group-steps per sub-step.  Register economy (one set of row constants / row fragments / first-half transposed fragments,
     reloaded as soon as their last reader has been issued; only the second-half transposed fragments, which the C1 MFMAs of the
     next group-step still read, alternate with the sub-step)."""
-    cur, nxt = ("a", "b") if s == 0 else ("b", "a")
     bundles = []
     issued_m = set()
     dqn = "dqA" if s == 0 else "dqB"
     dqo = "dqB" if s == 0 else "dqA"
-    rb = ((s + 1) % 2) * IMG_BUF64
-    wb = s * IMG_BUF64
+    img_buf = 256 * 64                             # bytes of one dS image: [256 keys][32 queries] bf16
+    rb = ((s + 1) % 2) * img_buf
+    wb = s * img_buf
+    nx = "1" if s == 0 else "n"
     for g in range(2):
         X, Y = ("A", "B") if g == 0 else ("B", "A")
         gp = 1 - g                                          # previous group (of the previous sub-step when g == 0)
@@ -245,19 +272,11 @@ def sub_step64(s):
         def add(kind, code, after=None, tag=""):
             F.append((Op(kind, code, tag), after))
 
-        def rd(j, after):
-            for qt in range(2):
-                x = f" ^ 32u" if qt else ""
-                add("ldsr", f"const bf16x4 bj{j}q{qt}l = lds_tr_ld((a_imglo{x}) + {rb + j * 2048});", after=after, tag=f"RD{j}q{qt}l")
-                add("ldsr", f"const bf16x4 bj{j}q{qt}h = lds_tr_ld((a_imghi{x}) + {rb + j * 2048});", after=after, tag=f"RD{j}q{qt}h")
-
         # image reads of the D stage: two k-steps at a time, ~6 MFMA slots ahead of their consumers (register economy)
         for j in range(4 * g, 4 * g + 4):
-            rd(j, f"AS1({gn})" if j % 4 < 2 else f"AS3({gn})")
+            image_reads(add, j, rb, 2, after=f"AS1({gn})" if j % 4 < 2 else f"AS3({gn})")
         if g == 0:
-            add("vaddr", "const unsigned ao = a_old + s_oldr;", tag="AO")
-            for qt in range(2):
-                add("ldsr", f"const f32x4 rold{qt} = lds_ld<f32x4>(ao + {(s * 2 + qt) * 4096});", tag=f"ROLD{qt}")
+            old_reads(add, s, 2)
             # second-half transposed fragments of THIS sub-step (one set: the C1 MFMAs just issued were the last readers of the
             # previous sub-step's; the first reader of these is C1 of the next group-step)
             add("vaddr", f"const unsigned pl1_ = a_trlo + s_x{s};", after="CK1b(1)", tag="PL1")
@@ -268,43 +287,15 @@ def sub_step64(s):
                 add("ldsr", f"oT1d{d} = cat4(lds_tr_ld((pl1_ ^ {64 * d}u) + {16 * 128} + (OR_ - QR)), lds_tr_ld((ph1_ ^ {64 * d}u) + {16 * 128} + (OR_ - QR)));",
                     after="CK1b(1)", tag=f"LT1o{d}")
         for half in range(2):
-            e0 = 8 * half
-            pf, dsf = f"pf{half}", f"dsf{half}"
-            if half == 1 and g == 0:
-                # next sub-step's row constants and row fragments: A(1), issued in this group-step, was the last reader of the old ones
-                nx = "1" if s == 0 else "n"
-                add("vaddr", f"const unsigned pc_ = a_const + s_pc{nx};", after="AP3(1)", tag="PC")
-                add("vaddr", f"const unsigned pr_ = a_row + s_x{nx};", after="AP3(1)", tag="PR")
-                for G in range(4):
-                    add("ldsr", f"{{ const f32x4 c_ = lds_ld<f32x4>(pc_ + {32 * G}); lse_t[{4 * G}] = c_[0]; lse_t[{4 * G + 1}] = c_[1]; "
-                                f"lse_t[{4 * G + 2}] = c_[2]; lse_t[{4 * G + 3}] = c_[3]; }}", after="AP3(1)", tag=f"LCa{G}")
-                    add("ldsr", f"{{ const f32x4 c_ = lds_ld<f32x4>(pc_ + {256 + 32 * G}); dlt_t[{4 * G}] = c_[0]; dlt_t[{4 * G + 1}] = c_[1]; "
-                                f"dlt_t[{4 * G + 2}] = c_[2]; dlt_t[{4 * G + 3}] = c_[3]; }}", after="AP3(1)", tag=f"LCd{G}")
-                for ks in range(4):
-                    add("ldsr", f"qrow{ks} = lds_ld<bf16x8>(pr_ ^ {32 * ks}u);", after="AP3(1)", tag=f"LQ{ks}")
-                    add("ldsr", f"orow{ks} = lds_ld<bf16x8>((pr_ ^ {32 * ks}u) + (OR_ - QR));", after="AP3(1)", tag=f"LO{ks}")
-            for e in range(e0, e0 + 8):
-                add("exp", f"{sa}[{e}] = fast_exp2({sa}[{e}]);", tag=f"E{e}")
-            for e in range(e0, e0 + 8):
-                add("mul", f"{dp}[{e}] = {sa}[{e}] * {dp}[{e}];", tag=f"MU{e}")
-            for i in range(4):
-                add("cvt", f"{pf}[{i}] = pack2bf({sa}[{e0 + 2 * i}], {sa}[{e0 + 2 * i + 1}]);", tag=f"CP{4 * half + i}")
-            for i in range(4):
-                add("cvt", f"{dsf}[{i}] = pack2bf({dp}[{e0 + 2 * i}], {dp}[{e0 + 2 * i + 1}]);", tag=f"CD{4 * half + i}")
-            add("ldsw8", f"lds_st<u32x2>((a_imgw ^ {32 * half}u) + {wb + g * 32 * 64}, u32x2{{{dsf}[0], {dsf}[1]}});", tag=f"WR{half}0")
-            add("ldsw8", f"lds_st<u32x2>((a_imgw ^ {32 * half + 16}u) + {wb + g * 32 * 64}, u32x2{{{dsf}[2], {dsf}[3]}});", tag=f"WR{half}1")
+            if half == 1 and g == 0:   # A(1), issued in this group-step, was the last reader of the old ones
+                reload_rows(add, "AP3(1)", nx, "lse_t", "dlt_t", [f"qrow{ks}" for ks in range(4)], [f"orow{ks}" for ks in range(4)])
+            softmax_half(add, sa, dp, half, wb + g * IMG_KSTEP)
             if half == 0 and g == 0:
-                for qt in range(2):
-                    add("add", f"f32x4 rv{qt}; rv{qt}[0] = {dqo}{qt}[0] + rold{qt}[0]; rv{qt}[1] = {dqo}{qt}[1] + rold{qt}[1]; "
-                               f"rv{qt}[2] = {dqo}{qt}[2] + rold{qt}[2]; rv{qt}[3] = {dqo}{qt}[3] + rold{qt}[3];", tag=f"RA{qt}")
-                add("vaddr", f"const unsigned rvo = BWD1W_RVO(wsoff + s_redoff{s});", tag="RVO")
-                add("store", "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rv0), rsWs, rvo, 0, BWD1W_WS_ST_AUX);", tag="RST0")
-                add("store", "__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rv1), rsWs, rvo + 4096u, 0, BWD1W_WS_ST_AUX);", tag="RST1")
+                write_out(add, s, 2, [f"{dqo}0", f"{dqo}1"])
             if half == 0 and g == 1 and s == 0:
                 add("dma", "issue_tile();", tag="DMA")
         if g == 1:
             # first-half transposed fragments of the next sub-step: C0(1) of this one was their last reader
-            nx = "1" if s == 0 else "n"
             add("vaddr", f"const unsigned pl0_ = a_trlo + s_x{nx};", after="CK0b(1)", tag="PL0")
             add("vaddr", f"const unsigned ph0_ = a_trhi + s_x{nx};", after="CK0b(1)", tag="PH0")
             for d in range(2):
@@ -317,31 +308,47 @@ def sub_step64(s):
         merge(mf, F, need, bundles, issued_m)
     return bundles
 
+
+# per head dim: the bundle table, what the drains keep of it, and the layout constants the tables bake into offsets
+HEAD_DIMS = {
+    32: dict(table=sub_step, last_c1=("CV1(3)", "CK1(3)"), drains=("SLIM0", "SLIM1", "TINY0", "TINY1"),
+             layout=f"IMG_BUF == {512 * 64} && IMG_KSTEP == {IMG_KSTEP} && OLD_QUAD == {OLD_QUAD} && 16 * T::ROWB == {16 * 64}"),
+    # (the head_dim 64 kernel has no full-drain copy: a second copy costs it register spills)
+    64: dict(table=sub_step64, last_c1=("CV1a(1)", "CV1b(1)", "CK1a(1)", "CK1b(1)"), drains=("SLIM1", "TINY0"),
+             layout=f"IMG_BUF == {256 * 64} && IMG_KSTEP == {IMG_KSTEP} && OLD_QUAD == {OLD_QUAD} && WS_QT == {WS_QT} && 16 * T::ROWB == {16 * 128}"),
+}
+
+
 def guard(o):
-    """Timing-only ablation switches (-DABL_...: results are wrong, the instruction stream is otherwise unchanged)."""
+    """Timing-only ablation switches (-DABL_...: results are wrong, the instruction stream is otherwise unchanged): the statement
+    goes into the macro of its switch (csrc/attn_bwd1w.hpp), which expands to it or to nothing."""
     t = o.tag
     g = None
-    if t.startswith("WR"): g = "ABL_NO_WR"
-    elif t in ("AO", "RVO") or t.startswith(("RA", "ROLD", "RST")): g = "ABL_NO_WP"
-    elif t.startswith("E") and t[1:].isdigit(): g = "ABL_NO_EXP"
-    elif t.startswith("CV") or t.startswith("CK"): g = "ABL_NO_ACC"
-    elif t.startswith("MD") or t.startswith("RD"): g = "ABL_NO_MD"
-    if g is None:
-        return o.code
-    if t.startswith("RST"):
-        return f"\n#if !defined({g}) && !defined(ABL_NO_RST)\n  {o.code}\n#endif\n "
-    return f"\n#ifndef {g}\n  {o.code}\n#endif\n "
+    if t.startswith("RST"): g = "ABL_RST"
+    elif t.startswith("WR"): g = "ABL_WR"
+    elif t in ("AO", "RVO") or t.startswith(("RA", "ROLD")): g = "ABL_WP"
+    elif t.startswith("E") and t[1:].isdigit(): g = "ABL_EXP"
+    elif t.startswith("CV") or t.startswith("CK"): g = "ABL_ACC"
+    elif t.startswith("MD") or t.startswith("RD"): g = "ABL_MD"
+    return o.code if g is None else f"{g}({o.code})"
 
 
 def emit(hd=32):
-    out = ["// GENERATED by tools/gen_attn_bwd1w.py -- do not edit; the bundle order is the instruction order (see the generator's header)."]
+    cfg = HEAD_DIMS[hd]
+    tiles = [cfg["table"](s) for s in range(2)]
+    ops = [o for bl in tiles for m, fill in bl for o in fill]
+    out = ["// GENERATED by tools/gen_attn_bwd1w.py -- do not edit; the bundle order is the instruction order (see the generator's header).",
+           "// What the kernel's counted vmcnt ring (BWD1W_WAIT) and LDS layout must agree with: the vector-memory operations placed below",
+           "// and the constants baked into their offsets.",
+           f"static_assert(NST == {sum(o.kind == 'store' for o in ops)}, \"write-out stores placed per tile\");",
+           f"static_assert(VM_ITER == NST + {sum(o.code.count('issue_tile()') for o in ops)} * (NP + 1 + NOLDREQ), \"issue_tile() calls placed per tile: one\");",
+           f"static_assert({cfg['layout']}, \"layout constants baked into the offsets of this body\");"]
     report = []
-    for s in range(2):
+    for s, bl in enumerate(tiles):
         out.append(f"// ======================== sub-step {s} of the tile ========================")
         if s == 1:
             out.append("#ifndef BWD1W_ONLY_SUBSTEP0     // (the half iteration behind the loop: see the kernels)")
         out.append("{")
-        bl = sub_step(s) if hd == 32 else sub_step64(s)
         nst = 0
         for bi, (m, fill) in enumerate(bl):
             if m and (m.tag.startswith(("CV1(", "CV0(", "CV1a", "CV0a"))):
@@ -375,31 +382,31 @@ def emit(hd=32):
 def emit_drain(hd=32):
     """The pipeline drain behind the last real sub-step X of a key block, instead of padding sub-steps run in full: SLIM(s) is
     sub-step s reduced to what still has an effect -- dV^T / dK^T of X's last group (second half), the dQ^T product of X from its dS
-    image, the write-out of the tile before -- and TINY(s) is the last write-out alone.  Same instruction order as the full body."""
-    out = ["// GENERATED by tools/gen_attn_bwd1w.py -- do not edit.  Selected by the kernels with BWD1W_DRAIN_SLIM0 / _SLIM1 / _TINY0 / _TINY1."]
-    last_c1 = ("CV1(3)", "CK1(3)") if hd == 32 else ("CV1a(1)", "CV1b(1)", "CK1a(1)", "CK1b(1)")
+    image, the write-out of the tile before -- and TINY(s) is the last write-out alone.  Same instruction order as the full body.
+    Only the variants the kernel of this head dim includes are emitted."""
+    cfg = HEAD_DIMS[hd]
+    out = ["// GENERATED by tools/gen_attn_bwd1w.py -- do not edit.  Selected by the kernel with " + " / ".join("BWD1W_DRAIN_" + d for d in cfg["drains"]) + "."]
     wo = lambda t: t in ("AO", "RVO") or t.startswith(("ROLD", "RA", "RST"))
-    for kind in ("SLIM", "TINY"):
-        for s in range(2):
-            out.append(f"#ifdef BWD1W_DRAIN_{kind}{s}")
-            out.append("{")
-            bl = sub_step(s) if hd == 32 else sub_step64(s)
-            for bi, (m, fill) in enumerate(bl):
-                keep_m = m is not None and kind == "SLIM" and (m.tag in last_c1 or m.tag.startswith("MD("))
-                keep_f = [o for o in fill if wo(o.tag) or (kind == "SLIM" and o.tag.startswith("RD"))]
-                if not keep_m and not keep_f:
-                    continue
-                out.append(f"  // from bundle {bi}")
-                if keep_m:
-                    out.append("  " + guard(m))
-                    out.append("  __builtin_amdgcn_sched_barrier(0);")
-                for o in keep_f:
-                    out.append("  " + guard(o))
+    for name in cfg["drains"]:
+        kind, s = name[:4], int(name[4])
+        out.append(f"#ifdef BWD1W_DRAIN_{name}")
+        out.append("{")
+        for bi, (m, fill) in enumerate(cfg["table"](s)):
+            keep_m = m is not None and kind == "SLIM" and (m.tag in cfg["last_c1"] or m.tag.startswith("MD("))
+            keep_f = [o for o in fill if wo(o.tag) or (kind == "SLIM" and o.tag.startswith("RD"))]
+            if not keep_m and not keep_f:
+                continue
+            out.append(f"  // from bundle {bi}")
+            if keep_m:
+                out.append("  " + guard(m))
                 out.append("  __builtin_amdgcn_sched_barrier(0);")
-            if kind == "SLIM":
-                out.append("  SUBSTEP_END(0);     // every wave is done with the dS image: the epilogue may reuse the region")
-            out.append("}")
-            out.append("#endif")
+            for o in keep_f:
+                out.append("  " + guard(o))
+            out.append("  __builtin_amdgcn_sched_barrier(0);")
+        if kind == "SLIM":
+            out.append("  SUBSTEP_END(0);     // every wave is done with the dS image: the epilogue may reuse the region")
+        out.append("}")
+        out.append("#endif")
     return "\n".join(out) + "\n"
 
 
